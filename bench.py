@@ -2,6 +2,7 @@
 """bench.py — forward images/sec of the BASELINE.json workloads on N MI355X GPUs of one node.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet50|vit_b16|swin_b] [--no-also]
+                    [--dump-outputs DIR]
 
 Headline (config.workload): BASELINE.json configs[1] — ResNet-50 fp16 forward, batch 256 per GPU, synthetic
 ImageNet-shaped input already resident in HBM, seeded random weights of the real architecture.  A "step" is one forward
@@ -25,6 +26,9 @@ SURVEY.md §8e); scaling is weak.  Prints ONE JSON line (rank 0).  On the same l
                 hands one GPU's share of the host, 16 cores, whatever os.cpu_count() says.  `all_affinity_cores` (ResNet-50
                 only): the same protocol on every core of the affinity mask, in a CPU-only child process with a 75 s budget
                 (value null + the reason when the box cannot finish it: see cpu_baseline()).
+  --dump-outputs DIR  after the run, the logits of the LAST timed step of every workload measured (the headline and, if run,
+                also's), as DIR/<workload>_logits.npy in float32: with the same arguments the inputs and weights are the same
+                seeded values in every run, so two builds can be compared output for output.
 Progress lines go to stderr ([bench] ...), the JSON line alone to stdout; the default run takes 2 - 4 minutes.
 """
 import argparse
@@ -38,7 +42,7 @@ import time
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
-import numpy as np  # noqa: E402,F401
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
@@ -223,12 +227,16 @@ def measure(workload, batch, steps, warmup, dev, rank, world, graph=True, probe_
     if world > 1:
         assert last[0] is not None and last[0].shape[0] == batch * world and torch.isfinite(last[0].float()).all(), "gathered logits"
         assert torch.equal(last[0][rank * batch:(rank + 1) * batch].to(y.device), y), "this rank's rows of the gathered logits"
+    # what a caller of the timed path receives from its last step (the gathered logits for N > 1), copied to the host before
+    # the secondary passes below replay the same graph
+    logits = (last[0] if world > 1 else y).float().cpu().numpy()
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
     median_ms = per_step[steps // 2] if steps % 2 else 0.5 * (per_step[steps // 2 - 1] + per_step[steps // 2])
     ms_per_step = 1e3 * dt / steps
     value = batch * world * steps / dt
     out = {"value": round(value, 1), "ms_per_step": round(ms_per_step, 4),
-           "ms_per_step_median": round(median_ms, 4), "value_at_median": round(batch * world / (median_ms * 1e-3), 1)}
+           "ms_per_step_median": round(median_ms, 4), "value_at_median": round(batch * world / (median_ms * 1e-3), 1),
+           "logits": logits}
 
     if rank == 0:
         _, _, flop_img, bytes_img, wbytes, bound = WORK[workload]
@@ -315,6 +323,24 @@ def measure(workload, batch, steps, warmup, dev, rank, world, graph=True, probe_
     return out, params, model
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: one float32 DIR/<name>.npy per array, DUMP_BUDGET_BYTES in all.  An array over its even share
+    of the budget keeps a fixed sample of its rows (seed 0, in row order), so two runs with the same arguments dump the
+    same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays) - 4096         # (room for the .npy header)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        if arr.nbytes > share:
+            keep = share // (arr.nbytes // arr.shape[0])
+            arr = arr[np.sort(np.random.default_rng(0).choice(arr.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+        print(f"[bench] wrote {os.path.join(out_dir, name)}.npy {tuple(arr.shape)} float32", file=sys.stderr, flush=True)
+
+
 def main():
     if len(sys.argv) >= 4 and sys.argv[1] == "--cpu-baseline-child":
         cpu_baseline_child(sys.argv[2], int(sys.argv[3]))
@@ -330,7 +356,11 @@ def main():
     ap.add_argument("--option", action="append", default=[], metavar="NAME=0|1", help="engine.set_option(NAME, value) before building")
     ap.add_argument("--no-probe", action="store_true", help="timed region only: no instrumented per-kernel pass, no two_in_flight run (profiling runs)")
     ap.add_argument("--no-graph", action="store_true", help="launch kernel by kernel instead of replaying a hipGraph")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step of every measured workload as DIR/<workload>_logits.npy (float32)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.batch is None:
         a.batch = WORK[a.workload][1]
 
@@ -368,6 +398,7 @@ def main():
     }
     if rank == 0:
         line["roofline"] = res["roofline"]
+        dumps = {f"{a.workload}_logits": res["logits"]}
         if world == 1 and a.workload == "resnet50" and not a.no_also:
             del model
             torch.cuda.empty_cache()
@@ -378,6 +409,7 @@ def main():
                 r, p2, m2 = measure(wl, b, min(a.steps, 30), min(a.warmup, 5), dev, 0, 1, graph=not a.no_graph)
                 del m2
                 torch.cuda.empty_cache()
+                dumps[f"{wl}_logits"] = r["logits"]
                 also.append({"workload": LABEL[wl].format(b=b), "value": r["value"], "unit": "images/sec",
                              "ms_per_step": r["ms_per_step"], "ms_per_step_median": r["ms_per_step_median"],
                              "steps": min(a.steps, 30), "warmup": min(a.warmup, 5), "roofline": r["roofline"],
@@ -389,6 +421,8 @@ def main():
             line["also"] = also
         if world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.workload, params)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, dumps)
     if world > 1:
         dist.barrier()
     if rank == 0:
