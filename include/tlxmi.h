@@ -401,7 +401,8 @@ int tlxmi_softmax_rows(const void* x, void* y, int dtype, int64_t rows, int C, i
 /* A transformer MLP as one launch (swin_transformer.py:62-82, :335): out = fc2(gelu(fc1(x) + b1)) + b2 + res; the hidden activations
  * (rows x hidden) never leave the CU.  fp16; x [rows][x_ld] (K channels), res / out [rows][ld] (N channels); w1 / w2 packed by
  * tlxmi_pack_filter (1 x 1) as [hidden][K] and [N][hidden].  Compiled for K = N = 128, hidden a multiple of 64 up to 2048 (Swin-B
- * stage 1); tlxmi_mlp_seam_supported answers 1 when a shape is taken. */
+ * stage 1); tlxmi_mlp_seam_supported answers 1 when a shape is taken.  It is shape-only: the call also needs rows * {x_ld, res_ld,
+ * out_ld} * 2 < 2^31 (each tensor within the 2 GiB the 32-bit buffer offsets address) and returns TLXMI_ERR_UNSUPPORTED otherwise. */
 int tlxmi_mlp_seam_supported(int dtype, int K, int hidden, int N);
 int tlxmi_mlp_seam(int dtype, int64_t rows, int K, int hidden, int N, const void* x, int x_ld, const void* w1_packed, const float* bias1,
                    const void* w2_packed, const float* bias2, const void* res, int res_ld, void* out, int out_ld, void* stream);
@@ -423,7 +424,8 @@ int tlxmi_mlp_seam(int dtype, int64_t rows, int K, int hidden, int N, const void
  * Both run on the 256 x 256 GEMM kernels (the persistent one; a residual with K < 704 and launches of few tiles on its
  * one-tile-per-workgroup form): fp16, Cout % 32 == 0, Cout >= 256, K >= 128, K <= 1024 for the consumer;
  * tlxmi_linear_ln_supported(dtype, rows, K, Cout, act, with_res) — with_res 0: the consumer, 1: a producer with a residual, 2: a producer
- * without (a producer's Cout, the consumer's K <= 1024: the LayerNorm's width) — answers 1 when the shape is taken, otherwise the calls return
+ * without (a producer's Cout, the consumer's K <= 1024: the LayerNorm's width) — answers 1 when the shape is taken with dense operands
+ * (x_ld = K, y_ld = res_ld = Cout; rows * K * 2, rows * Cout * 2 and the rows * 32 bytes of statistics each < 2^31), otherwise the calls return
  * TLXMI_ERR_UNSUPPORTED and the caller keeps tlxmi_layernorm + tlxmi_conv2d.  `flags`: TLXMI_PLAN_SHARED_* or 0.
  * ---------------------------------------------------------------------------------------- */
 int tlxmi_linear_ln_supported(int dtype, int64_t rows, int K, int Cout, int act, int with_res);

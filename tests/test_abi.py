@@ -225,3 +225,40 @@ def test_product_loader_ignores_TLXMI_LIB_and_ships_no_tuning_only_kernel():
     assert b"gemm_w4" not in blob
     if os.path.exists(_lib.TUNE_LIB_PATH):
         assert "gemm_w4" in subprocess.check_output(["nm", "-C", _lib.TUNE_LIB_PATH]).decode()
+
+
+def test_fold_and_seam_predicates_keep_their_promise_at_the_2_GiB_limit():
+    """`supported == 1` means the call is taken: at the first row count whose dense fp16 operands reach 2^31 bytes the predicates of the
+    folded LayerNorm (tlxmi_linear_ln_supported) and of the Mlp seam (engine.mlp_seam_supported over the shape-only
+    tlxmi_mlp_seam_supported) answer 0, one row below they answer 1, and at the limit the entry points refuse with
+    TLXMI_ERR_UNSUPPORTED before any launch (the buffers handed over are tiny)."""
+    import torch
+    from tlxcv_amd import _lib, engine as E
+    lib = _lib.load()
+    buf = (ctypes.c_char * 8192)()
+    base = ctypes.addressof(buf)
+    base += (-base) % 16
+    p, q, r, t = (ctypes.c_void_p(base + 1024 * i) for i in range(4))
+    F16, NONE, GELU = 0, 0, 6
+    big = 1 << 31
+    # (K, Cout, act, with_res): ViT-B/16 qkv and fc1 (consumers), fc2 / proj (producers with a residual), the Swin-B stage-4
+    # reduction (a producer without one)
+    for K, Cout, act, with_res in ((768, 2304, NONE, 0), (768, 3072, GELU, 0), (3072, 768, NONE, 1), (768, 768, NONE, 1),
+                                   (2048, 1024, NONE, 2)):
+        first = -(-big // (2 * max(K, Cout)))          # the first row count with a tensor of 2^31 bytes or more
+        assert (first - 1) * 2 * max(K, Cout) < big <= first * 2 * max(K, Cout)
+        assert lib.tlxmi_linear_ln_supported(F16, first - 1, K, Cout, act, with_res) == 1, (K, Cout, with_res)
+        assert lib.tlxmi_linear_ln_supported(F16, first, K, Cout, act, with_res) == 0, (K, Cout, with_res)
+        if with_res == 0:
+            rc = lib.tlxmi_linear_ln(F16, first, K, Cout, K, Cout, p, q, r, r, t, 1e-5, act, t, 0, None)
+        else:
+            rc = lib.tlxmi_linear_stats(F16, first, K, Cout, K, Cout, p, q, None, t if with_res == 1 else None, Cout if with_res == 1 else 0,
+                                        r, t, 0, None)
+        assert rc == -2, (K, Cout, with_res, rc, lib.tlxmi_last_error())
+    # Swin-B stage 1: 128 -> 512 -> 128, x and res / out of 256 bytes a row
+    first = big // 256
+    assert E.mlp_seam_supported(first - 1, 128, 512, 128, torch.float16)
+    assert not E.mlp_seam_supported(first, 128, 512, 128, torch.float16)
+    assert lib.tlxmi_mlp_seam_supported(F16, 128, 512, 128) == 1      # (shape-only)
+    assert lib.tlxmi_mlp_seam(F16, first, 128, 512, 128, p, 128, q, None, r, None, t, 128, t, 128, None) == -2
+    assert b"2 GiB" in lib.tlxmi_last_error()

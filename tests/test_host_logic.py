@@ -242,3 +242,21 @@ def test_linear_tail_plan_matches_the_round_arithmetic():
     finally:
         engine.set_option("tail_splitk", False)
         engine._cus.pop(0, None)
+
+
+def test_chunk_sizes_keep_every_chunk_below_the_2_GiB_operand_limit():
+    """engine.chunk_sizes: one chunk while batch x bytes per image stays below 2^31, else the fewest near-equal chunks that do
+    (VGG-16 fp32: 12.85 MB per image at conv1_2; ResNet-50 fp32: 3.21 MB at layer1; ViT-B/16 fp16: 1.21 MB at fc1)."""
+    from tlxcv_amd import engine as E
+    vgg, r50, vit16 = 224 * 224 * 64 * 4, 56 * 56 * 256 * 4, 197 * 3072 * 2
+    assert E.chunk_sizes(167, vgg) == [167] and E.chunk_sizes(168, vgg) == [84, 84] and E.chunk_sizes(169, vgg) == [85, 84]
+    assert E.chunk_sizes(336, vgg) == [112, 112, 112]
+    assert E.chunk_sizes(669, r50) == [335, 334] and E.chunk_sizes(1775, vit16) == [888, 887]
+    assert E.chunk_sizes(256, r50) == [256] and E.chunk_sizes(5, None) == [5] and E.chunk_sizes(5, 0) == [5]
+    for batch in (1, 2, 167, 168, 1000, 4097):
+        for per in (1 << 20, vgg, r50, vit16, (1 << 31) - 1):
+            sizes = E.chunk_sizes(batch, per)
+            assert sum(sizes) == batch and max(sizes) - min(sizes) <= 1 and max(sizes) * per < E.ACT_LIMIT
+            assert len(sizes) == 1 or -(-batch // (len(sizes) - 1)) * per >= E.ACT_LIMIT       # no fewer chunks would do
+    with pytest.raises(RuntimeError, match="2 GiB"):
+        E.chunk_sizes(2, 1 << 31)

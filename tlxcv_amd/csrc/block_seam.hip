@@ -717,7 +717,7 @@ extern "C" int tlxmi_bottleneck_seam_proj(const tlxmi_seam_desc* d, const void* 
 // A transformer MLP as ONE launch (round 5): out = fc2(gelu(fc1(x) + b1)) + b2 + res, the hidden activations never leave the CU
 // (swin_transformer.py:62-82, :335; the seam kernel above in its MLP form).  fp16; x [rows][x_ld] with K channels, res / out [rows][ld]
 // with N = K output channels; hidden = the middle width (a multiple of 64).  Compiled for K = N = 128 (stage 1 of Swin-B);
-// tlxmi_mlp_seam_supported asks first.
+// tlxmi_mlp_seam_supported asks first; it is shape-only (the 2 GiB limits on rows are checked by the call, engine.mlp_seam_supported mirrors them).
 extern "C" int tlxmi_mlp_seam_supported(int dtype, int K, int hidden, int N) {
     return (dtype == TLXMI_F16 && K == 128 && N == 128 && hidden % 64 == 0 && hidden >= 64 && hidden <= 2048 && block_seam_shape_ok(K, hidden, N)) ? 1 : 0;
 }

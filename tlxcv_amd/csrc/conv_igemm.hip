@@ -1240,6 +1240,10 @@ extern "C" int tlxmi_linear_ln_supported(int dtype, int64_t rows, int K, int Cou
     // with_res: 0 = the consumer (tlxmi_linear_ln), 1 = a producer with a residual, 2 = a producer without (tlxmi_linear_stats)
     if (act != TLXMI_ACT_NONE && !(act == TLXMI_ACT_GELU && !with_res)) return 0;
     if (with_res ? Cout > 1024 : K > 1024) return 0;      // the statistics of a row are 4 pairs, one per 256 channels of the LayerNorm's width
+    // the byte limits of fill_ln_gemm and tlxmi_linear_stats for dense operands (x_ld = K, y_ld = res_ld = Cout): every tensor of the
+    // launch, the (rows, 4, 2) fp32 statistics included, within the 2 GiB that the 32-bit buffer offsets address
+    const long long big = 1ll << 31;
+    if (rows * K * 2 >= big || rows * Cout * 2 >= big || rows * 32 >= big) return 0;
     return 1;
 }
 

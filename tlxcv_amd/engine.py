@@ -219,22 +219,100 @@ def run_halves(fn, x, plan=None):
     return fn(x)
 
 
+# Every kernel addresses a tensor through 32-bit buffer offsets: no activation operand of a launch may reach this many bytes
+# ("Sizing").  two_streams() cuts a forward's batch into chunks that stay below it.
+ACT_LIMIT = 1 << 31
+
+
+class _Oversize(Exception):
+    """Raised by _note_act() inside a sizing forward at the first operand of ACT_LIMIT bytes or more (before its launch)."""
+
+
+def _note_act(*nbytes):
+    """The largest activation operand (x / y / residual bytes of a launch) of the forward being sized by two_streams()."""
+    m = max(nbytes)
+    if m >= ACT_LIMIT:
+        raise _Oversize()
+    if m > _tls.act_max:
+        _tls.act_max = m
+
+
+def image_bytes(model, x):
+    """Bytes per image of the largest activation operand of model's forward on inputs shaped like x (at the current precision),
+    or None while it has not been measured (the first eager forward of that shape measures it; see two_streams())."""
+    return vars(model).get("_act_bytes_per_image", {}).get((tuple(x.shape[1:]), x.dtype, precision()))
+
+
+def chunk_sizes(batch, per_image):
+    """Near-equal chunks of `batch` images whose largest activation operand stays below ACT_LIMIT ([batch] when one fits)."""
+    if not per_image or batch * per_image < ACT_LIMIT:
+        return [batch]
+    cap = (ACT_LIMIT - 1) // per_image
+    if cap < 1:
+        raise RuntimeError(f"tlxcv_amd: one image needs a tensor of {per_image} bytes, beyond the 2 GiB the kernels address")
+    k = -(-batch // cap)
+    n, r = divmod(batch, k)
+    return [n + 1] * r + [n] * (k - r)
+
+
+def _sized(run, x, images):
+    """run(x) while recording its largest activation operand -> (run(x), bytes per image), `images` = the images of one launch;
+    (None, None) when an operand reached ACT_LIMIT (nothing of that size was launched)."""
+    _tls.act_max = 0
+    try:
+        y = run(x)
+        return y, -(-_tls.act_max // images)
+    except _Oversize:
+        torch.cuda.synchronize()          # what was enqueued before the refusal (on either stream) is finished and dropped
+        return None, None
+    finally:
+        _tls.act_max = None
+
+
 def two_streams(min_batch, plan=None, eager=True):
-    """Decorator of a model's forward(self, x): batches of at least `min_batch` (even) images run as run_halves().
+    """Decorator of a model's forward(self, x).
+    First the batch is cut into chunk_sizes() chunks: one, unless some activation operand of the forward would reach ACT_LIMIT
+    bytes.  The bytes per image are measured on the first eager forward of an input shape and kept on the model per (input shape,
+    dtype, precision) — a hipGraph capture, which needs that eager forward first, reuses them; a first forward that reaches the limit
+    stops before that launch and is sized on one image instead.  Then each chunk of at least `min_batch` (even) images runs as
+    run_halves(), and the logits of the chunks are joined.
     plan: None / "half" / "full" (run_halves), or a callable batch -> one of these.
-    eager=False: only while a hipGraph is being captured.  A forward of many tiny launches (MobileNetV3, EfficientNet: 150 - 250
+    eager=False: halves only while a hipGraph is being captured.  A forward of many tiny launches (MobileNetV3, EfficientNet: 150 - 250
     kernels of a few microseconds) is bound by the host when launched kernel by kernel, and two halves are twice the host work
     (MobileNetV3-small batch 256: 1.4 -> 2.3 ms eager, 1.37 -> 1.25 ms as a graph)."""
     def deco(fwd):
         import functools
 
+        def split(x):
+            return (_options["two_streams"] and x.shape[0] >= min_batch and x.shape[0] % 2 == 0 and _probe is None
+                    and (eager or torch.cuda.is_current_stream_capturing()))
+
+        def halves(self, x):
+            if split(x):
+                return run_halves(lambda h: fwd(self, h), x, plan(x.shape[0]) if callable(plan) else plan)
+            return fwd(self, x)
+
         @functools.wraps(fwd)
         def wrapper(self, x, *args, **kwargs):
-            if (_options["two_streams"] and not args and not kwargs and isinstance(x, torch.Tensor) and x.is_cuda
-                    and x.dim() == 4 and x.shape[0] >= min_batch and x.shape[0] % 2 == 0 and _probe is None
-                    and (eager or torch.cuda.is_current_stream_capturing())):
-                return run_halves(lambda h: fwd(self, h), x, plan(x.shape[0]) if callable(plan) else plan)
-            return fwd(self, x, *args, **kwargs)
+            if args or kwargs or not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4):
+                return fwd(self, x, *args, **kwargs)
+            if getattr(_tls, "act_max", None) is not None:      # inside the sizing forward of an enclosing model
+                return fwd(self, x)
+            key = (tuple(x.shape[1:]), x.dtype, precision())
+            per = image_bytes(self, x)
+            if per is None and not torch.cuda.is_current_stream_capturing():
+                y, per = _sized(lambda h: halves(self, h), x, x.shape[0] // 2 if split(x) else x.shape[0])
+                if per is None:
+                    _, per = _sized(lambda h: fwd(self, h), x[:1], 1)
+                    if per is None:
+                        raise RuntimeError("tlxcv_amd: one image of this forward needs a tensor beyond the 2 GiB the kernels address")
+                vars(self).setdefault("_act_bytes_per_image", {})[key] = per
+                if y is not None:
+                    return y
+            sizes = chunk_sizes(x.shape[0], per)
+            if len(sizes) == 1:
+                return halves(self, x)
+            return torch.cat([halves(self, c) for c in torch.split(x, sizes, 0)], 0)
         return wrapper
     return deco
 
@@ -532,6 +610,8 @@ def conv2d(x, pk, stride=1, padding=0, dilation=1, scale=None, shift=None, res=N
             return None
         out = torch.empty((N, Ho // 2, Wo // 2, pk.Cout), dtype=x.dtype, device=x.device)
     M = N * Ho * Wo
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * x.element_size(), M * out_ld * x.element_size(), M * d.res_ld * x.element_size() if res is not None else 0)
     splits = 0 if maxpool3s2 else _conv_splits(d, M, pk, x, out_ld, y_nstride, res_nstride, res_bcast)
 
     def launch():
@@ -598,6 +678,8 @@ def bottleneck_seam(t2, pk3, scale3, shift3, skip, pk1, scale1, shift1, proj=Non
     y = torch.empty((N, H, W, pk3.Cout), dtype=t2.dtype, device=t2.device)
     t1 = torch.empty((N, H, W, pk1.Cout), dtype=t2.dtype, device=t2.device)
     rows = N * H * W
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(t2.numel() * t2.element_size(), skip.numel() * skip.element_size(), y.numel() * y.element_size(), t1.numel() * t1.element_size())
     d = _lib.SeamDesc(dtype=dt_code(t2.dtype), rows=rows, K1=pk3.Cin, N1=pk3.Cout, N2=pk1.Cout, t2_ld=ld, skip_ld=skip.shape[-1],
                       y_ld=pk3.Cout, t1_ld=pk1.Cout, act=ACT_RELU)
     if proj is None:
@@ -649,6 +731,8 @@ def group_conv2d(x, pk, stride=1, padding=0, dilation=1, scale=None, shift=None,
                       y_nstride=0, res_nstride=0, act=act, act_param=float(act_param),
                       flags=(EPI_RES_AFTER_ACT if res_after_act else 0) | plan_flags())
     args = (C.byref(d), pk.groups, _p(x), _p(pk.buf), _p(scale), _p(shift), _p(res), _p(out), _stream())
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * x.element_size(), out.numel() * out.element_size(), res.numel() * res.element_size() if res is not None else 0)
     if _probe is None:
         _lib.call("tlxmi_group_conv2d", *args)
         return out
@@ -782,7 +866,10 @@ def _linear_splits(rows, K, pk, x):
 
 
 def mlp_seam_supported(rows, K, hidden, N, dtype):
-    return bool(_options["mlp_seam"] and dtype == torch.float16 and rows >= 4096 and _lib.load().tlxmi_mlp_seam_supported(F16, int(K), int(hidden), int(N)))
+    """Whether mlp_seam() takes these rows: tlxmi_mlp_seam_supported answers for the shape only, the rows of x (K channels) and of
+    res / out (N channels) must each stay under the 2 GiB the 32-bit buffer offsets address (the call refuses them otherwise)."""
+    return bool(_options["mlp_seam"] and dtype == torch.float16 and rows >= 4096 and rows * max(K, N) * 2 < (1 << 31)
+                and _lib.load().tlxmi_mlp_seam_supported(F16, int(K), int(hidden), int(N)))
 
 
 def mlp_seam(x, pk1, b1, pk2, b2, res, out=None):
@@ -797,6 +884,8 @@ def mlp_seam(x, pk1, b1, pk2, b2, res, out=None):
     if not res.is_contiguous():
         raise RuntimeError("mlp_seam: the residual must be dense")
     y = out if out is not None else torch.empty((*shp[:-1], N), dtype=x.dtype, device=x.device)
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(rows * max(K, N) * x.element_size())
     if _probe is not None:
         e0, e1 = _probe_pair()
     _lib.call("tlxmi_mlp_seam", dt_code(x.dtype), rows, K, pk1.Cout, N, _p(x), K, _p(pk1.buf), _p(b1), _p(pk2.buf), _p(b2), _p(res), N, _p(y), N, _stream())
@@ -854,6 +943,8 @@ def linear_stats(x, pk, bias=None, res=None, out=None):
         raise RuntimeError("linear_stats: the residual must be a dense tensor of the input's dtype")
     y = out if out is not None else torch.empty((*shp[:-1], pk.Cout), dtype=x.dtype, device=x.device)
     part = torch.empty((rows, 4, 2), dtype=torch.float32, device=x.device)      # pair p < ceil(Cout / 256) written
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(rows * max(K, pk.Cout) * x.element_size())
     if _probe is not None:
         e0, e1 = _probe_pair()
     _lib.call("tlxmi_linear_stats", dt_code(x.dtype), rows, K, pk.Cout, K, pk.Cout, _p(x), _p(pk.buf), _p(bias), _p(res),
@@ -866,7 +957,7 @@ def linear_stats(x, pk, bias=None, res=None, out=None):
     return y, part
 
 
-def linear_ln(x, prep, part, eps, act=ACT_NONE):
+def linear_ln(x, prep, part, eps, act=ACT_NONE, out=None):
     """act(Linear(LayerNorm(x))) on the RAW rows x (..., K): `part` = the (rows, 4, 2) pairs of (sum, sum of squares) the linear_stats
     launch that wrote x left (the first ceil(K / 256) of a row are read); mean / rstd of a row are formed inside the GEMM and applied in its epilogue."""
     need_gpu(x, "input")
@@ -876,7 +967,9 @@ def linear_ln(x, prep, part, eps, act=ACT_NONE):
     rows = x.numel() // shp[-1]
     if tuple(part.shape) != (rows, 4, 2) or part.dtype != torch.float32 or not part.is_contiguous():
         raise RuntimeError(f"linear_ln: statistics of shape {tuple(part.shape)} for {rows} rows (expected {(rows, 4, 2)} fp32)")
-    y = torch.empty((*shp[:-1], prep.Cout), dtype=x.dtype, device=x.device)
+    y = out if out is not None else torch.empty((*shp[:-1], prep.Cout), dtype=x.dtype, device=x.device)
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(rows * max(prep.K, prep.Cout) * x.element_size())
     if _probe is not None:
         e0, e1 = _probe_pair()
     _lib.call("tlxmi_linear_ln", dt_code(x.dtype), rows, prep.K, prep.Cout, prep.K, prep.Cout, _p(x), _p(prep.pk.buf), _p(prep.c1), _p(prep.c2),
