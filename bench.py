@@ -1,35 +1,46 @@
 #!/usr/bin/env python3
 """bench.py — forward images/sec of the BASELINE.json workloads on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet50|vit_b16|swin_b] [--no-also]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet50|vit_b16|swin_b] [--dump-outputs DIR]
+                    [--full [--no-also] [--no-cpu-baseline] [--no-probe]]
 
 Headline (config.workload): BASELINE.json configs[1] — ResNet-50 fp16 forward, batch 256 per GPU, synthetic
 ImageNet-shaped input already resident in HBM, seeded random weights of the real architecture.  A "step" is one forward
 of one batch on every rank followed, for N>1, by the RCCL all-gather of the (256, 1000) logits (the only exchange,
-SURVEY.md §8e); scaling is weak.  Prints ONE JSON line (rank 0).  On the same line:
+SURVEY.md §8e); scaling is weak.  Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and
+prints the line; beside the headline it carries only what the timed region itself gives:
 
-  also          (N=1, default workload) the other half of the metric and the third config, each measured the same way in
-                this same run: ViT-B/16 batch 256 (configs[2]) and Swin-B batch 128 (configs[3]), each with
-                value / ms_per_step / roofline.
   roofline      the WHOLE FORWARD over the TIMED region: SURVEY.md §8d's algorithmic bytes (or FLOPs) per image x the
                 images of a step (+ the weights once per step), divided by the timed ms_per_step — so achieved and
-                value come from the same clock.  `kernel_family` (secondary) is the implicit-GEMM kernel family (every
-                conv / linear launch): Σ algorithmic bytes and FLOPs per launch from the launch descriptors, durations
-                from HIP events on the launch stream in an instrumented per-kernel pass; its share of that pass's
-                wall time is applied to the timed step, so family_ms_per_step <= ms_per_step by construction.
-                `traffic`: HBM bytes per forward from separate rocprofv3 --pmc passes (tools/pmc_traffic.sh), only when
-                the file under profiles/ was measured on exactly these kernel sources (sha of csrc/), else null.
-  cpu_baseline  the CPU oracle (oracle/functional.py, torch fp32 on the host cores) on a bounded sample — the stand-in
-                for "TensorLayerX torch-CPU backend", which cannot be installed.  ResNet-50 at top level, ViT-B/16 inside
-                also[0] (both halves of the headline metric); threads = min(cores the process may use, 16): a GPU box
-                hands one GPU's share of the host, 16 cores, whatever os.cpu_count() says.  `all_affinity_cores` (ResNet-50
-                only): the same protocol on every core of the affinity mask, in a CPU-only child process with a 75 s budget
-                (value null + the reason when the box cannot finish it: see cpu_baseline()).
-  --dump-outputs DIR  after the run, the logits of the LAST timed step of every workload measured (the headline and, if run,
-                also's), as DIR/<workload>_logits.npy in float32: with the same arguments the inputs and weights are the same
-                seeded values in every run, so two builds can be compared output for output.
-Progress lines go to stderr ([bench] ...), the JSON line alone to stdout; the default run takes 2 - 4 minutes.
+                value come from the same clock.  `traffic`: HBM bytes per forward from separate rocprofv3 --pmc passes
+                (tools/pmc_traffic.sh), only when the file under profiles/ was measured on exactly these kernel sources
+                (sha of csrc/), else null.
+
+--full adds everything that needs runs of its own (--no-also, --no-probe and --no-cpu-baseline leave parts out again):
+
+  also          (N=1, default workload; --no-also) the other half of the metric and the third config, each measured the
+                same way in this same run: ViT-B/16 batch 256 (configs[2]) and Swin-B batch 128 (configs[3]), each with
+                value / ms_per_step / roofline.
+  roofline.kernel_family  the implicit-GEMM kernel family (every conv / linear launch): Σ algorithmic bytes
+                and FLOPs per launch from the launch descriptors, durations from HIP events on the launch stream in an
+                instrumented per-kernel pass; its share of that pass's wall time is applied to the timed step, so
+                family_ms_per_step <= ms_per_step by construction.
+  two_in_flight (N=1, graph mode) consecutive steps alternating between two launch streams; secondary figure.
+                --no-probe drops both from the headline (profiling runs).
+  cpu_baseline  (N=1; --no-cpu-baseline) the CPU oracle (oracle/functional.py, torch fp32 on the host cores) on a bounded
+                sample — the stand-in for "TensorLayerX torch-CPU backend", which cannot be installed.  ResNet-50 at top
+                level, ViT-B/16 inside also[0] (both halves of the headline metric); threads = min(cores the process may
+                use, 16): a GPU box hands one GPU's share of the host, 16 cores, whatever os.cpu_count() says.
+                `all_affinity_cores` (ResNet-50 only): the same protocol on every core of the affinity mask, in a CPU-only
+                child process with a 75 s budget (value null + the reason when the box cannot finish it: see cpu_baseline()).
+
+--dump-outputs DIR  after the run, the logits of the LAST timed step of the headline and, for the default workload at N=1
+                unless --no-also, of ViT-B/16 and Swin-B, as DIR/<workload>_logits.npy in float32: with the same arguments
+                the inputs and weights are the same seeded values in every run, so two builds can be compared output for
+                output.  A plain run writes the same files as --full: it runs the other two workloads' warm-up and steps
+                for their logits alone and reports no figure of theirs.
+Progress lines go to stderr ([bench] ...), the JSON line alone to stdout; a plain run spends about 3 s beyond its steps
+(6 s with --dump-outputs), --full about 2 minutes, most of it in cpu_baseline.
 """
 import argparse
 import hashlib
@@ -351,13 +362,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default 256; 128 for swin_b)")
     ap.add_argument("--workload", default="resnet50", choices=list(WORK))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="headline workload only (skip the ViT-B/16 and Swin-B lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: also[ViT-B/16, Swin-B], kernel_family, two_in_flight, cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-also", action="store_true", help="headline workload only (skip the ViT-B/16 and Swin-B lines and logits)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=0|1", help="engine.set_option(NAME, value) before building")
-    ap.add_argument("--no-probe", action="store_true", help="timed region only: no instrumented per-kernel pass, no two_in_flight run (profiling runs)")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: no instrumented per-kernel pass, no two_in_flight run for the headline")
     ap.add_argument("--no-graph", action="store_true", help="launch kernel by kernel instead of replaying a hipGraph")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="write the logits of the last timed step of every measured workload as DIR/<workload>_logits.npy (float32)")
+                    help="write the logits of the last timed step of the headline and (unless --no-also) of ViT-B/16 and Swin-B as "
+                         "DIR/<workload>_logits.npy (float32); the same files with or without --full")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
@@ -382,7 +396,7 @@ def main():
 
     if rank == 0:
         print(f"[bench] {a.workload} batch {a.batch} x {world} GPU(s), {a.steps} steps ...", file=sys.stderr, flush=True)
-    res, params, model = measure(a.workload, a.batch, a.steps, a.warmup, dev, rank, world, graph=not a.no_graph, probe_family=not a.no_probe)
+    res, params, model = measure(a.workload, a.batch, a.steps, a.warmup, dev, rank, world, graph=not a.no_graph, probe_family=a.full and not a.no_probe)
     line = {
         "metric": "images/sec fwd", "value": res["value"], "unit": "images/sec", "n_gpus": world,
         "steps": a.steps, "warmup": a.warmup, "ms_per_step": res["ms_per_step"],
@@ -399,27 +413,31 @@ def main():
     if rank == 0:
         line["roofline"] = res["roofline"]
         dumps = {f"{a.workload}_logits": res["logits"]}
-        if world == 1 and a.workload == "resnet50" and not a.no_also:
+        # a plain run with --dump-outputs still runs the other two workloads, for their logits alone: the dumped files do not
+        # depend on --full, so two builds compare the same outputs however each was run
+        if world == 1 and a.workload == "resnet50" and not a.no_also and (a.full or a.dump_outputs):
             del model
             torch.cuda.empty_cache()
             also = []
             for wl in ("vit_b16", "swin_b"):
                 b = WORK[wl][1]
-                print(f"[bench] also: {wl} batch {b} ...", file=sys.stderr, flush=True)
-                r, p2, m2 = measure(wl, b, min(a.steps, 30), min(a.warmup, 5), dev, 0, 1, graph=not a.no_graph)
+                print(f"[bench] {'also' if a.full else 'logits only'}: {wl} batch {b} ...", file=sys.stderr, flush=True)
+                r, p2, m2 = measure(wl, b, min(a.steps, 30), min(a.warmup, 5), dev, 0, 1, graph=not a.no_graph, probe_family=a.full)
                 del m2
                 torch.cuda.empty_cache()
                 dumps[f"{wl}_logits"] = r["logits"]
-                also.append({"workload": LABEL[wl].format(b=b), "value": r["value"], "unit": "images/sec",
-                             "ms_per_step": r["ms_per_step"], "ms_per_step_median": r["ms_per_step_median"],
-                             "steps": min(a.steps, 30), "warmup": min(a.warmup, 5), "roofline": r["roofline"],
-                             **({"two_in_flight": r["two_in_flight"]} if "two_in_flight" in r else {})})
-                if wl == "vit_b16" and not a.no_cpu_baseline:
-                    # the other half of the headline metric gets its CPU number in the same run
-                    also[-1]["cpu_baseline"] = cpu_baseline(wl, p2, min_iters=3, min_seconds=8.0, all_cores=False)
+                if a.full:
+                    also.append({"workload": LABEL[wl].format(b=b), "value": r["value"], "unit": "images/sec",
+                                 "ms_per_step": r["ms_per_step"], "ms_per_step_median": r["ms_per_step_median"],
+                                 "steps": min(a.steps, 30), "warmup": min(a.warmup, 5), "roofline": r["roofline"],
+                                 **({"two_in_flight": r["two_in_flight"]} if "two_in_flight" in r else {})})
+                    if wl == "vit_b16" and not a.no_cpu_baseline:
+                        # the other half of the headline metric gets its CPU number in the same run
+                        also[-1]["cpu_baseline"] = cpu_baseline(wl, p2, min_iters=3, min_seconds=8.0, all_cores=False)
                 del p2
-            line["also"] = also
-        if world == 1 and not a.no_cpu_baseline:
+            if a.full:
+                line["also"] = also
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.workload, params)
         if a.dump_outputs:
             dump_outputs(a.dump_outputs, dumps)
