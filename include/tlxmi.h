@@ -516,6 +516,18 @@ int tlxmi_upsample2x_nearest(const void* x, void* y, int dtype, int N, int H, in
 int tlxmi_copy_channels(const void* x, void* y, int dtype, int64_t rows, int C, int x_ld, int y_ld,
                         void* stream);
 
+/* bilinear resize of an NHWC map (tlx.Resize(method="bilinear"); deeplab.py:177-182, pyramid_pool.py:94-99): x[N][H][W][x_ld],
+ * C channels used, fp16 or fp32 -> y fp16 or fp32, fp32 arithmetic.  Ho / Wo are the caller's (floor(in * scale) for a
+ * scale factor); scale_h / scale_w > 0: the source coordinate uses 1 / scale as torch's interpolate(scale_factor=) does,
+ * <= 0: in / out.  align_corners 0 / 1.  y_layout TLXMI_LAYOUT_NHWC: y + n * y_nstride + (ho * Wo + wo) * y_ld + c
+ * (a column slice of a wider buffer; y_nstride 0 = Ho * Wo * y_ld); TLXMI_LAYOUT_NCHW: dense y[N][C][Ho][Wo] (y_ld 0 or C,
+ * y_nstride 0).  Offsets are 64-bit: outputs past 2 GiB are fine. */
+#define TLXMI_LAYOUT_NHWC 0
+#define TLXMI_LAYOUT_NCHW 1
+int tlxmi_resize_bilinear(const void* x, int x_dtype, int N, int H, int W, int C, int x_ld, void* y, int y_dtype,
+                          int Ho, int Wo, int y_layout, int y_ld, int64_t y_nstride, int align_corners, double scale_h,
+                          double scale_w, void* stream);
+
 /* argmax over the last dimension -> int64 (tasks/image_classification.py:23) */
 int tlxmi_argmax_lastdim(const void* x, int dtype, int64_t rows, int C, int x_ld, int64_t* out,
                          void* stream);

@@ -17,6 +17,7 @@ EPI_RES_AFTER_ACT = 1
 EPI_MAXPOOL_3S2P1 = 4
 PLAN_SHARED_HALF = 0x100      # planning hints in the same flags word (include/tlxmi.h)
 PLAN_SHARED_FULL = 0x200
+LAYOUT_NHWC, LAYOUT_NCHW = 0, 1    # tlxmi_resize_bilinear's y_layout
 
 
 class ConvDesc(C.Structure):
@@ -106,6 +107,7 @@ PROTOTYPES = {
     "tlxmi_upsample2x_nearest": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_copy_channels": [_vp, _vp, _i, _l, _i, _i, _i, _vp],
     "tlxmi_argmax_lastdim": [_vp, _i, _l, _i, _i, _vp, _vp],
+    "tlxmi_resize_bilinear": [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _l, _i, C.c_double, C.c_double, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),

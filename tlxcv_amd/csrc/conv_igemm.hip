@@ -566,6 +566,17 @@ template <typename T, int BM, int BN, int WGM, int STAGES> static int launch(con
     return TLXMI_OK;
 }
 
+// gemm_pp.hip's CONV mode addresses the input through 32-bit byte offsets: a row's tap (0,0) lies up to (pad_h * W + pad_w) pixels
+// before the image, and its farthest tap ((R-1) * dil_h * W + (S-1) * dil_w) pixels after that (plus one pixel of channel chunks).
+// For DILATED convs (pad = dilation up to 18) both are kept under 2^30 bytes — half the int32 range — so that no intermediate of the
+// tap arithmetic wraps (pad = dilation = 18 on a 2048-channel fp16 map: W < 3640).  Dilation-1 convs keep the dispatch they had.
+static bool pp_conv_offsets_ok(int W, int R, int S, int ph, int pw, int dh, int dw, int x_ld, int es) {
+    const long long px = (long long)x_ld * es;
+    const long long lead = ((long long)ph * W + pw) * px;
+    const long long reach = ((long long)(R - 1) * dh * W + (long long)(S - 1) * dw + 1) * px;
+    return lead < (1ll << 30) && reach < (1ll << 30);
+}
+
 template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, bool allow_stream = true, bool allow_split = true) {
     // Tile choice = max over the four shapes of (grid quantisation efficiency) x (shape efficiency):
     // a launch of B blocks on S = CUs x resident-blocks-per-CU slots runs ceil(B/S) rounds, so B/(rounds*S)
@@ -653,7 +664,10 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
     // (also the strided 1x1 projection shortcuts, resnet.py:246-261: one "tap", rows gathered at stride 2)
     const bool strided1x1 = a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && (a.sh > 1 || a.sw > 1);
     const bool as_conv = !(a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && a.sh == 1 && a.sw == 1);   // needs the gather of CONV mode
-    const bool pp_conv128_ok = a.nchunk == 1 && !a.overhang && ((a.S == 3 && a.R <= 3) || strided1x1) && a.dh == 1 && a.dw == 1 && !a.strided_n &&
+    // dilated 3x3 convs (DeepLabV3) take the same path; TLXMI_PP_DIL=0 (tuning flavour, A/B) keeps them on the tiles above
+    const bool dilated = a.dh != 1 || a.dw != 1;
+    const bool pp_dil_ok = !dilated || (tune_int("TLXMI_PP_DIL", 1) != 0 && pp_conv_offsets_ok(a.W, a.R, a.S, a.ph, a.pw, a.dh, a.dw, a.x_ld, (int)sizeof(T)));
+    const bool pp_conv128_ok = a.nchunk == 1 && !a.overhang && ((a.S == 3 && a.R <= 3) || strided1x1) && pp_dil_ok && !a.strided_n &&
                                a.vec_io && a.Cout % 8 == 0 && a.Cout >= 128 && a.y_bytes != 0 && a.cpt % 8 == 0 && (tpk & (tpk - 1)) == 0 &&
                                (!a.res || (long long)a.M * a.res_ld * (long long)sizeof(T) < (1ll << 31));
     const bool pp_conv_ok = pp_conv128_ok && a.Cout >= 256;
@@ -853,6 +867,7 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
         if (as_conv) {      // candidates 7 / 9 / 10 as a convolution
             g.conv = 1;
             g.cH = a.H; g.cW = a.W; g.cWo = a.Wo; g.cHoWo = a.HoWo; g.csh = a.sh; g.csw = a.sw; g.cph = a.ph; g.cpw = a.pw;
+            g.cdh = a.dh; g.cdw = a.dw;
             g.ctaps = a.R * a.S;
             g.ctshift = 0;
             while ((1 << g.ctshift) < tpk) ++g.ctshift;
@@ -1017,7 +1032,10 @@ static bool conv_splitk_shape_ok(const tlxmi_conv2d_desc* d, int splits) {
     if (!d || (d->dtype != TLXMI_F16 && d->dtype != TLXMI_F32) || splits < 2 || splits > 16) return false;
     const int es = (int)elt_size(d->dtype);
     const bool strided1x1 = d->R == 1 && d->S == 1 && d->pad_h == 0 && d->pad_w == 0 && (d->stride_h > 1 || d->stride_w > 1);
-    if (!((d->S == 3 && d->R >= 1 && d->R <= 3) || strided1x1) || d->dil_h != 1 || d->dil_w != 1) return false;
+    if (!((d->S == 3 && d->R >= 1 && d->R <= 3) || strided1x1)) return false;
+    if ((d->dil_h != 1 || d->dil_w != 1) &&
+        (!tune_int("TLXMI_PP_DIL", 1) || !pp_conv_offsets_ok(d->W, d->R, d->S, d->pad_h, d->pad_w, d->dil_h, d->dil_w, d->x_ld, es)))
+        return false;
     if (d->Cout % 8 || d->Cout < 128 || d->y_nstride || d->res_nstride || (d->flags & (TLXMI_EPI_RES_BCAST_N | TLXMI_EPI_MAXPOOL_3S2P1))) return false;
     if ((d->C * es) % 128) return false;
     const int tpk = d->C * es / 128;                       // K tiles per tap: a power of two
@@ -1026,7 +1044,8 @@ static bool conv_splitk_shape_ok(const tlxmi_conv2d_desc* d, int splits) {
     if (ktiles / splits < 4) return false;                 // at least 4 K tiles per slice
     // what the dispatcher's gemm_pp convolution path (pp_conv128_ok) asks on top: no window past the bottom / right edge
     // (one-sided 'SAME' padding), whole 16-byte chunks on the output and residual rows
-    const int Ho = (d->H + 2 * d->pad_h - (d->R - 1) - 1) / d->stride_h + 1, Wo = (d->W + 2 * d->pad_w - (d->S - 1) - 1) / d->stride_w + 1;
+    const int Ho = (d->H + 2 * d->pad_h - d->dil_h * (d->R - 1) - 1) / d->stride_h + 1;
+    const int Wo = (d->W + 2 * d->pad_w - d->dil_w * (d->S - 1) - 1) / d->stride_w + 1;
     if (d->Ho > Ho || d->Wo > Wo) return false;
     const int vecn = 16 / es;
     if (d->y_ld % vecn || (d->res_ld > 0 && d->res_ld % vecn)) return false;

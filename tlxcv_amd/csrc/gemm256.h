@@ -38,12 +38,15 @@ struct Gemm256Args {
     // gemm_pp.hip only — 3-wide-filter convolution as implicit GEMM (conv != 0): X rows are gathered per filter tap.
     // One K tile (128 bytes) never straddles taps: C * sizeof(T) is 128 << ctshift bytes.
     int conv;
-    int cH, cW, cWo, cHoWo, csh, csw, cph, cpw;   // input extent, output extent, stride, padding (dilation 1)
+    int cH, cW, cWo, cHoWo, csh, csw, cph, cpw;   // input extent, output extent, stride, padding (dilation: cdh / cdw below)
     int ctshift, ctaps;                           // log2(K tiles per tap), R * 3 taps
     // gemm_pp.hip only — split K (tlxmi_conv2d_splitk): the grid holds kslices copies of the tile grid, copy s multiplies K tiles
     // [s * kt_slice, (s + 1) * kt_slice) and stores its fp32 accumulators, unscaled, at y + s * slice_bytes ([M][y_ld] floats)
     int kslices = 1, kt_slice = 0;
     long long slice_bytes = 0;
+    // gemm_pp.hip CONV mode — dilation: tap (r, s) reads input pixel (hi0 + r * cdh, wi0 + s * cdw).  Read only by the dilated
+    // instances (launch_gemm_pp* pick them when cdh | cdw != 1); kept last so the other fields keep their kernel-argument offsets.
+    int cdh = 1, cdw = 1;
 };
 
 int launch_gemm256(int dtype, int variant, const Gemm256Args& a, hipStream_t st);

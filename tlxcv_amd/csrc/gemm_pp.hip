@@ -64,9 +64,9 @@ template <> struct MmaPP<float> {
 // With one X half a K tile is two phases ((0,0) and (0,1)) and 48 KiB, so THREE K tiles are resident and the
 // DMA runs two K tiles ahead:  p0(k): X0, W0 of k+2 (vmcnt(10) retires W1(k));  p1(k): W1 of k+2 (vmcnt(8)
 // retires X0, W0 of k+1) — again every half tile is refilled two phases after its last read.
-// CONV: the X operand is the im2col view of an NHWC map under an R x 3 filter, stride / zero padding as given
+// CONV: the X operand is the im2col view of an NHWC map under an R x 3 filter, stride / zero padding / dilation as given
 // (3x3 convs with >= 256 output channels: resnet.py:111-121 conv2 of the 14x14 / 7x7 stages, vgg.py:74-80,
-// darknet.py:54-58).  A K tile of 128 bytes lies inside one filter tap (C * sizeof(T) = 128 << ctshift), so the tap
+// darknet.py:54-58; the dilated 3x3 convs of DeepLabV3's backbone and ASPP head).  A K tile of 128 bytes lies inside one filter tap (C * sizeof(T) = 128 << ctshift), so the tap
 // of a K tile is wave-uniform: its byte offset is scalar arithmetic, and each of a lane's four rows carries a bit
 // mask of the taps that fall inside the image (bit clear -> out-of-range descriptor offset -> zero fill).
 // HN = W half tiles per K tile: (HM, HN) = (2, 1) is the mirror image of (1, 2) — a 256 x 128 tile for layers with 128
@@ -76,7 +76,8 @@ template <> struct MmaPP<float> {
 // folded LayerNorm); a.stats_out: per-row (sum, sum^2) of this tile's 256 output channels as plane bn0 / 256 (the producer; the four
 // wc waves of a row are added through LDS).  Used where the persistent kernel does not apply: a residual with fewer than 11 K tiles
 // (Swin-B stage 3 proj: K = 512), fewer tiles than half the CUs.
-template <typename T, int HM, int HN, bool CONV, bool LNF = false>
+// DIL (CONV only): the dilated instances read a.cdh / a.cdw; the undilated ones keep the dilation-1 arithmetic (and ISA).
+template <typename T, int HM, int HN, bool CONV, bool LNF = false, bool DIL = false>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
     static_assert(HM + HN >= 3 && HM <= 2 && HN <= 2, "tile is 256x256, 128x256 or 256x128");
     constexpr int ES = (int)sizeof(T);
@@ -128,12 +129,15 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
                 const int n = mm / a.cHoWo, rem = mm - n * a.cHoWo;
                 const int ho = rem / a.cWo, wo_ = rem - ho * a.cWo;
                 const int hi0 = ho * a.csh - a.cph, wi0 = wo_ * a.csw - a.cpw;
-                xo[h][j] = ((n * a.cH + hi0) * a.cW + wi0) * a.x_ld * ES;     // tap (0,0); may wrap below zero under padding
+                // tap (0,0); may wrap below zero under padding (dilated convs: the dispatcher keeps (pad_h * W + pad_w) * x_ld * ES and
+                // the farthest tap offset under 2^30, pp_conv_offsets_ok)
+                xo[h][j] = ((n * a.cH + hi0) * a.cW + wi0) * a.x_ld * ES;
+                const int dh = DIL ? a.cdh : 1, dw = DIL ? a.cdw : 1;
                 unsigned mk = 0;
 #pragma unroll
                 for (int tp = 0; tp < 9; ++tp) {
                     const int r = tp / 3, s_ = tp - 3 * r;
-                    if (live && tp < a.ctaps && (unsigned)(hi0 + r) < (unsigned)a.cH && (unsigned)(wi0 + s_) < (unsigned)a.cW) mk |= 1u << tp;
+                    if (live && tp < a.ctaps && (unsigned)(hi0 + r * dh) < (unsigned)a.cH && (unsigned)(wi0 + s_ * dw) < (unsigned)a.cW) mk |= 1u << tp;
                 }
                 tapmask[h][j] = mk;
             } else {
@@ -153,7 +157,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
         if constexpr (CONV) {
             const int tap = kt >> a.ctshift;                       // wave-uniform; >= ctaps past the end (mask bit clear)
             const int r = (tap * 11) >> 5, s_ = tap - 3 * r;       // tap / 3 for tap <= 8
-            const int d = (r * a.cW + s_) * a.x_ld * ES + (((kt - (tap << a.ctshift)) * 8 + lc) << 4);
+            const int d = (DIL ? r * a.cdh * a.cW + s_ * a.cdw : r * a.cW + s_) * a.x_ld * ES + (((kt - (tap << a.ctshift)) * 8 + lc) << 4);
 #pragma unroll
             for (int j = 0; j < 2; ++j) pp_dma16(xsrd, b + j * 8192, (mine && ((tapmask[h][j] >> tap) & 1u)) ? xo[h][j] + d : OOB);
         } else {
@@ -525,7 +529,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
 }
 
 // Preconditions as launch_gemm256 (checked by conv_igemm.hip's dispatcher); a.ksteps = packed pitch / 128.
-template <typename T, int HM, int HN, bool CONV, bool LNF = false> static int launch_pp_t(const Gemm256Args& a0, hipStream_t st) {
+template <typename T, int HM, int HN, bool CONV, bool LNF = false, bool DIL = false> static int launch_pp_t(const Gemm256Args& a0, hipStream_t st) {
     Gemm256Args a = a0;
     a.debug = (int)tune_int("TLXMI_DEBUG", 0);     // ablation bits: tuning flavour only (TLXMI_DBG is `false` in the product)
     a.mtiles = (a.M + 128 * HM - 1) / (128 * HM);
@@ -533,7 +537,7 @@ template <typename T, int HM, int HN, bool CONV, bool LNF = false> static int la
     a.gn = a.ntiles;
     if (const long g = tune_int("TLXMI_GS_PANEL", 3); !CONV && g > 0 && g < a.ntiles) a.gn = (int)g;
     const size_t lds = (size_t)(HM + HN == 4 ? 8 : 9) * 128 * 128 + 2 * 256 * sizeof(float);
-    const void* fn = reinterpret_cast<const void*>(&gemm_pp_kernel<T, HM, HN, CONV, LNF>);
+    const void* fn = reinterpret_cast<const void*>(&gemm_pp_kernel<T, HM, HN, CONV, LNF, DIL>);
     if (int rc = raise_lds_limit(fn, (int)lds, "gemm_pp")) return rc;
     void* args[] = {&a};
     hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(a.mtiles * a.ntiles * (a.kslices > 1 ? a.kslices : 1))), dim3(512), args, lds, st);
@@ -541,11 +545,17 @@ template <typename T, int HM, int HN, bool CONV, bool LNF = false> static int la
     return TLXMI_OK;
 }
 
-int launch_gemm_pp(int dtype, const Gemm256Args& a, hipStream_t st) {
-    if (a.conv) {
-        if (dtype == TLXMI_F16) return launch_pp_t<half_t, 2, 2, true>(a, st);
-        return launch_pp_t<float, 2, 2, true>(a, st);
+template <int HM, int HN> static int launch_pp_conv(int dtype, const Gemm256Args& a, hipStream_t st) {
+    if (a.cdh != 1 || a.cdw != 1) {
+        if (dtype == TLXMI_F16) return launch_pp_t<half_t, HM, HN, true, false, true>(a, st);
+        return launch_pp_t<float, HM, HN, true, false, true>(a, st);
     }
+    if (dtype == TLXMI_F16) return launch_pp_t<half_t, HM, HN, true>(a, st);
+    return launch_pp_t<float, HM, HN, true>(a, st);
+}
+
+int launch_gemm_pp(int dtype, const Gemm256Args& a, hipStream_t st) {
+    if (a.conv) return launch_pp_conv<2, 2>(dtype, a, st);
     if (a.rowstats || a.stats_out) {      // LayerNorm fold (fp16, Cout % 32 == 0: checked by the entry points in conv_igemm.hip)
         if (dtype != TLXMI_F16 || (a.Cout & 31) || a.kslices > 1) return fail(TLXMI_ERR_UNSUPPORTED, "gemm_pp: the LayerNorm fold is fp16, Cout %% 32 == 0");
         return launch_pp_t<half_t, 2, 2, false, true>(a, st);
@@ -556,10 +566,7 @@ int launch_gemm_pp(int dtype, const Gemm256Args& a, hipStream_t st) {
 
 // 128 x 256 tiles (same preconditions)
 int launch_gemm_pp128(int dtype, const Gemm256Args& a, hipStream_t st) {
-    if (a.conv) {
-        if (dtype == TLXMI_F16) return launch_pp_t<half_t, 1, 2, true>(a, st);
-        return launch_pp_t<float, 1, 2, true>(a, st);
-    }
+    if (a.conv) return launch_pp_conv<1, 2>(dtype, a, st);
     if (a.rowstats || a.stats_out) {      // LayerNorm fold on half-height tiles (few row tiles: Swin-B stage 3 proj, 49 x 2 tiles of 256 x 256)
         if (dtype != TLXMI_F16 || (a.Cout & 31) || a.kslices > 1) return fail(TLXMI_ERR_UNSUPPORTED, "gemm_pp: the LayerNorm fold is fp16, Cout %% 32 == 0");
         return launch_pp_t<half_t, 1, 2, false, true>(a, st);
@@ -570,10 +577,7 @@ int launch_gemm_pp128(int dtype, const Gemm256Args& a, hipStream_t st) {
 
 // 256 x 128 tiles (layers with 128 output channels)
 int launch_gemm_pp_n128(int dtype, const Gemm256Args& a, hipStream_t st) {
-    if (a.conv) {
-        if (dtype == TLXMI_F16) return launch_pp_t<half_t, 2, 1, true>(a, st);
-        return launch_pp_t<float, 2, 1, true>(a, st);
-    }
+    if (a.conv) return launch_pp_conv<2, 1>(dtype, a, st);
     if (dtype == TLXMI_F16) return launch_pp_t<half_t, 2, 1, false>(a, st);
     return launch_pp_t<float, 2, 1, false>(a, st);
 }

@@ -1439,3 +1439,48 @@ def argmax_lastdim(x):
     out = torch.empty(x.shape[:-1], dtype=torch.int64, device=x.device)
     _lib.call("tlxmi_argmax_lastdim", _p(x), dt_code(x.dtype), rows, Cc, Cc, _p(out), _stream())
     return out
+
+
+def resize_out_size(n_in, scale):
+    """Output extent of torch.nn.functional.interpolate(scale_factor=scale) along one axis: floor(n_in * scale) in double."""
+    import math
+    return int(math.floor(float(n_in) * float(scale)))
+
+
+def resize_bilinear(x, scale, align_corners=False, channels=None, out=None, layout="nhwc", out_dtype=None):
+    """Bilinear resize (tlx.Resize(method="bilinear"), deeplab.py:177-182) of an NHWC map x (N, H, W, x_ld), `channels` of its
+    x_ld used (default all).  scale: s or (sh, sw) as interpolate(scale_factor=) takes it -> (floor(H * sh), floor(W * sw)).
+    layout "nhwc": y (N, Ho, Wo, C), or written into `out` — an (N, Ho, Wo, C) view with unit channel stride, e.g. a column
+    slice of a wider buffer (the ASPP concat); "nchw": a dense (N, C, Ho, Wo) tensor.  fp32 interpolation; out_dtype fp16 / fp32
+    (default x's)."""
+    need_gpu(x, "input")
+    N, H, W, ld = x.shape
+    if not x.is_contiguous():
+        raise RuntimeError("resize_bilinear: x must be a dense NHWC map (N, H, W, x_ld)")
+    Cc = ld if channels is None else int(channels)
+    sh, sw = (scale, scale) if isinstance(scale, (int, float)) else (scale[0], scale[1])
+    Ho, Wo = resize_out_size(H, sh), resize_out_size(W, sw)
+    if Ho <= 0 or Wo <= 0:
+        raise RuntimeError(f"resize_bilinear: empty output {Ho}x{Wo} for input {H}x{W} at scale {scale}")
+    dt = out_dtype or (out.dtype if out is not None else x.dtype)
+    nstride = 0
+    if layout == "nchw":
+        if out is not None:
+            raise RuntimeError("resize_bilinear: the NCHW form allocates its output")
+        out = torch.empty((N, Cc, Ho, Wo), dtype=dt, device=x.device)
+        y_ld, lay = 0, _lib.LAYOUT_NCHW
+    elif layout == "nhwc":
+        if out is None:
+            out = torch.empty((N, Ho, Wo, Cc), dtype=dt, device=x.device)
+        # pixel pitch / image stride of the view (strides of size-1 axes carry no meaning)
+        y_ld = out.stride(2) if Wo > 1 else out.stride(1) if Ho > 1 else Cc
+        nstride = out.stride(0) if N > 1 else Ho * Wo * y_ld
+        if (tuple(out.shape) != (N, Ho, Wo, Cc) or out.dtype != dt or (Cc > 1 and out.stride(3) != 1) or y_ld < Cc
+                or (Ho > 1 and Wo > 1 and out.stride(1) != Wo * y_ld)):
+            raise RuntimeError(f"resize_bilinear: out must be an ({N}, {Ho}, {Wo}, {Cc}) {dt} view with rows of one pitch")
+        lay = _lib.LAYOUT_NHWC
+    else:
+        raise ValueError(f"resize_bilinear: layout {layout!r}")
+    _lib.call("tlxmi_resize_bilinear", _p(x), dt_code(x.dtype), N, H, W, Cc, ld, _p(out), dt_code(dt), Ho, Wo, lay, y_ld, nstride,
+              1 if align_corners else 0, float(sh), float(sw), _stream())
+    return out

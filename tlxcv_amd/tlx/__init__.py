@@ -10,7 +10,7 @@ import torch
 from .. import engine as _E
 from . import nn, ops, vision  # noqa: F401
 from .nn import initializers  # noqa: F401
-from .ops import (GeLU, softmax, sigmoid, relu, arange, stack)  # noqa: F401
+from .ops import (GeLU, Resize, softmax, sigmoid, relu, arange, stack)  # noqa: F401
 
 BACKEND = "torch"
 float32 = torch.float32
