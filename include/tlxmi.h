@@ -332,6 +332,31 @@ int tlxmi_dwconv2d(const tlxmi_dwconv2d_desc* d, const void* x, const void* w_rs
                    const float* shift, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Separable conv: depthwise 3x3 (+ BN) -> fp16 -> pointwise 1x1 (+ BN + ReLU) in one launch, the depthwise map kept on chip.
+ * Replaces SeparableConvBNReLU (segmentation/layers/layer_libs.py:98-133): DeepLabV3+'s ASPP branches (deeplab.py:252-262,
+ * pyramid_pool.py:35-38) and decoder convs (deeplab.py:268-281).
+ *     y[m][n] = act( sum_c fp16( dw(x)[m][c] * dw_scale[c] + dw_shift[c] ) * Wp[n][c] * pw_scale[n] + pw_shift[n] )
+ * dw: 3x3 depthwise correlation, stride 1, padding = dilation (output extent = input extent), fp32 accumulation in
+ * tlxmi_dwconv2d's tap order.  w_dw: [3][3][C] fp16 (as tlxmi_dwconv2d); w_packed: tlxmi_pack_filter of the [Cout][C][1][1]
+ * pointwise filter; scales / shifts fp32 (null: 1 / 0), the BN folded with the conv bias.  x: N*H*W pixels of pitch x_ld;
+ * y: pixels of pitch y_ld, Cout columns each (a column slice of a wider buffer).  act: TLXMI_ACT_NONE / TLXMI_ACT_RELU.
+ * Supported (tlxmi_sepconv2d_supported() == 1): fp16, R = S = 3, stride 1, pad_h = pad_w = dil_h = dil_w >= 1, Cout == 256,
+ * C % 8 == 0, x_ld >= C and y_ld >= 256 multiples of 8, input bytes + (dil * W + dil) * x_ld * 2 < 2^31, y extent < 2^31
+ * bytes; buffers 16-byte aligned.  Anything else returns TLXMI_ERR_UNSUPPORTED (run tlxmi_dwconv2d + tlxmi_conv2d instead).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_sepconv2d_desc {
+    int32_t dtype;
+    int32_t N, H, W, C, Cout;
+    int32_t R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+    int32_t x_ld, y_ld;
+    int32_t act;
+    float act_param;
+} tlxmi_sepconv2d_desc;
+int tlxmi_sepconv2d_supported(const tlxmi_sepconv2d_desc* d);
+int tlxmi_sepconv2d(const tlxmi_sepconv2d_desc* d, const void* x, const void* w_dw, const float* dw_scale, const float* dw_shift,
+                    const void* w_packed, const float* pw_scale, const float* pw_shift, void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

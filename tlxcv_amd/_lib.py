@@ -33,6 +33,12 @@ class DwConvDesc(C.Structure):
         "dil_w", "Ho", "Wo", "x_ld", "y_ld", "act")] + [("act_param", C.c_float)]
 
 
+class SepConvDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "dtype", "N", "H", "W", "C", "Cout", "R", "S", "stride_h", "stride_w", "pad_h", "pad_w", "dil_h", "dil_w",
+        "x_ld", "y_ld", "act")] + [("act_param", C.c_float)]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "B", "Ntok", "heads", "hd")] + [
         ("scale", C.c_float), ("nW", C.c_int32)]
@@ -108,6 +114,7 @@ PROTOTYPES = {
     "tlxmi_copy_channels": [_vp, _vp, _i, _l, _i, _i, _i, _vp],
     "tlxmi_argmax_lastdim": [_vp, _i, _l, _i, _i, _vp, _vp],
     "tlxmi_resize_bilinear": [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _l, _i, C.c_double, C.c_double, _vp],
+    "tlxmi_sepconv2d": [C.POINTER(SepConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -124,6 +131,7 @@ _SPECIAL = {
     "tlxmi_bottleneck_seam_supported": ([_i, _i, _i, _i], C.c_int),
     "tlxmi_linear_ln_supported": ([_i, _l, _i, _i, _i, _i], C.c_int),
     "tlxmi_mlp_seam_supported": ([_i, _i, _i, _i], C.c_int),
+    "tlxmi_sepconv2d_supported": ([C.POINTER(SepConvDesc)], C.c_int),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

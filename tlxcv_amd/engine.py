@@ -37,6 +37,9 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
             "lnfold_min_rows": 2048,  # (a number) folded Linear layers need at least this many rows (below, the tiled kernels of the dispatcher win)
             "lnfold_min_rows_one_stream": 12000,  # (a number) ... and this many outside a two-stream forward
             "lnfold_min_c": 256,  # (a number) Swin: fold the LayerNorms of the stages with at least this many channels (tools/ A/B per stage)
+            "sepconv": True,      # DeepLabV3+'s separable convs (fp16): depthwise 3x3 + BN -> pointwise 1x1 + BN + ReLU as one launch
+                                  # (tlxmi_sepconv2d), the depthwise map kept on chip; off = tlxmi_dwconv2d then tlxmi_conv2d (the A/B and
+                                  # the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -999,6 +1002,65 @@ def dwconv2d(x, w_rsc, stride=1, padding=0, dilation=1, scale=None, shift=None, 
                         act_param=float(act_param))
     _lib.call("tlxmi_dwconv2d", C.byref(d), _p(x), _p(w_rsc), _p(scale), _p(shift), _p(y), _stream())
     return y
+
+
+_conv2d = conv2d        # the unfused arm of sepconv2d (a tool that wraps E.conv2d sees the pair as one separable conv)
+
+
+def sepconv2d(x, w_dw, dw_scale, dw_shift, pk, pw_scale, pw_shift, dilation, act=ACT_RELU, act_param=0.0, out=None, out_ld=None,
+              fused=None):
+    """SeparableConvBNReLU (layer_libs.py:98-133): depthwise 3x3 (stride 1, padding = dilation) + folded BN, rounded to the
+    activation dtype, then pointwise 1x1 + folded BN + act.  x (N, H, W, ld) NHWC with C = w_dw.shape[2] channels used;
+    w_dw [3][3][C]; pk: PackedFilter of the [Cout][C] pointwise filter -> y (N, H, W, Cout), or written into `out` (a column slice
+    of a wider buffer, pixel pitch out_ld).  One launch (tlxmi_sepconv2d) when the "sepconv" option is on, the precision is
+    fp16, the conv is dilated and the library takes the shape; otherwise tlxmi_dwconv2d then tlxmi_conv2d (fp32 always: the
+    parity reference).  Dilation 1 keeps the pair: there the depthwise runs on dwconv_strip_kernel, and the pair measured faster
+    than the fused kernel at DeepLabV3+'s decoder shapes.  fused=True / False forces one form (tests, tools/)."""
+    global _probe
+    need_gpu(x, "input")
+    N, H, W, ld = x.shape
+    R, S, Cc = w_dw.shape
+    d = int(dilation)
+    if (R, S) != (3, 3) or pk.R != 1 or pk.S != 1 or pk.Cin != Cc:
+        raise RuntimeError(f"sepconv2d: depthwise {R}x{S}x{Cc} -> pointwise {pk.Cout}x{pk.Cin}x{pk.R}x{pk.S} is not a separable 3x3 conv")
+    if x.dtype != pk.dtype or w_dw.dtype != x.dtype or ld < Cc or not x.is_contiguous():
+        raise RuntimeError("sepconv2d: x must be a dense NHWC map of the filters' dtype with at least C channels")
+    if out is None:
+        out = torch.empty((N, H, W, pk.Cout), dtype=x.dtype, device=x.device)
+        out_ld = pk.Cout
+    elif out_ld is None:
+        out_ld = out.shape[-1]
+    es = x.element_size()
+    M = N * H * W
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * es, M * Cc * es, M * out_ld * es)
+    desc = _lib.SepConvDesc(dtype=dt_code(x.dtype), N=N, H=H, W=W, C=Cc, Cout=pk.Cout, R=3, S=3, stride_h=1, stride_w=1, pad_h=d,
+                            pad_w=d, dil_h=d, dil_w=d, x_ld=ld, y_ld=out_ld, act=act, act_param=float(act_param))
+    if fused is None:
+        fused = bool(_options["sepconv"] and x.dtype == torch.float16 and d > 1 and _lib.load().tlxmi_sepconv2d_supported(C.byref(desc)))
+
+    def launch():
+        if fused:
+            _lib.call("tlxmi_sepconv2d", C.byref(desc), _p(x), _p(w_dw), _p(dw_scale), _p(dw_shift), _p(pk.buf), _p(pw_scale),
+                      _p(pw_shift), _p(out), _stream())
+        else:
+            t = dwconv2d(x, w_dw, 1, d, d, dw_scale, dw_shift)
+            _conv2d(t, pk, 1, 0, 1, pw_scale, pw_shift, act=act, act_param=act_param, out=out, out_ld=out_ld)
+    if _probe is None:
+        launch()
+        return out
+    probe, _probe = _probe, None      # the pair is one entry
+    try:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+    finally:
+        _probe = probe
+    alg_bytes = (M * Cc + M * pk.Cout + 9 * Cc + pk.Cout * Cc) * es
+    flops = 2 * M * Cc * 9 + 2 * M * pk.Cout * Cc
+    probe.append((e0, e1, alg_bytes, flops, (N, H, W, Cc, pk.Cout, "sep", d, fused)))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
