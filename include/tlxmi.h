@@ -357,6 +357,31 @@ int tlxmi_sepconv2d(const tlxmi_sepconv2d_desc* d, const void* x, const void* w_
                     const void* w_packed, const float* pw_scale, const float* pw_shift, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Depthwise 7x7 conv that feeds the LayerNorm fold: the first layer of a ConvNeXt block (classification/convnext.py:91-94, 106-111:
+ * dwconv -> LayerNorm -> pwconv1).
+ *     y[n][h][w][c] = sum_{r,s<7} x[n][h+r-3][w+s-3][c] * w[r][s][c] + bias[c]      zero padding 3, stride 1, dilation 1,
+ * fp32 accumulation, rounded to fp16 once on store; and, from the fp32 values BEFORE rounding,
+ *     partials[pixel][p] = (sum, sum of squares) of y[pixel][256 p .. 256 p + 255]  for p < ceil(C / 256)
+ * — `partials` is pixels x 4 x 2 floats, the layout tlxmi_linear_stats writes and tlxmi_linear_ln reads, so the tlxmi_linear_ln
+ * launch of pwconv1 consumes it with no launch in between; pairs past ceil(C / 256) are not written.  partials may be NULL
+ * (the conv only).  One writer per (pixel, plane), fixed summation order, no atomics: two launches give the same bits.
+ * x / y: N*H*W pixels of pitch x_ld / y_ld (C columns used); w_rsc: [7][7][C] fp16 (as tlxmi_dwconv2d); bias fp32 [C] or NULL.
+ * Supported (tlxmi_dwconv7_stats_supported() == 1, a pure shape predicate): fp16, R = S = 7, stride 1, pad 3, dilation 1,
+ * C % 8 == 0, 8 <= C <= 1024 (a row has four pairs), x_ld >= C and y_ld >= C multiples of 8, ((pixels - 1) * x_ld + C) * 2 < 2^31
+ * and the same for y_ld (32-bit byte offsets), pixels * 32 < 2^31 (the statistics, as tlxmi_linear_ln requires); buffers 16-byte
+ * aligned.  Anything else returns TLXMI_ERR_UNSUPPORTED (run tlxmi_dwconv2d, and tlxmi_layernorm, instead).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_dwconv7_desc {
+    int32_t dtype;
+    int32_t N, H, W, C;
+    int32_t R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+    int32_t x_ld, y_ld;
+} tlxmi_dwconv7_desc;
+int tlxmi_dwconv7_stats_supported(const tlxmi_dwconv7_desc* d);
+int tlxmi_dwconv7_stats(const tlxmi_dwconv7_desc* d, const void* x, const void* w_rsc, const float* bias, void* y, float* partials,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

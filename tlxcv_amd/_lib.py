@@ -39,6 +39,11 @@ class SepConvDesc(C.Structure):
         "x_ld", "y_ld", "act")] + [("act_param", C.c_float)]
 
 
+class DwConv7Desc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "dtype", "N", "H", "W", "C", "R", "S", "stride_h", "stride_w", "pad_h", "pad_w", "dil_h", "dil_w", "x_ld", "y_ld")]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "B", "Ntok", "heads", "hd")] + [
         ("scale", C.c_float), ("nW", C.c_int32)]
@@ -115,6 +120,7 @@ PROTOTYPES = {
     "tlxmi_argmax_lastdim": [_vp, _i, _l, _i, _i, _vp, _vp],
     "tlxmi_resize_bilinear": [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _l, _i, C.c_double, C.c_double, _vp],
     "tlxmi_sepconv2d": [C.POINTER(SepConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_dwconv7_stats": [C.POINTER(DwConv7Desc), _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -132,6 +138,7 @@ _SPECIAL = {
     "tlxmi_linear_ln_supported": ([_i, _l, _i, _i, _i, _i], C.c_int),
     "tlxmi_mlp_seam_supported": ([_i, _i, _i, _i], C.c_int),
     "tlxmi_sepconv2d_supported": ([C.POINTER(SepConvDesc)], C.c_int),
+    "tlxmi_dwconv7_stats_supported": ([C.POINTER(DwConv7Desc)], C.c_int),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

@@ -40,6 +40,9 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
             "sepconv": True,      # DeepLabV3+'s separable convs (fp16): depthwise 3x3 + BN -> pointwise 1x1 + BN + ReLU as one launch
                                   # (tlxmi_sepconv2d), the depthwise map kept on chip; off = tlxmi_dwconv2d then tlxmi_conv2d (the A/B and
                                   # the tests' other arm)
+            "dwconv7": True,      # ConvNeXt's depthwise 7x7 (fp16) on tlxmi_dwconv7_stats: the input tile staged in LDS once, the taps in registers,
+                                  # and the row statistics of the LayerNorm fold out of the same launch; off = tlxmi_dwconv2d (+ tlxmi_layernorm
+                                  # in the model): the A/B and the tests' other arm
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1002,6 +1005,51 @@ def dwconv2d(x, w_rsc, stride=1, padding=0, dilation=1, scale=None, shift=None, 
                         act_param=float(act_param))
     _lib.call("tlxmi_dwconv2d", C.byref(d), _p(x), _p(w_rsc), _p(scale), _p(shift), _p(y), _stream())
     return y
+
+
+def _dwconv7_desc(x, Cc, y_ld):
+    N, H, W, ld = x.shape
+    return _lib.DwConv7Desc(dtype=dt_code(x.dtype), N=N, H=H, W=W, C=Cc, R=7, S=7, stride_h=1, stride_w=1, pad_h=3, pad_w=3, dil_h=1, dil_w=1,
+                            x_ld=ld, y_ld=y_ld)
+
+
+def dwconv7_supported(x, Cc=None):
+    """Whether dwconv7_stats() runs tlxmi_dwconv7_stats on this dense NHWC map (the "dwconv7" option on, fp16, the library takes the shape)."""
+    Cc = x.shape[-1] if Cc is None else Cc
+    return bool(_options["dwconv7"] and x.dtype == torch.float16 and x.is_contiguous()
+                and _lib.load().tlxmi_dwconv7_stats_supported(C.byref(_dwconv7_desc(x, Cc, Cc))))
+
+
+def dwconv7_stats(x, w_rsc, bias=None, stats=True, fused=None):
+    """ConvNeXt's depthwise conv (convnext.py:91-93: 7x7, stride 1, padding 3, + bias): x (N, H, W, C) NHWC, w_rsc [7][7][C], bias fp32 [C]
+    or None -> (y (N, H, W, C), part).  On tlxmi_dwconv7_stats (fp16, the "dwconv7" option, shapes the library takes) part is the
+    (N*H*W, 4, 2) fp32 (sum, sum of squares) per 256-channel plane of the fp32 y before rounding — what linear_ln() reads — when
+    `stats`, else None.  Otherwise tlxmi_dwconv2d runs and part is None: the caller keeps its layernorm() launch.
+    fused=True / False forces one form (tests, tools/)."""
+    need_gpu(x, "input")
+    N, H, W, Cc = x.shape
+    if tuple(w_rsc.shape) != (7, 7, Cc) or w_rsc.dtype != x.dtype or not x.is_contiguous():
+        raise RuntimeError(f"dwconv7_stats: a dense NHWC map and a [7][7][{Cc}] filter of its dtype are expected, got {tuple(x.shape)} / {tuple(w_rsc.shape)}")
+    if fused is None:
+        fused = dwconv7_supported(x)
+    es = x.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * es)
+    part = None
+    if _probe is not None:
+        e0, e1 = _probe_pair()
+    if fused:
+        y = torch.empty_like(x)
+        if stats:
+            part = torch.empty((N * H * W, 4, 2), dtype=torch.float32, device=x.device)      # pair p < ceil(C / 256) written
+        _lib.call("tlxmi_dwconv7_stats", C.byref(_dwconv7_desc(x, Cc, Cc)), _p(x), _p(w_rsc), _p(bias), _p(y), _p(part), _stream())
+    else:
+        y = dwconv2d(x, w_rsc, 1, 3, 1, None, bias)
+    if _probe is not None:
+        e1.record()
+        _probe.append((e0, e1, 2 * x.numel() * es + 49 * Cc * es + (part.numel() * 4 if part is not None else 0), 2 * 49 * x.numel(),
+                       (N, H, W, Cc, Cc, 7, 1, "dwconv7" if fused else "dwconv2d")))
+    return y, part
 
 
 _conv2d = conv2d        # the unfused arm of sepconv2d (a tool that wraps E.conv2d sees the pair as one separable conv)

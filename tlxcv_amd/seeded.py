@@ -50,6 +50,7 @@ def fill(shapes, seed):
       *.moving_var               U(0.8, 1.2)
       pos_embed / cls_token / relative_position_bias_table   N(0, 0.02) clipped at 2 sigma
       *_weight (attention projections, out x in)   N(0, sqrt(1/fan_in));   *_bias   N(0, 0.02)
+      *.weight (1-D) / *.bias    the channels-first LayerNorm of ConvNeXt: as gamma / beta
     """
     rng = np.random.default_rng(seed)
     out = {}
@@ -77,6 +78,10 @@ def fill(shapes, seed):
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(np.sqrt(1.0 / shape[1]))
         elif leaf.endswith("_bias"):
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(0.02)
+        elif leaf == "weight" and len(shape) == 1:              # ChannelsFirstLayerNorm (convnext.py:61-64): as gamma
+            a = rng.uniform(0.8, 1.2, shape).astype(np.float32)
+        elif leaf == "bias":                                    # ... as beta
+            a = rng.standard_normal(shape, dtype=np.float32) * np.float32(0.05)
         else:
             raise KeyError(f"seeded.fill: no rule for parameter {name!r}")
         out[name] = np.ascontiguousarray(a, dtype=np.float32)

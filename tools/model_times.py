@@ -16,7 +16,8 @@ CASES = [("resnet18", 256, 224, False), ("resnet34", 256, 224, False), ("resnet5
          ("MobileNetV1", 256, 224, False), ("mobilenet_v2", 256, 224, False), ("mobilenet_v3_small", 256, 224, False),
          ("mobilenet_v3_large", 256, 224, False), ("DarkNet", 64, 256, True), ("YOLOv3", 32, 416, True),
          ("vit_small_patch16_224", 256, 224, False), ("vit_base_patch16_224", 256, 224, False),
-         ("swintransformer_tiny_patch4_window7_224", 128, 224, False), ("swintransformer_base_patch4_window7_224", 128, 224, False)]
+         ("swintransformer_tiny_patch4_window7_224", 128, 224, False), ("swintransformer_base_patch4_window7_224", 128, 224, False),
+         ("convnext", 256, 224, False)]
 only = sys.argv[1].split(",") if len(sys.argv) > 1 else None
 for ctor, bs, hw, dict_in in CASES:
     if only and ctor not in only:
