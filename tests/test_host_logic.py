@@ -260,3 +260,66 @@ def test_chunk_sizes_keep_every_chunk_below_the_2_GiB_operand_limit():
             assert len(sizes) == 1 or -(-batch // (len(sizes) - 1)) * per >= E.ACT_LIMIT       # no fewer chunks would do
     with pytest.raises(RuntimeError, match="2 GiB"):
         E.chunk_sizes(2, 1 << 31)
+
+
+# ---- the feature x kernel matrix of tlxmi_conv2d (dispatch_matrix.py, test_conv_dispatch_matrix_gpu.py): its float64 reference
+# and its shape, checked without a GPU
+def _dm_ids(c):
+    return c.name
+
+
+def _dm_cases():
+    import dispatch_matrix as DM
+    return DM.CASES
+
+
+@pytest.mark.parametrize("case", _dm_cases(), ids=_dm_ids)
+def test_dispatch_matrix_reference_agrees_with_the_oracle(case):
+    """The float64 reference of every matrix case (explicit one-sided padding + slicing) against oracle.functional.conv_bn_act
+    in fp32 (symmetric over-padding + a shifted slice), on the fp32 and on the fp16-rounded inputs, within util.tol(fp32)."""
+    import dispatch_matrix as DM
+    from util import tol
+    for dtype in DM.DTYPES:
+        t = DM.make_inputs(case, dtype)
+        ref = DM.reference(case, t)
+        L = DM.layout(case, dtype)
+        assert tuple(ref.shape) == (case.N, L.Ho, L.Wo, case.Cout) and ref.dtype == torch.float64
+        torch.testing.assert_close(ref.float(), DM.oracle_reference(case, t), **tol(torch.float32))
+
+
+def test_dispatch_matrix_has_every_required_pair():
+    """a - d, h, i on every product-reachable kernel, e / f / g / j on the four small igemm tiles, in fp16 and fp32 (fp16 only:
+    conv_halo, gemm_wreg); the special shapes the matrix must contain; no case outside a kernel's documented conditions."""
+    import dispatch_matrix as DM
+    from tlxcv_amd import _lib
+    have = {(c.feat, kn, dt) for c, dt, kn in DM.CELLS}
+    for kn in DM.KERNELS:
+        for dt in DM.DTYPES:
+            if kn in DM.FP16_ONLY and dt != torch.float16:
+                assert not any(k == kn and d == dt for _, k, d in have)
+                continue
+            feats = "abci" if kn == "wreg" else "abcdhi" if kn not in ("gemm256_6", "stream8") else "abcdi"
+            if kn in ("igemm0", "igemm1", "igemm2", "igemm3"):
+                feats += "efgj"
+            if kn == "stream8" and dt != torch.float16:
+                feats = feats.replace("d", "")         # gemm_stream takes a residual in fp16 only
+            missing = [f for f in feats if (f, kn, dt) not in have]
+            assert not missing, (kn, dt, missing)
+    # GEMM-family kernels never appear where the batch strides or the row alignment rule them out
+    assert not any(f in "efgj" and kn in DM.GEMM_FAMILY + DM.FP16_ONLY for f, kn, _ in have)
+    for c in DM.CASES:
+        for dt in DM.DTYPES:
+            L, es = DM.layout(c, dt), DM.es_of(dt)
+            assert L.M <= 40000 and (c.Cin * es) % 16 == 0 and (L.x_ld * es) % 16 == 0 and (c.x_off * es) % 16 == 0
+            assert L.x_ld >= c.x_off + c.Cin and L.y_ld >= c.y_off + c.Cout and L.res_ld >= c.res_off + c.Cout
+            ktiles = -(-(c.R * c.S * (c.Cin // c.groups) * es // 16) // 8)
+            assert 1 <= ktiles <= 80
+            if c.groups > 1:
+                n = DM.group_chunks(c.Cin, c.Cout, c.groups, es)
+                assert n > 1 and n == _lib.load().tlxmi_group_conv_chunks(c.Cin, c.Cout, c.groups, 0 if es == 2 else 1)
+    f16 = torch.float16
+    kch = lambda c: c.R * c.S * c.Cin * 2 // 16      # noqa: E731
+    assert any(kch(c) % 8 for c in DM.CASES) and any(DM.layout(c, f16).M % 256 for c in DM.CASES)
+    assert any(c.Cout % 8 == 0 and c.Cout % 64 and c.Cout % 128 and c.Cout % 256 for c in DM.CASES)
+    assert any(kch(c) <= 8 for c in DM.CASES) and any(kch(c) >= 320 for c in DM.CASES)          # 1 .. 40 K tiles in fp16
+    assert any(DM.out_hw(c)[2] for c in DM.CASES) and any(c.out_hw and not DM.out_hw(c)[2] for c in DM.CASES)

@@ -72,7 +72,19 @@ def check_fp16_logits(got, ref, gold_argmax, name):
     bound = max(3.0 * FP16_OBSERVED.get(name, 0.0), 0.003 * rng_)
     s = np.sort(ref, axis=1)
     margin = s[:, -1] - s[:, -2]
+    return _record_and_assert_fp16(got, ref, gold_argmax, name, err, rng_, bound, margin)
+
+
+def report_dir():
+    """Where the GPU tests leave their figures (fp16_err.txt, dispatch_matrix.txt); they write only when it exists."""
+    import os
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+    return out
+
+
+def _record_and_assert_fp16(got, ref, gold_argmax, name, err, rng_, bound, margin):
+    import os
+    out = report_dir()
     if os.path.isdir(out):
         with open(os.path.join(out, "fp16_err.txt"), "a") as f:
             f.write(f"{name} err={err:.4e} range={rng_:.4f} frac={err / rng_:.2e} max_margin={margin.max():.3e}\n")

@@ -526,6 +526,16 @@ __global__ __launch_bounds__(WGM * 128) void conv_igemm_kernel(const ConvArgs a0
 
 static int num_cus() { return device_cus(); }      // core.hip: cached per device
 
+// TLXMI_TRACE_TILES (tuning flavour): one stderr line per launch naming the kernel that actually runs, after every fallback
+// of the dispatcher (the "-> cand N" line below is the choice BEFORE them).  Nothing in the product library.
+#ifdef TLXMI_TUNING
+static void trace_launched(const char* name, int M, int N) {
+    if (tune_int("TLXMI_TRACE_TILES", 0)) fprintf(stderr, "launched %s M=%d N=%d\n", name, M, N);
+}
+#else
+static inline void trace_launched(const char*, int, int) {}
+#endif
+
 // resident blocks per CU for a tile shape: LDS bound (160 KiB) and the register allocation hipcc
 // reports for this kernel (128x128: 156 -> 3 waves/SIMD, others <= 128 -> 4)
 template <typename T, int BM, int BN, int WGM, int STAGES> static int launch(const ConvArgs& a, hipStream_t st) {
@@ -544,7 +554,8 @@ template <typename T, int BM, int BN, int WGM, int STAGES> static int launch(con
     lds += 2 * BN * sizeof(float);
     const long grid = (long)b.mtiles * b.ntiles;
     const bool is1x1 = a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0;
-    const bool resp = a.res && a.vec_io && !a.strided_n;
+    // (the prefetch reads whole 8-channel chunks: with Cout % 8 != 0 the partial last chunk of a row takes the per-element reads)
+    const bool resp = a.res && a.vec_io && !a.strided_n && a.Cout % 8 == 0;
     const void* fns[4] = {reinterpret_cast<const void*>(&conv_igemm_kernel<T, BM, BN, false, WGM, STAGES, false>),
                           reinterpret_cast<const void*>(&conv_igemm_kernel<T, BM, BN, false, WGM, STAGES, true>),
                           reinterpret_cast<const void*>(&conv_igemm_kernel<T, BM, BN, true, WGM, STAGES, false>),
@@ -610,6 +621,7 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
             h.y_bytes = (unsigned)((long long)a.N * (a.Ho / 2) * (a.Wo / 2) * a.y_ld * 2);
             h.res_bytes = 0u;
             h.pool = 1;
+            trace_launched("halo_pool", a.M, a.Cout);
             return launch_conv_halo(h, st, num_cus());
         }
         const int forced_h = (int)tune_int("TLXMI_HALO", -1);   // tuning flavour: 0 = off (A/B runs)
@@ -635,7 +647,10 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
             while (h.nring < 2 * (span + a.R - 1) + span) h.nring *= 2;
             h.x_bytes = a.x_bytes; h.w_bytes = a.w_bytes; h.y_bytes = a.y_bytes;
             h.res_bytes = a.res ? (unsigned)((long long)a.M * a.res_ld * 2) : 0u;
-            if ((long)h.nring * h.PWp * PB + 512 <= 160 * 1024) return launch_conv_halo(h, st, num_cus());
+            if ((long)h.nring * h.PWp * PB + 512 <= 160 * 1024) {
+                trace_launched("halo", a.M, a.Cout);
+                return launch_conv_halo(h, st, num_cus());
+            }
         }
     }
     if (pool) return fail(TLXMI_ERR_UNSUPPORTED, "conv2d: TLXMI_EPI_MAXPOOL_3S2P1 is an fp16-only fusion");
@@ -688,7 +703,10 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
         g.act = a.act; g.act_param = a.act_param; g.flags = a.flags; g.mtiles = g.ntiles = 0; g.gn = 1;
         g.x_bytes = a.x_bytes; g.w_bytes = a.w_bytes; g.y_bytes = a.y_bytes;
         g.res_bytes = a.res ? (unsigned)((long long)a.M * a.res_ld * (long long)sizeof(T)) : 0u;
-        if (gemm_wreg_ok(TLXMI_F16, g)) return launch_gemm_wreg(g, st);
+        if (gemm_wreg_ok(TLXMI_F16, g)) {
+            trace_launched("wreg", a.M, a.Cout);
+            return launch_gemm_wreg(g, st);
+        }
     }
     if (!gemm256_ok) cands[5].eff = cands[6].eff = cands[8].eff = cands[11].eff = 0.f;
     if (!gemm256_ok && !pp_conv_ok) cands[7].eff = 0.f;
@@ -780,7 +798,8 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
         }
     }
     const int forced = a.pp_slices > 1 ? -1 : (int)tune_int("TLXMI_TILE", -1);
-    if (forced >= 0 && forced < NC && !(cands[forced].bn == 128 && a.Cout <= 64) &&
+    // (candidate 4's 3-deep ring needs the >= 4 K tiles the cost model asks of it above)
+    if (forced >= 0 && forced < NC && !(cands[forced].bn == 128 && a.Cout <= 64) && (forced != 4 || a.ktiles >= 4) &&
         (forced < 5 || (forced <= 9 && gemm256_ok) || ((forced == 7 || forced == 9) && pp_conv_ok) ||
          (forced == 10 && (pp_conv128_ok || gemm128_ok)) || (forced == 11 && gemm256_ok))) best = forced;
 #ifdef TLXMI_TUNING
@@ -857,6 +876,7 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
             g.act = hi.act; g.act_param = hi.act_param; g.flags = hi.flags; g.mtiles = g.ntiles = 0; g.gn = 1;
             g.x_bytes = hi.x_bytes; g.w_bytes = hi.w_bytes; g.y_bytes = hi.y_bytes;
             g.res_bytes = hi.res ? (unsigned)((long long)hi.M * hi.res_ld * (long long)sizeof(T)) : 0u;
+            trace_launched("pp9", hi.M, hi.Cout);
             return launch_gemm_pp128(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g, st);
         }
     }
@@ -881,15 +901,19 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
         if (best == 11) {      // gemm_w4.hip is part of the tuning flavour only (make tune): the product never dispatches it (eff = 0)
 #ifdef TLXMI_TUNING
             g.ksteps = a.Kp_bytes / 128;
-            if (gemm_w4_ok(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g))
+            if (gemm_w4_ok(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g)) {
+                trace_launched("w4_11", a.M, a.Cout);
                 return launch_gemm_w4(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g, st, cus);
+            }
 #endif
             best = 8;
         }
         if (best == 8) {
             g.ksteps = a.Kp_bytes / 128;
-            if (gemm_stream_ok(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g))
+            if (gemm_stream_ok(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g)) {
+                trace_launched("stream8", a.M, a.Cout);
                 return launch_gemm_stream(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g, st, cus);
+            }
             best = 7;
         }
         if (best == 7 || best == 9 || best == 10) {
@@ -901,10 +925,14 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
                 g.res = nullptr; g.scale = g.shift = nullptr;
             }
             const int dt = sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32;
+            trace_launched(best == 7 ? "pp7" : best == 9 ? "pp9" : "pp10", a.M, a.Cout);
             return best == 7 ? launch_gemm_pp(dt, g, st) : best == 9 ? launch_gemm_pp128(dt, g, st) : launch_gemm_pp_n128(dt, g, st);
         }
+        trace_launched(best == 5 ? "gemm256_5" : "gemm256_6", a.M, a.Cout);
         return launch_gemm256(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, best - 5, g, st);
     }
+    static const char* const igemm_names[5] = {"igemm0", "igemm1", "igemm2", "igemm3", "igemm4"};
+    trace_launched(igemm_names[best >= 0 && best <= 4 && best != 3 ? best : 3], a.M, a.Cout);
     switch (best) {
         case 0: return launch<T, 128, 128, 2, 2>(a, st);
         case 1: return launch<T, 64, 128, 2, 2>(a, st);
