@@ -382,6 +382,25 @@ int tlxmi_dwconv7_stats(const tlxmi_dwconv7_desc* d, const void* x, const void* 
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pre-activation 1x1 conv: BatchNorm + ReLU applied to the INPUT of a 1x1 conv inside the GEMM — DenseNet's BNACConvLayer
+ * (classification/densenet.py:31-46) with a 1x1 filter: the bottleneck conv of every DenseLayer and the conv of every TransitionLayer.
+ *     a[m][k] = fp16( pre( x[m*x_ld + k] * pre_scale[k] + pre_shift[k] ) )   k < K   (fp32 arithmetic, rounded once)
+ *     y[m*y_ld + n] = act( (sum_k a[m][k] * W[n][k]) * scale[n] + shift[n] )          n < Cout, m < rows
+ * x is a channel PREFIX of a wider buffer (x_ld >= K): columns k >= K are never multiplied, whatever they hold (NaN included).
+ * y is a column slice of a wider buffer (y_ld >= Cout); nothing outside rows x Cout is written.  w_packed: tlxmi_pack_filter of
+ * the [Cout][K][1][1] filter; pre_scale / pre_shift: fp32 [K]; scale / shift: fp32 [Cout] or NULL (1 / 0); pre_act, act:
+ * TLXMI_ACT_NONE or TLXMI_ACT_RELU.
+ * tlxmi_preact_conv1x1_supported() is pure host code and answers 1 exactly for: fp16; K, Cout, x_ld, y_ld positive multiples of 8
+ * with x_ld >= K and y_ld >= Cout; pre_act, act none or ReLU; rows > 0 with rows * x_ld * 2 and rows * y_ld * 2 below 2^31.  1 means
+ * the call is taken, given x, pre_scale, pre_shift, w_packed and y 16-byte aligned (TLXMI_ERR_ALIGNMENT otherwise); anything the
+ * predicate refuses returns TLXMI_ERR_UNSUPPORTED (run tlxmi_affine_act + tlxmi_conv2d instead).
+ * ---------------------------------------------------------------------------------------- */
+int tlxmi_preact_conv1x1_supported(int dtype, int64_t rows, int K, int Cout, int x_ld, int y_ld, int pre_act, int act);
+int tlxmi_preact_conv1x1(int dtype, int64_t rows, int K, int Cout, int x_ld, int y_ld, const void* x, const float* pre_scale,
+                         const float* pre_shift, int pre_act, const void* w_packed, const float* scale, const float* shift, int act,
+                         void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

@@ -1,0 +1,113 @@
+"""CPU-side tests of DenseNet: the five factories build with the reference's channel plans, the parameter tree is the fixtures' (and the
+reference model file's where the reference tree is present), the plain-torch restatement reproduces the fixtures' logits from the seeded
+weights, and a forward in train mode is refused."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, REPO
+
+FIXTURES = ["densenet121_b2.npz", "densenet121_c10_96x160_b1.npz"]
+VALUES_1000 = 8062504           # DenseNet-121 at 1000 classes; the head holds 1025 per class
+
+
+@pytest.mark.parametrize("layers,init,growth,config,features", [
+    (121, 64, 32, [6, 12, 24, 16], 1024), (161, 96, 48, [6, 12, 36, 24], 2208), (169, 64, 32, [6, 12, 32, 32], 1664),
+    (201, 64, 32, [6, 12, 48, 32], 1920), (264, 64, 32, [6, 12, 64, 48], 2688)])
+def test_factories_and_channel_plans(layers, init, growth, config, features):
+    from tlxcv_amd import models
+    from tlxcv_amd.models.classification import densenet as D
+    m = getattr(models, f"densenet{layers}")(num_classes=10)
+    assert isinstance(m, models.DenseNet) and m.block_config == config and m.num_features == features
+    assert tuple(m.conv1_func._conv.filters.shape) == (init, 3, 7, 7)
+    c = init
+    for i, (blk, n) in enumerate(zip(m.dense_block_func_list, config)):
+        assert isinstance(blk, D.DenseBlock) and len(blk.dense_layer_func) == n and blk.num_channels == c
+        for j, layer in enumerate(blk.dense_layer_func):
+            assert isinstance(layer, D.DenseLayer) and layer is getattr(blk, f"conv{i + 2}_{j + 1}")
+            assert tuple(layer.bn_ac_func1._conv.filters.shape) == (4 * growth, c + j * growth, 1, 1)
+            assert tuple(layer.bn_ac_func2._conv.filters.shape) == (growth, 4 * growth, 3, 3)
+            assert layer.bn_ac_func1.batch_norm.num_features == c + j * growth
+        c += n * growth
+        assert blk.out_channels == c
+        if i < 3:
+            tr = m.transition_func_list[i]
+            assert isinstance(tr, D.TransitionLayer) and tr is getattr(m, f"tr_conv{i + 2}_blk")
+            assert tuple(tr.conv_ac_func._conv.filters.shape) == (c // 2, c, 1, 1)
+            c //= 2
+    assert c == features and tuple(m.out.weights.shape) == (features, 10) and m.batch_norm.num_features == features
+
+
+@pytest.mark.parametrize("fname", FIXTURES)
+def test_parameter_tree_matches_fixture(fname):
+    from tlxcv_amd import seeded
+    from tlxcv_amd.models import densenet121
+    g = np.load(os.path.join(GOLDEN, fname))
+    assert str(g["arch"]) == "densenet121"
+    m = densenet121(num_classes=int(g["num_classes"]))
+    shapes = seeded.shapes_of(m)
+    assert list(shapes.keys()) == list(g["param_names"])          # the lists that hold the same modules add no second name
+    assert len(shapes) == 606
+    assert sum(int(np.prod(s)) for s in shapes.values()) == VALUES_1000 + (int(g["num_classes"]) - 1000) * 1025
+    names = list(shapes)
+    assert names[:2] == ["conv1_func._conv.filters", "conv1_func.batch_norm.gamma"]
+    assert "db_conv_2.conv2_1.bn_ac_func1.batch_norm.gamma" in shapes and "tr_conv2_blk.conv_ac_func._conv.filters" in shapes
+    assert names[-6:] == ["batch_norm.gamma", "batch_norm.beta", "batch_norm.moving_mean", "batch_norm.moving_var", "out.weights", "out.biases"]
+
+
+def test_constructor_arguments_and_refusals():
+    from tlxcv_amd.models import DenseNet, densenet121, densenet161
+    m = DenseNet()
+    assert m.block_config == [6, 12, 24, 16] and m.num_classes == 1000 and m.with_pool
+    assert tuple(DenseNet(bn_size=2).db_conv_2.conv2_1.bn_ac_func1._conv.filters.shape) == (64, 64, 1, 1)
+    d = DenseNet(dropout=0.2, num_classes=0)
+    assert not hasattr(d, "out") and hasattr(d.db_conv_2.conv2_1, "dropout_func")
+    assert not hasattr(DenseNet(with_pool=False), "pool2d_avg")
+    with pytest.raises(AssertionError, match="supported layers"):
+        DenseNet(layers=50)
+    with pytest.raises(NotImplementedError, match="pretrained"):
+        densenet121(pretrained=True)
+    with pytest.raises(NotImplementedError, match="set_eval"):
+        m(torch.zeros(1, 3, 32, 32))                               # train mode: refused like the other models
+    with pytest.raises(NotImplementedError, match="set_eval"):
+        densenet161(num_classes=10).db_conv_2(torch.zeros(1, 96, 8, 8))
+
+
+def test_parameter_tree_matches_reference_model_file():
+    from oracle.gen_golden import REF
+    if not os.path.isfile(os.path.join(REF, "tlxcv", "models", "classification", "densenet.py")):
+        pytest.skip("reference tree not present")
+    code = ("import sys; sys.path.insert(0, 'tools'); import gen_densenet_golden as G; from tlxcv_amd import seeded; "
+            "ref, _ = G.reference_module(); "
+            "print('\\n'.join(f'{k} {v}' for k, v in seeded.shapes_of(ref.densenet161()).items()))")
+    out = subprocess.check_output([sys.executable, "-c", code], cwd=REPO, text=True)
+    from tlxcv_amd import seeded
+    from tlxcv_amd.models import densenet161
+    mine = [f"{k} {tuple(v)}" for k, v in seeded.shapes_of(densenet161()).items()]
+    assert out.strip().splitlines() == mine
+
+
+@pytest.mark.parametrize("fname", FIXTURES)
+def test_fp32_restatement_reproduces_the_fixture(fname):
+    """float32 restatement on seeded.fill weights against the logits the reference file gave in float64: 1e-4 of the row's logit scale,
+    same argmax; and the margin rule that keeps the GPU test's fp16 argmax check from being vacuous."""
+    import densenet_restated as RS
+    from tlxcv_amd import seeded
+    from tlxcv_amd.models import densenet121
+    from util import check_fp32_logits
+    g = np.load(os.path.join(GOLDEN, fname))
+    params = seeded.fill(seeded.shapes_of(densenet121(num_classes=int(g["num_classes"]))), int(g["weight_seed"]))
+    x = torch.from_numpy(RS.densenet_input(int(g["batch"]), int(g["input_seed"]), *[int(v) for v in g["hw"]]))
+    torch.set_num_threads(8)
+    with torch.no_grad():
+        out = RS.densenet({k: torch.from_numpy(v) for k, v in params.items()}, x).numpy()
+    err = check_fp32_logits(out, g["logits"], fname[:-4])
+    print(f"{fname}: fp32 restatement vs fixture max|err| = {err:.3e}")
+    assert (out.argmax(-1) == g["argmax"]).all()
+    s = np.sort(g["logits"], axis=1)
+    need = 2 * 0.003 * float(g["logits"].max() - g["logits"].min())
+    assert ((s[:, -1] - s[:, -2]) > need).all()                    # no row is left out of the argmax check

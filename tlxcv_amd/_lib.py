@@ -121,6 +121,7 @@ PROTOTYPES = {
     "tlxmi_resize_bilinear": [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _l, _i, C.c_double, C.c_double, _vp],
     "tlxmi_sepconv2d": [C.POINTER(SepConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_dwconv7_stats": [C.POINTER(DwConv7Desc), _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_preact_conv1x1": [_i, _l, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -139,6 +140,7 @@ _SPECIAL = {
     "tlxmi_mlp_seam_supported": ([_i, _i, _i, _i], C.c_int),
     "tlxmi_sepconv2d_supported": ([C.POINTER(SepConvDesc)], C.c_int),
     "tlxmi_dwconv7_stats_supported": ([C.POINTER(DwConv7Desc)], C.c_int),
+    "tlxmi_preact_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i], C.c_int),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

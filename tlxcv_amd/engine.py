@@ -43,6 +43,9 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
             "dwconv7": True,      # ConvNeXt's depthwise 7x7 (fp16) on tlxmi_dwconv7_stats: the input tile staged in LDS once, the taps in registers,
                                   # and the row statistics of the LayerNorm fold out of the same launch; off = tlxmi_dwconv2d (+ tlxmi_layernorm
                                   # in the model): the A/B and the tests' other arm
+            "preact": True,       # DenseNet's pre-activation 1x1 convs (fp16): BatchNorm + ReLU of the INPUT applied on the way to the MFMA
+                                  # (tlxmi_preact_conv1x1), the concat prefix read once; off = tlxmi_affine_act into a dense temporary then
+                                  # tlxmi_conv2d (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1111,10 +1114,59 @@ def sepconv2d(x, w_dw, dw_scale, dw_shift, pk, pw_scale, pw_shift, dilation, act
     return out
 
 
+def preact_conv1x1(x, pre_scale, pre_shift, pk, scale=None, shift=None, act=ACT_NONE, out=None, out_ld=None, fused=None, pre_act=ACT_RELU):
+    """BNACConvLayer with a 1x1 filter (densenet.py:31-46): y = act(conv1x1(pre_act(x * pre_scale + pre_shift)) * scale + shift).
+    x (N, H, W, x_ld) NHWC (or (rows, x_ld)): the first K = pk.Cin channels of each pixel are the operand — a channel prefix of a dense
+    block's buffer; the columns behind K are never used, whatever they hold.  pre_scale / pre_shift: fp32 [K] -> y (N, H, W, Cout), or
+    written into `out` (a column slice of a wider buffer, pixel pitch out_ld).  One launch (tlxmi_preact_conv1x1) when the "preact"
+    option is on, the precision is fp16 and the library takes the shape; otherwise tlxmi_affine_act into a dense K-channel temporary
+    then tlxmi_conv2d (fp32 always: the parity reference).  fused=True / False forces one form (tests, tools/)."""
+    global _probe
+    need_gpu(x, "input")
+    if x.dim() == 2:
+        x = x.view(x.shape[0], 1, 1, x.shape[1])
+    N, H, W, ld = x.shape
+    K = pk.Cin
+    if pk.R != 1 or pk.S != 1 or x.dtype != pk.dtype or ld < K or not x.is_contiguous() or K % vec(x.dtype):
+        raise RuntimeError(f"preact_conv1x1: x must be a dense NHWC map of the filter's dtype with at least K = {K} channels (a multiple of "
+                           f"{vec(x.dtype)}) and the filter 1x1; got {tuple(x.shape)} {x.dtype} for a {pk.R}x{pk.S} filter")
+    if pre_scale is None or pre_shift is None or pre_scale.numel() != K or pre_shift.numel() != K:
+        raise RuntimeError(f"preact_conv1x1: pre_scale / pre_shift must hold K = {K} values")
+    if out is None:
+        out = torch.empty((N, H, W, pk.Cout), dtype=x.dtype, device=x.device)
+        out_ld = pk.Cout
+    elif out_ld is None:
+        out_ld = out.shape[-1]
+    es = x.element_size()
+    M = N * H * W
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * es, M * out_ld * es)
+    if fused is None:
+        fused = bool(_options["preact"] and x.dtype == torch.float16
+                     and _lib.load().tlxmi_preact_conv1x1_supported(F16, M, K, pk.Cout, ld, out_ld, pre_act, act))
+    if not fused:
+        t = torch.empty((N, H, W, K), dtype=x.dtype, device=x.device)
+        _lib.call("tlxmi_affine_act", _p(x), _p(pre_scale), _p(pre_shift), None, _p(t), dt_code(x.dtype), M, K, ld, 0, K, pre_act, 0.0, 0,
+                  _stream())
+        conv2d(t, pk, 1, 0, 1, scale, shift, act=act, out=out, out_ld=out_ld)
+        return out
+    args = (F16, M, K, pk.Cout, ld, out_ld, _p(x), _p(pre_scale), _p(pre_shift), pre_act, _p(pk.buf), _p(scale), _p(shift), act, _p(out), _stream())
+    if _probe is None:
+        _lib.call("tlxmi_preact_conv1x1", *args)
+        return out
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    _lib.call("tlxmi_preact_conv1x1", *args)
+    e1.record()
+    _probe.append((e0, e1, (M * K + M * pk.Cout + pk.Cout * K) * es, 2 * M * pk.Cout * K, (N, H, W, K, pk.Cout, "preact")))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # pooling / elementwise / norm
 # ---------------------------------------------------------------------------------------------
-def maxpool2d(x, kernel, stride, padding):
+def maxpool2d(x, kernel, stride, padding, out=None, out_ld=None):
+    """nn.MaxPool2d on an NHWC map -> (N, Ho, Wo, C), or written into `out` (a column slice of a wider buffer, pixel pitch out_ld)."""
     need_gpu(x, "input")
     N, H, W, Cc = x.shape
     R, S = _pair(kernel)
@@ -1122,14 +1174,15 @@ def maxpool2d(x, kernel, stride, padding):
     ph, pw = _pair(padding)
     Ho = (H + 2 * ph - R) // sh + 1
     Wo = (W + 2 * pw - S) // sw + 1
-    y = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
-    _lib.call("tlxmi_maxpool2d", _p(x), _p(y), dt_code(x.dtype), N, H, W, Cc, Cc, Cc, R, S, sh, sw, ph, pw, Ho, Wo,
+    y = out if out is not None else torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
+    y_ld = Cc if out is None else (out_ld if out_ld is not None else out.shape[-1])
+    _lib.call("tlxmi_maxpool2d", _p(x), _p(y), dt_code(x.dtype), N, H, W, Cc, Cc, y_ld, R, S, sh, sw, ph, pw, Ho, Wo,
               _stream())
     return y
 
 
-def avgpool2d(x, kernel, stride, padding):
-    """nn.AvgPool2d on an NHWC map; zero padding counts in the divisor."""
+def avgpool2d(x, kernel, stride, padding, out=None, out_ld=None):
+    """nn.AvgPool2d on an NHWC map; zero padding counts in the divisor.  `out` / out_ld as maxpool2d."""
     need_gpu(x, "input")
     N, H, W, Cc = x.shape
     R, S = _pair(kernel)
@@ -1137,8 +1190,9 @@ def avgpool2d(x, kernel, stride, padding):
     ph, pw = _pair(padding)
     Ho = (H + 2 * ph - R) // sh + 1
     Wo = (W + 2 * pw - S) // sw + 1
-    y = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
-    _lib.call("tlxmi_avgpool2d", _p(x), _p(y), dt_code(x.dtype), N, H, W, Cc, Cc, Cc, R, S, sh, sw, ph, pw, Ho, Wo, _stream())
+    y = out if out is not None else torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
+    y_ld = Cc if out is None else (out_ld if out_ld is not None else out.shape[-1])
+    _lib.call("tlxmi_avgpool2d", _p(x), _p(y), dt_code(x.dtype), N, H, W, Cc, Cc, y_ld, R, S, sh, sw, ph, pw, Ho, Wo, _stream())
     return y
 
 

@@ -17,3 +17,5 @@ from .resnext import (ResNeXt, resnext50_32x4d, resnext50_64x4d, resnext101_32x4
 from .efficientnet import efficientnet, EfficientNet  # noqa: F401
 from .resnest import resnest50_fast_1s1x64d, resnest50, resnest101, ResNeSt  # noqa: F401
 from .convnext import ConvNeXt, convnext, Block, ChannelsFirstLayerNorm, DropPath  # noqa: F401
+from .densenet import (DenseNet, densenet121, densenet161, densenet169, densenet201, densenet264, BNACConvLayer, DenseLayer,  # noqa: F401
+                       DenseBlock, TransitionLayer, ConvBNLayer)
