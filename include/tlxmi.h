@@ -559,6 +559,25 @@ int tlxmi_mha(const tlxmi_mha_desc* d, const void* q, const void* k, const void*
               void* out, float* avg_weights, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Spatial-reduction attention: MANY queries against FEW keys on MFMA — the attention of PVTv2 (classification/pvt_v2.py:108-146) and of
+ * the other hierarchical transformers that shrink K / V with a strided conv: the queries are every token of a stage (3136 / 784 / 196 /
+ * 49 at 224 x 224), the keys and values a few dozen rows of the `kv` Linear.  The descriptor is tlxmi_mha's: separate, strided q, k, v
+ * and out, head h of a row at offset h*hd (a packed kv matrix [B][Lk][2][heads][hd]: k = kv, v = kv + heads*hd, both with row stride
+ * 2*heads*hd).
+ *   out[b][i][h*hd + :] = sum_j softmax_j( scale * q_i . k_j ) v_j
+ * K and V of one (image, head) are staged once per workgroup in LDS and every wave walks 16-query tiles; the softmax is one pass in
+ * registers (no running maximum: Lk <= 64), the probabilities rounded to fp16 feed the second MFMA and the fp32 sum divides its result.
+ * Key rows >= Lk and query rows >= Lq are never read and output rows >= Lq never written, whatever lies behind them; one writer per
+ * output element and a fixed summation order (two launches give the same bits).
+ * tlxmi_sr_attention_supported() is pure host code and answers 1 exactly for: fp16; hd 32 or 64; 1 <= Lk <= 64; B, heads, Lq >= 1;
+ * mask_mode 0; every stride a non-negative multiple of 8 elements; each tensor's byte extent ((B-1)*batch stride + (L-1)*row stride
+ * + heads*hd) * 2 below 2^31; output rows that do not overlap (batch-major or sequence-major).  1 means the call is taken, given q, k, v
+ * and out 16-byte aligned; everything else returns TLXMI_ERR_UNSUPPORTED (run tlxmi_mha instead).
+ * ---------------------------------------------------------------------------------------- */
+int tlxmi_sr_attention_supported(const tlxmi_mha_desc* d);
+int tlxmi_sr_attention(const tlxmi_mha_desc* d, const void* q, const void* k, const void* v, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Swin window plumbing folded into index math (swin_transformer.py:85-116, 317-333):
  *   partition: x[B][H][W][C] --roll(-shift)--> windows [B*nW][ws*ws][C]
  *   reverse:   windows --> x (+roll(+shift)), optionally y = res + reverse(windows)

@@ -111,6 +111,7 @@ PROTOTYPES = {
     "tlxmi_attention_comb": [C.POINTER(AttnDesc), _vp, _vp, _vp, _vp],
     "tlxmi_attention_windows": [C.POINTER(AttnDesc), _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "tlxmi_mha": [C.POINTER(MhaDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_sr_attention": [C.POINTER(MhaDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_window_partition": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_window_reverse": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_patch_merge_gather": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -141,6 +142,7 @@ _SPECIAL = {
     "tlxmi_sepconv2d_supported": ([C.POINTER(SepConvDesc)], C.c_int),
     "tlxmi_dwconv7_stats_supported": ([C.POINTER(DwConv7Desc)], C.c_int),
     "tlxmi_preact_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i], C.c_int),
+    "tlxmi_sr_attention_supported": ([C.POINTER(MhaDesc)], C.c_int),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

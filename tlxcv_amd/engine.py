@@ -46,6 +46,9 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
             "preact": True,       # DenseNet's pre-activation 1x1 convs (fp16): BatchNorm + ReLU of the INPUT applied on the way to the MFMA
                                   # (tlxmi_preact_conv1x1), the concat prefix read once; off = tlxmi_affine_act into a dense temporary then
                                   # tlxmi_conv2d (the A/B and the tests' other arm)
+            "sr_attn": True,      # PVTv2's spatial-reduction attention (fp16, at most 64 keys, head dim 32 / 64) on tlxmi_sr_attention: K / V staged
+                                  # once per workgroup, both products on MFMA, the scores in registers; off = tlxmi_mha, the general kernel
+                                  # (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1422,6 +1425,45 @@ def mha(q, k, v, heads, scale, mask=None, need_weights=False, batch_first=False)
                      out_batch_stride=out.stride(bd), out_row_stride=out.stride(ld))
     _lib.call("tlxmi_mha", C.byref(d), _p(q), _p(k), _p(v), _p(mask), _p(out), _p(avg), _stream())
     return out, avg
+
+
+def sr_attention(q, kv, heads, scale, fused=None):
+    """Spatial-reduction attention (pvt_v2.py:108-146): q (B, Lq, C), kv (B, Lk, 2C) packed [2][heads][hd] as the `kv` Linear leaves it
+    -> (B, Lq, C) = softmax(scale * q k^T) v per head, with k = kv[..., :C] and v = kv[..., C:] read in place (two pointers into kv,
+    row stride 2C).  tlxmi_sr_attention (MFMA, the scores in registers) when the "sr_attn" option is on, the precision is fp16 and the
+    library takes the shape (hd 32 or 64, Lk <= 64); otherwise tlxmi_mha (fp32 always: the parity reference; Lk > 64: a 384 x 384
+    input leaves 144 keys).  fused=True / False forces one form (tests, tools/)."""
+    need_gpu(q, "q")
+    need_gpu(kv, "kv")
+    if q.dim() != 3 or kv.dim() != 3 or q.dtype != kv.dtype or kv.shape[0] != q.shape[0] or kv.shape[2] != 2 * q.shape[2] or q.shape[2] % heads:
+        raise RuntimeError(f"sr_attention: q (B, Lq, C) and kv (B, Lk, 2C) of one dtype with C a multiple of heads = {heads} are expected, "
+                           f"got {tuple(q.shape)} {q.dtype} / {tuple(kv.shape)} {kv.dtype}")
+    if q.stride(-1) != 1 or kv.stride(-1) != 1:
+        raise RuntimeError("sr_attention: the feature axis must be dense")
+    B, Lq, Cc = q.shape
+    Lk = kv.shape[1]
+    k, v = kv[..., :Cc], kv[..., Cc:]
+    out = torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device)
+    es = q.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(B * Lq * Cc * es, kv.numel() * es)
+    d = _lib.MhaDesc(dtype=dt_code(q.dtype), B=B, Lq=Lq, Lk=Lk, heads=heads, hd=Cc // heads, scale=float(scale), mask_mode=0,
+                     q_batch_stride=q.stride(0), q_row_stride=q.stride(1), k_batch_stride=k.stride(0), k_row_stride=k.stride(1),
+                     v_batch_stride=v.stride(0), v_row_stride=v.stride(1), out_batch_stride=out.stride(0), out_row_stride=out.stride(1))
+    if fused is None:
+        fused = bool(_options["sr_attn"] and q.dtype == torch.float16 and _lib.load().tlxmi_sr_attention_supported(C.byref(d))
+                     and all(t.data_ptr() % 16 == 0 for t in (q, k, v, out)))
+    if _probe is not None:
+        e0, e1 = _probe_pair()
+    if fused:
+        _lib.call("tlxmi_sr_attention", C.byref(d), _p(q), _p(k), _p(v), _p(out), _stream())
+    else:
+        _lib.call("tlxmi_mha", C.byref(d), _p(q), _p(k), _p(v), None, _p(out), None, _stream())
+    if _probe is not None:
+        e1.record()
+        _probe.append((e0, e1, (2 * B * Lq * Cc + 2 * B * Lk * Cc) * es, 4 * B * Lq * Lk * Cc,
+                       (B, Lq, Lk, heads, Cc // heads, "sr_attn" if fused else "mha")))
+    return out
 
 
 def yolo_box(heads_nhwc, anchors, num_classes, img_size, conf_thresh=0.005, downsample_ratio=32, clip_bbox=True, scale_x_y=1.0):

@@ -19,3 +19,5 @@ from .resnest import resnest50_fast_1s1x64d, resnest50, resnest101, ResNeSt  # n
 from .convnext import ConvNeXt, convnext, Block, ChannelsFirstLayerNorm, DropPath  # noqa: F401
 from .densenet import (DenseNet, densenet121, densenet161, densenet169, densenet201, densenet264, BNACConvLayer, DenseLayer,  # noqa: F401
                        DenseBlock, TransitionLayer, ConvBNLayer)
+# (the PVTv2 file's Mlp / Attention / Block / DWConv stay in their module: ConvNeXt's Block and DropPath own those names here)
+from .pvt_v2 import PyramidVisionTransformerV2, pvt_v2, OverlapPatchEmbed  # noqa: F401
