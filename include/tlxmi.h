@@ -401,6 +401,54 @@ int tlxmi_preact_conv1x1(int dtype, int64_t rows, int K, int Cout, int x_ld, int
                          void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Large-kernel attention of VAN (classification/van.py:83-121; the block's residual :146), two launches.
+ *
+ * tlxmi_lka_dw: LKA.conv0 -> LKA.conv_spatial (van.py:87-98), the intermediate map kept on chip:
+ *     a0[n][h][w][c] = fp16( sum_{r,s<5} t[n][h+r-2][w+s-2][c] * w0[r][s][c] + b0[c] )              zero padding 2
+ *     y [n][h][w][c] = fp16( sum_{r,s<7} a0[n][h+3(r-3)][w+3(s-3)][c] * w1[r][s][c] + b1[c] )       dilation 3, zero padding 9
+ * fp32 accumulation in tlxmi_dwconv2d's tap order, a0 rounded to fp16 once (as two tlxmi_dwconv2d launches store it); a0 at a
+ * position OUTSIDE the image is zero (the second conv's padding), not b0 + a partial sum.  x / y: N*H*W pixels of pitch x_ld / y_ld
+ * (C columns used); w0_rsc: [5][5][C], w1_rsc: [7][7][C] fp16 (as tlxmi_dwconv2d); b0, b1: fp32 [C] or NULL.  One writer per output
+ * element, fixed summation order, no atomics.
+ * tlxmi_lka_dw_supported() is pure host code and answers 1 exactly for: fp16; N, H, W >= 1; W <= 87 (one output row's tiles of an
+ * 8-channel slab fit in 64 KiB of LDS); C a positive multiple of 8; x_ld >= C and y_ld >= C multiples of 8;
+ * ((pixels - 1) * x_ld + C) * 2 < 2^31 and the same for y_ld (32-bit byte offsets).  1 means the call is taken, given x, w0_rsc,
+ * w1_rsc and y 16-byte aligned (TLXMI_ERR_ALIGNMENT otherwise); anything else returns TLXMI_ERR_UNSUPPORTED (run two tlxmi_dwconv2d
+ * launches instead).
+ *
+ * tlxmi_lka_gate: LKA.conv1 -> the gate `x * attn` -> Attention.proj_2 -> layer_scale_1 and the shortcut (van.py:99-100, :119-120, :146):
+ *     a2[m][k] = (sum_j a1[m][j] * W1[k][j]) * scale1[k] + shift1[k]                                   fp32
+ *     g [m][k] = fp16( t[m][k] * a2[m][k] )                                                            rounded once, stays on chip
+ *     y [m][n] = fp16( res[m][n] * res_scale[n] + (sum_k g[m][k] * W2[n][k]) * scale2[n] + shift2[n] )
+ * a1, t, res, y: rows x C fp16 of pitch a1_ld, t_ld, res_ld, y_ld; w1_packed, w2_packed: tlxmi_pack_filter of the [C][C][1][1]
+ * filters; scale1, shift1, scale2, shift2, res_scale: fp32 [C] or NULL (1 for a scale, 0 for a shift).  y aliases no input.  The
+ * shortcut of van.py:146 is the NORMALISED x, so the model passes res = x, res_scale = 1 + ls * bn_scale and folds ls * bn_shift
+ * into shift2.  Both products run on MFMA; fixed summation order, no atomics.
+ * tlxmi_lka_gate_supported() is pure host code and answers 1 exactly for: fp16; rows >= 1; C a multiple of 32, 32 <= C <= 256; every
+ * pitch >= C, a multiple of 8, with rows * pitch * 2 < 2^31.  1 means the call is taken, given every buffer 16-byte aligned
+ * (TLXMI_ERR_ALIGNMENT otherwise); anything else returns TLXMI_ERR_UNSUPPORTED (run tlxmi_conv2d, tlxmi_mul, tlxmi_affine_act,
+ * tlxmi_conv2d instead).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_lka_dw_desc {
+    int32_t dtype;
+    int32_t N, H, W, C;
+    int32_t x_ld, y_ld;
+} tlxmi_lka_dw_desc;
+int tlxmi_lka_dw_supported(const tlxmi_lka_dw_desc* d);
+int tlxmi_lka_dw(const tlxmi_lka_dw_desc* d, const void* x, const void* w0_rsc, const float* b0, const void* w1_rsc, const float* b1,
+                 void* y, void* stream);
+typedef struct tlxmi_lka_gate_desc {
+    int32_t dtype;
+    int64_t rows;
+    int32_t C;
+    int32_t a1_ld, t_ld, res_ld, y_ld;
+} tlxmi_lka_gate_desc;
+int tlxmi_lka_gate_supported(const tlxmi_lka_gate_desc* d);
+int tlxmi_lka_gate(const tlxmi_lka_gate_desc* d, const void* a1, const void* t, const void* w1_packed, const float* scale1,
+                   const float* shift1, const void* w2_packed, const float* scale2, const float* shift2, const void* res,
+                   const float* res_scale, void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.
@@ -438,6 +486,10 @@ int tlxmi_adaptive_avgpool2d(const void* x, void* y, int dtype, int N, int H, in
 int tlxmi_affine_act(const void* x, const float* scale, const float* shift, const void* res, void* y,
                      int dtype, int64_t rows, int C, int x_ld, int res_ld, int y_ld, int act,
                      float act_param, uint32_t flags, void* stream);
+
+/* Elementwise product y[m][c] = a[m][c] * b[m][c] of two row matrices of pitch a_ld / b_ld into pitch y_ld (fp16 or fp32, C a whole
+ * number of 16-byte chunks): VAN's gate `x * attn` (van.py:100) where tlxmi_lka_gate does not run. */
+int tlxmi_mul(const void* a, const void* b, void* y, int dtype, int64_t rows, int C, int a_ld, int b_ld, int y_ld, void* stream);
 
 /* Squeeze-Excitation gating (mobilenetv3.py:54-56 `scale * input`): y[n][p][c] = x[n][p][c] * s[n][c],
  * s is the (N, C) output of the SE bottleneck, same dtype as x. */

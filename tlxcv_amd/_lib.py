@@ -44,6 +44,14 @@ class DwConv7Desc(C.Structure):
         "dtype", "N", "H", "W", "C", "R", "S", "stride_h", "stride_w", "pad_h", "pad_w", "dil_h", "dil_w", "x_ld", "y_ld")]
 
 
+class LkaDwDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "C", "x_ld", "y_ld")]
+
+
+class LkaGateDesc(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in ("C", "a1_ld", "t_ld", "res_ld", "y_ld")]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "B", "Ntok", "heads", "hd")] + [
         ("scale", C.c_float), ("nW", C.c_int32)]
@@ -123,6 +131,9 @@ PROTOTYPES = {
     "tlxmi_sepconv2d": [C.POINTER(SepConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_dwconv7_stats": [C.POINTER(DwConv7Desc), _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_preact_conv1x1": [_i, _l, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp],
+    "tlxmi_lka_dw": [C.POINTER(LkaDwDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_lka_gate": [C.POINTER(LkaGateDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_mul": [_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -143,6 +154,8 @@ _SPECIAL = {
     "tlxmi_dwconv7_stats_supported": ([C.POINTER(DwConv7Desc)], C.c_int),
     "tlxmi_preact_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i], C.c_int),
     "tlxmi_sr_attention_supported": ([C.POINTER(MhaDesc)], C.c_int),
+    "tlxmi_lka_dw_supported": ([C.POINTER(LkaDwDesc)], C.c_int),
+    "tlxmi_lka_gate_supported": ([C.POINTER(LkaGateDesc)], C.c_int),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

@@ -486,6 +486,27 @@ __global__ void affine_act_kernel(const T* __restrict__ x, const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------
+// Elementwise product of two pitched row matrices (VAN's gate `x * attn`, van.py:100, outside the fused kernel).
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void mul_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ y, long rows, int C, int a_ld, int b_ld,
+                           int y_ld) {
+    constexpr int V = Chunk<T>::N;
+    const int nch = C / V;
+    const long total = rows * nch;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int cg = (int)(i % nch);
+        const long row = i / nch;
+        float v[V], u[V];
+        Chunk<T>::load(a + row * a_ld + cg * V, v);
+        Chunk<T>::load(b + row * b_ld + cg * V, u);
+#pragma unroll
+        for (int e = 0; e < V; ++e) v[e] *= u[e];
+        Chunk<T>::store(y + row * y_ld + cg * V, v);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Depthwise conv: one lane per (output pixel, channel chunk); taps re-read through L1/L2.
 // ------------------------------------------------------------------------------------------
 template <typename T>
@@ -1003,6 +1024,19 @@ extern "C" int tlxmi_affine_act(const void* x, const float* scale, const float* 
     else
         hipLaunchKernelGGL((affine_act_kernel<float>), g, b, 0, as_stream(stream), (const float*)x, scale, shift, (const float*)res, (float*)y, (long)rows, C, x_ld, res_ld, y_ld, act, ap, flags);
     return check_launch("affine_act");
+}
+
+extern "C" int tlxmi_mul(const void* a, const void* b, void* y, int dt, int64_t rows, int C, int a_ld, int b_ld, int y_ld, void* stream) {
+    TLXMI_REQUIRE(a && b && y && rows > 0, TLXMI_ERR_BAD_ARG, "mul: bad argument");
+    REQUIRE_CHUNKED("mul", dt, C, a_ld, b_ld, y_ld);
+    TLXMI_REQUIRE(aligned16(a) && aligned16(b) && aligned16(y), TLXMI_ERR_ALIGNMENT, "mul: buffers must be 16-byte aligned");
+    const long work = rows * (C / VECN(dt));
+    dim3 g(grid_for(work)), blk(256);
+    if (dt == TLXMI_F16)
+        hipLaunchKernelGGL((mul_kernel<half_t>), g, blk, 0, as_stream(stream), (const half_t*)a, (const half_t*)b, (half_t*)y, (long)rows, C, a_ld, b_ld, y_ld);
+    else
+        hipLaunchKernelGGL((mul_kernel<float>), g, blk, 0, as_stream(stream), (const float*)a, (const float*)b, (float*)y, (long)rows, C, a_ld, b_ld, y_ld);
+    return check_launch("mul");
 }
 
 extern "C" int tlxmi_dwconv2d(const tlxmi_dwconv2d_desc* d, const void* x, const void* w, const float* scale,

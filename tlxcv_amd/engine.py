@@ -49,6 +49,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
             "sr_attn": True,      # PVTv2's spatial-reduction attention (fp16, at most 64 keys, head dim 32 / 64) on tlxmi_sr_attention: K / V staged
                                   # once per workgroup, both products on MFMA, the scores in registers; off = tlxmi_mha, the general kernel
                                   # (the A/B and the tests' other arm)
+            "lka": True,          # VAN's large-kernel attention (fp16): the depthwise 5x5 -> dilated 7x7 chain as one launch (tlxmi_lka_dw, the
+                                  # intermediate map in LDS; planes of >= 196 pixels) and conv1 -> gate -> proj_2 -> layer scale + shortcut as one
+                                  # launch (tlxmi_lka_gate, both products on MFMA, the gated map in registers; C <= 64); elsewhere and off = two tlxmi_dwconv2d launches, and tlxmi_conv2d -> tlxmi_mul
+                                  # -> tlxmi_affine_act -> tlxmi_conv2d (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1163,6 +1167,138 @@ def preact_conv1x1(x, pre_scale, pre_shift, pk, scale=None, shift=None, act=ACT_
     e1.record()
     _probe.append((e0, e1, (M * K + M * pk.Cout + pk.Cout * K) * es, 2 * M * pk.Cout * K, (N, H, W, K, pk.Cout, "preact")))
     return out
+
+
+def mul(a, b, cols=None, out=None):
+    """Elementwise product (VAN's gate `x * attn`, van.py:100) on tlxmi_mul: a, b dense tensors of one dtype whose rows are their last
+    axis — the first `cols` columns of each row are multiplied (default: all of a's), so a and b may be pitched differently -> y with
+    `cols` columns, or written into `out` (any pitch >= cols)."""
+    need_gpu(a, "input")
+    need_gpu(b, "input")
+    Cc = a.shape[-1] if cols is None else int(cols)
+    rows = a.numel() // a.shape[-1]
+    if a.dtype != b.dtype or not a.is_contiguous() or not b.is_contiguous() or b.numel() // b.shape[-1] != rows or a.shape[-1] < Cc or b.shape[-1] < Cc:
+        raise RuntimeError(f"mul: two dense tensors of one dtype with the same rows and at least {Cc} columns are expected, got {tuple(a.shape)} {a.dtype} / {tuple(b.shape)} {b.dtype}")
+    if out is None:
+        out = torch.empty(tuple(a.shape[:-1]) + (Cc,), dtype=a.dtype, device=a.device)
+    elif out.dtype != a.dtype or not out.is_contiguous() or out.shape[-1] < Cc or out.numel() // out.shape[-1] != rows:
+        raise RuntimeError("mul: out must be a dense tensor of the operands' dtype and rows")
+    _lib.call("tlxmi_mul", _p(a), _p(b), _p(out), dt_code(a.dtype), rows, Cc, a.shape[-1], b.shape[-1], out.shape[-1], _stream())
+    return out
+
+
+def _lka_dw_desc(t, Cc, y_ld):
+    N, H, W, ld = t.shape
+    return _lib.LkaDwDesc(dtype=dt_code(t.dtype), N=N, H=H, W=W, C=Cc, x_ld=ld, y_ld=y_ld)
+
+
+# Shapes the fused kernels keep by default: those that measured faster than the old arm on one MI355X at batch 256 and 128 (tools/van_bench.py,
+# profiles/van/van_bench_b256.txt).  tlxmi_lka_dw won on planes of 56 x 56, 28 x 28 and 14 x 14 (0.66 - 0.94 of the two launches) and lost on
+# 7 x 7 (1.8 - 2.8 x: 49 of a workgroup's 128 pixel slots have work); nothing between 49 and 196 pixels was measured, so the smallest measured win
+# is the threshold.  tlxmi_lka_gate won at C = 32 and 64 (0.39 - 0.79 of the four launches), tied at 160 (1.04 at batch 256, 0.84 at 128) and lost
+# at 256 (2.2 - 2.8 x: every wave re-reads 256 KiB of filters); 96 and 128 were not measured, so 64 is the limit.
+LKA_DW_MIN_PIXELS = 196
+LKA_GATE_MAX_C = 64
+
+
+def lka_dw_supported(t, Cc=None):
+    """Whether lka_dw() runs tlxmi_lka_dw on this NHWC map by default: the "lka" option on, fp16, the library takes the shape, and the plane
+    has at least LKA_DW_MIN_PIXELS pixels (smaller planes measured slower than two tlxmi_dwconv2d launches)."""
+    Cc = t.shape[-1] if Cc is None else Cc
+    return bool(_options["lka"] and t.dtype == torch.float16 and t.is_contiguous() and t.shape[1] * t.shape[2] >= LKA_DW_MIN_PIXELS
+                and _lib.load().tlxmi_lka_dw_supported(C.byref(_lka_dw_desc(t, Cc, Cc))))
+
+
+def lka_dw(t, w0, b0, w1, b1, fused=None):
+    """LKA.conv0 -> LKA.conv_spatial (van.py:87-98): depthwise 5x5 (padding 2) then depthwise 7x7 at dilation 3 (padding 9), each + bias, the
+    map between them rounded to the activation dtype.  t (N, H, W, ld) NHWC with the first C = w0.shape[2] channels used; w0 [5][5][C],
+    w1 [7][7][C]; b0, b1 fp32 [C] or None -> y (N, H, W, C).  One launch (tlxmi_lka_dw, the map between the convs kept in LDS) when the
+    "lka" option is on, the precision is fp16, the library takes the shape and the plane has at least LKA_DW_MIN_PIXELS pixels; otherwise
+    two tlxmi_dwconv2d launches (fp32 always: the parity reference).  fused=True / False forces one form (tests, tools/)."""
+    need_gpu(t, "input")
+    N, H, W, ld = t.shape
+    Cc = w0.shape[2]
+    if tuple(w0.shape) != (5, 5, Cc) or tuple(w1.shape) != (7, 7, Cc) or w0.dtype != t.dtype or w1.dtype != t.dtype or ld < Cc or not t.is_contiguous():
+        raise RuntimeError(f"lka_dw: a dense NHWC map with at least C channels and [5][5][C] / [7][7][C] filters of its dtype are expected, got "
+                           f"{tuple(t.shape)} {t.dtype} / {tuple(w0.shape)} / {tuple(w1.shape)}")
+    if fused is None:
+        fused = lka_dw_supported(t, Cc)
+    es = t.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(t.numel() * es)
+    if _probe is not None:
+        e0, e1 = _probe_pair()
+    if fused:
+        y = torch.empty((N, H, W, Cc), dtype=t.dtype, device=t.device)
+        _lib.call("tlxmi_lka_dw", C.byref(_lka_dw_desc(t, Cc, Cc)), _p(t), _p(w0), _p(b0), _p(w1), _p(b1), _p(y), _stream())
+    else:
+        y = dwconv2d(dwconv2d(t, w0, 1, 2, 1, None, b0), w1, 1, 9, 3, None, b1)
+        if ld != Cc:
+            y = y[..., :Cc].contiguous()
+    if _probe is not None:
+        e1.record()
+        M = N * H * W
+        _probe.append((e0, e1, (2 * M * Cc + 74 * Cc) * es, 2 * 74 * M * Cc, (N, H, W, Cc, Cc, "lka_dw" if fused else "dwconv2d x2")))
+    return y
+
+
+def _lka_gate_desc(rows, Cc, dtype):
+    return _lib.LkaGateDesc(dtype=dt_code(dtype), rows=rows, C=Cc, a1_ld=Cc, t_ld=Cc, res_ld=Cc, y_ld=Cc)
+
+
+def lka_gate_supported(rows, Cc, dtype):
+    """Whether lka_gate() runs tlxmi_lka_gate on dense (rows, C) operands by default: the "lka" option on, fp16, the library takes the shape,
+    and C <= LKA_GATE_MAX_C (wider stages measured no faster than the four launches)."""
+    return bool(_options["lka"] and dtype == torch.float16 and Cc <= LKA_GATE_MAX_C
+                and _lib.load().tlxmi_lka_gate_supported(C.byref(_lka_gate_desc(rows, Cc, dtype))))
+
+
+def lka_gate(a1, t, pk1, scale1, shift1, pk2, scale2, shift2, res, res_scale, fused=None):
+    """LKA.conv1 -> the gate -> Attention.proj_2 -> layer scale and shortcut (van.py:99-100, :119-120, :146):
+        a2 = conv1x1(a1; pk1) * scale1 + shift1;   g = t * a2 (rounded to the activation dtype);
+        y  = res * res_scale + conv1x1(g; pk2) * scale2 + shift2
+    a1, t, res: dense (N, H, W, C) or (rows, C) of one dtype; pk1, pk2: PackedFilter of [C][C] 1x1 filters; the scales / shifts fp32 [C]
+    or None (1 / 0) -> y of a1's shape.  One launch (tlxmi_lka_gate: both products on MFMA, g never in memory) when the "lka" option
+    is on, the precision is fp16, the library takes the shape (C a multiple of 32 up to 256) and C <= LKA_GATE_MAX_C; otherwise
+    tlxmi_conv2d -> tlxmi_mul -> tlxmi_affine_act -> tlxmi_conv2d (fp32 always: the parity reference).  fused=True / False forces one form (tests, tools/)."""
+    global _probe
+    need_gpu(a1, "input")
+    Cc = a1.shape[-1]
+    rows = a1.numel() // Cc
+    for o in (t, res):
+        if o.shape != a1.shape or o.dtype != a1.dtype or not o.is_contiguous():
+            raise RuntimeError(f"lka_gate: a1, t and res must be dense tensors of one shape and dtype, got {tuple(a1.shape)} {a1.dtype} / {tuple(o.shape)} {o.dtype}")
+    if not a1.is_contiguous() or any(pk.R != 1 or pk.S != 1 or pk.Cin != Cc or pk.Cout != Cc or pk.dtype != a1.dtype for pk in (pk1, pk2)):
+        raise RuntimeError(f"lka_gate: dense operands and two packed {Cc} x {Cc} 1x1 filters of their dtype are expected")
+    if fused is None:
+        fused = lka_gate_supported(rows, Cc, a1.dtype)
+    es = a1.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(a1.numel() * es)
+
+    def launch():
+        if fused:
+            y = torch.empty_like(a1)
+            _lib.call("tlxmi_lka_gate", C.byref(_lka_gate_desc(rows, Cc, a1.dtype)), _p(a1), _p(t), _p(pk1.buf), _p(scale1), _p(shift1),
+                      _p(pk2.buf), _p(scale2), _p(shift2), _p(res), _p(res_scale), _p(y), _stream())
+            return y
+        v4 = (lambda v: v) if a1.dim() == 4 else (lambda v: v.view(rows, 1, 1, Cc))
+        a2 = conv2d(v4(a1), pk1, 1, 0, 1, scale1, shift1)
+        g = mul(v4(t), a2)
+        r = affine_act(v4(res), res_scale) if res_scale is not None else v4(res)
+        return conv2d(g, pk2, 1, 0, 1, scale2, shift2, res=r).view(a1.shape)
+    if _probe is None:
+        return launch()
+    probe, _probe = _probe, None      # the chain is one entry
+    try:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        y = launch()
+        e1.record()
+    finally:
+        _probe = probe
+    probe.append((e0, e1, (4 * rows * Cc + 2 * Cc * Cc) * es, 4 * rows * Cc * Cc, (rows, 1, 1, Cc, Cc, "lka_gate" if fused else "conv-mul-affine-conv")))
+    return y
 
 
 # ---------------------------------------------------------------------------------------------

@@ -21,3 +21,5 @@ from .densenet import (DenseNet, densenet121, densenet161, densenet169, densenet
                        DenseBlock, TransitionLayer, ConvBNLayer)
 # (the PVTv2 file's Mlp / Attention / Block / DWConv stay in their module: ConvNeXt's Block and DropPath own those names here)
 from .pvt_v2 import PyramidVisionTransformerV2, pvt_v2, OverlapPatchEmbed  # noqa: F401
+# (the VAN file's Mlp / LKA / Attention / Block / OverlapPatchEmbed / DWConv stay in their module, like PVTv2's)
+from .van import VAN, VAN_B0, van  # noqa: F401

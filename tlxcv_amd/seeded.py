@@ -51,6 +51,7 @@ def fill(shapes, seed):
       pos_embed / cls_token / relative_position_bias_table   N(0, 0.02) clipped at 2 sigma
       *_weight (attention projections, out x in)   N(0, sqrt(1/fan_in));   *_bias   N(0, 0.02)
       *.weight (1-D) / *.bias    the channels-first LayerNorm of ConvNeXt: as gamma / beta
+      layer_scale_*              U(0.05, 0.15)                                   (VAN: van.py:139-143)
     """
     rng = np.random.default_rng(seed)
     out = {}
@@ -82,6 +83,8 @@ def fill(shapes, seed):
             a = rng.uniform(0.8, 1.2, shape).astype(np.float32)
         elif leaf == "bias":                                    # ... as beta
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(0.05)
+        elif leaf.startswith("layer_scale_"):                   # VAN's [dim, 1, 1] layer scales (van.py:139-143): large enough to matter, small enough that 13 gated blocks stay far inside fp16
+            a = rng.uniform(0.05, 0.15, shape).astype(np.float32)
         else:
             raise KeyError(f"seeded.fill: no rule for parameter {name!r}")
         out[name] = np.ascontiguousarray(a, dtype=np.float32)
