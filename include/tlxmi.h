@@ -630,6 +630,43 @@ int tlxmi_sr_attention_supported(const tlxmi_mha_desc* d);
 int tlxmi_sr_attention(const tlxmi_mha_desc* d, const void* q, const void* k, const void* v, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cross-shaped window attention with LePE — the attention of CSWin (classification/cswin_transformer.py:151-222, :285-300) in one launch
+ * per block.  A stage is a row matrix, token (y, x) of an H x W image = row y*W + x.  The heads are split over `branches` (1 or 2);
+ * branch b cuts the image into stripes of hs[b] x ws[b] tokens and each of its `heads` heads attends inside every stripe.  Column
+ * (branch*heads + h)*hd + d of a q / k / v / out row belongs to head h of that branch, so q, k, v are three pointers into the packed
+ * [B][H*W][3][C] output of the qkv Linear (row stride 3*C, C = branches*heads*hd) and out is the [B][H*W][C] matrix `proj` reads.
+ *   out[i] = sum_j softmax_j( scale * q_i . k_j ) v_j  +  sum_{r,s<3} w_lepe[r][s][c] * v[(y_i+r-1, x_i+s-1)] + b_lepe[c]
+ * j over the tokens of i's stripe; a tap outside the STRIPE (not merely the image) contributes zero.  w_lepe is [3][3][C] in the data
+ * dtype (tlxmi_dwconv2d's [R][S][C] with both branches' channels side by side), b_lepe fp32 [C] or NULL.  The two terms are summed in
+ * fp32 and rounded once; one writer per output element, a fixed summation order, no atomics.  Rows of another image, rows behind the
+ * last token and columns outside the heads' columns are never read; nothing outside the C output columns is written.
+ *   tlxmi_cswin_attention            fp16, hd 32, stripes of <= 128 tokens: K / V of a (stripe, head) staged once in LDS, both products on
+ *                                    MFMA, the softmax one pass in registers, LePE from the V tile in LDS in the epilogue.
+ *   tlxmi_cswin_attention_supported  pure host code; 1 exactly for: fp16; hd 32; branches 1 or 2; B, heads >= 1; for each used branch
+ *                                    hs | H, ws | W and 1 <= hs*ws <= 128; every stride a non-negative multiple of 8 elements; each
+ *                                    tensor's byte extent ((B-1)*batch stride + (H*W-1)*row stride + C) * 2 below 2^31; output rows that
+ *                                    do not overlap.  1 means the call is taken, given 16-byte aligned pointers; everything else returns
+ *                                    TLXMI_ERR_UNSUPPORTED.
+ *   tlxmi_cswin_attention_plain      same arguments; fp16 or fp32, hd <= 128, any stripe length and any non-negative strides, fp32
+ *                                    arithmetic, no MFMA: the fp32 parity path and the arm of what the hot path does not take.  Not tuned.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_cswin_attention_desc {
+    int32_t dtype;
+    int32_t B, H, W, hd;
+    float scale;
+    int32_t branches;           /* 1 or 2 */
+    int32_t heads;              /* per branch */
+    int32_t hs[2], ws[2];       /* stripe height / width of each branch */
+    int64_t q_batch_stride, q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride,
+            out_batch_stride, out_row_stride;       /* in elements */
+} tlxmi_cswin_attention_desc;
+int tlxmi_cswin_attention_supported(const tlxmi_cswin_attention_desc* d);
+int tlxmi_cswin_attention(const tlxmi_cswin_attention_desc* d, const void* q, const void* k, const void* v, const void* w_lepe,
+                          const float* b_lepe, void* out, void* stream);
+int tlxmi_cswin_attention_plain(const tlxmi_cswin_attention_desc* d, const void* q, const void* k, const void* v, const void* w_lepe,
+                                const float* b_lepe, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Swin window plumbing folded into index math (swin_transformer.py:85-116, 317-333):
  *   partition: x[B][H][W][C] --roll(-shift)--> windows [B*nW][ws*ws][C]
  *   reverse:   windows --> x (+roll(+shift)), optionally y = res + reverse(windows)

@@ -64,6 +64,13 @@ class MhaDesc(C.Structure):
             "out_batch_stride", "out_row_stride")]
 
 
+class CswinAttnDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "B", "H", "W", "hd")] + [("scale", C.c_float)] + [
+        (n, C.c_int32) for n in ("branches", "heads")] + [("hs", C.c_int32 * 2), ("ws", C.c_int32 * 2)] + [(n, C.c_int64) for n in (
+            "q_batch_stride", "q_row_stride", "k_batch_stride", "k_row_stride", "v_batch_stride", "v_row_stride",
+            "out_batch_stride", "out_row_stride")]
+
+
 class SeamDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in (
         "K1", "N1", "N2", "t2_ld", "skip_ld", "y_ld", "t1_ld", "act")]
@@ -120,6 +127,8 @@ PROTOTYPES = {
     "tlxmi_attention_windows": [C.POINTER(AttnDesc), _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "tlxmi_mha": [C.POINTER(MhaDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_sr_attention": [C.POINTER(MhaDesc), _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_cswin_attention": [C.POINTER(CswinAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_cswin_attention_plain": [C.POINTER(CswinAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_window_partition": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_window_reverse": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_patch_merge_gather": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -154,6 +163,7 @@ _SPECIAL = {
     "tlxmi_dwconv7_stats_supported": ([C.POINTER(DwConv7Desc)], C.c_int),
     "tlxmi_preact_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i], C.c_int),
     "tlxmi_sr_attention_supported": ([C.POINTER(MhaDesc)], C.c_int),
+    "tlxmi_cswin_attention_supported": ([C.POINTER(CswinAttnDesc)], C.c_int),
     "tlxmi_lka_dw_supported": ([C.POINTER(LkaDwDesc)], C.c_int),
     "tlxmi_lka_gate_supported": ([C.POINTER(LkaGateDesc)], C.c_int),
 }

@@ -53,6 +53,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # intermediate map in LDS; planes of >= 196 pixels) and conv1 -> gate -> proj_2 -> layer scale + shortcut as one
                                   # launch (tlxmi_lka_gate, both products on MFMA, the gated map in registers; C <= 64); elsewhere and off = two tlxmi_dwconv2d launches, and tlxmi_conv2d -> tlxmi_mul
                                   # -> tlxmi_affine_act -> tlxmi_conv2d (the A/B and the tests' other arm)
+            "cswin_attn": True,   # CSWin's cross-shaped window attention + LePE (fp16, head dim 32, stripes of at most 128 tokens) on
+                                  # tlxmi_cswin_attention: K / V of a (stripe, head) staged once in LDS, both products on MFMA, the scores in
+                                  # registers, LePE from the V tile in the epilogue; off = tlxmi_cswin_attention_plain (the A/B and the tests'
+                                  # other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1599,6 +1603,70 @@ def sr_attention(q, kv, heads, scale, fused=None):
         e1.record()
         _probe.append((e0, e1, (2 * B * Lq * Cc + 2 * B * Lk * Cc) * es, 4 * B * Lq * Lk * Cc,
                        (B, Lq, Lk, heads, Cc // heads, "sr_attn" if fused else "mha")))
+    return out
+
+
+def cswin_stripes(H, W, splits):
+    """The stripe (height, width) of each branch: `splits` = one (hs, ws) pair per branch, or an int s for CSWin's pair of a vertical
+    (H, s) and a horizontal (s, W) stripe (cswin_transformer.py:263-273)."""
+    if isinstance(splits, int):
+        return [(H, splits), (splits, W)]
+    return [(int(a), int(b)) for a, b in splits]
+
+
+def _cswin_desc(dtype, B, H, W, heads, hd, stripes, scale, q, k, v, out):
+    hs = (C.c_int32 * 2)(*([s[0] for s in stripes] + [0])[:2])
+    ws = (C.c_int32 * 2)(*([s[1] for s in stripes] + [0])[:2])
+    return _lib.CswinAttnDesc(dtype=dt_code(dtype), B=B, H=H, W=W, hd=hd, scale=float(scale), branches=len(stripes), heads=heads // len(stripes),
+                              hs=hs, ws=ws, q_batch_stride=q.stride(0), q_row_stride=q.stride(1), k_batch_stride=k.stride(0),
+                              k_row_stride=k.stride(1), v_batch_stride=v.stride(0), v_row_stride=v.stride(1),
+                              out_batch_stride=out.stride(0), out_row_stride=out.stride(1))
+
+
+def cswin_attention(qkv, B, H, W, heads, splits, w_lepe, b_lepe, scale, fused=None):
+    """CSWin's attention of one block (cswin_transformer.py:151-222, :285-300): qkv (B, H*W, 3C) packed [3][heads][hd] as the `qkv`
+    Linear leaves it, token (y, x) = row y*W + x -> (B, H*W, C).  `heads` heads in all, split evenly over the branches of `splits`
+    (cswin_stripes: an int s = the (H, s) and (s, W) stripes; a list of (hs, ws) pairs, one per branch); each head attends inside the
+    stripes of its branch and adds LePE, the depthwise 3x3 of V inside the stripe: w_lepe [3][3][C] in qkv's dtype (both branches'
+    channels side by side), b_lepe fp32 [C] or None.  q, k, v are three pointers into qkv (row stride 3C), read in place.
+    tlxmi_cswin_attention (MFMA, the scores in registers) when the "cswin_attn" option is on, the precision is fp16, the library takes
+    the shape (hd 32, stripes of at most 128 tokens) and the pointers are 16-byte aligned; otherwise tlxmi_cswin_attention_plain (fp32
+    always: the parity reference).  fused=True / False forces one form (tests, tools/); a forced unsupported call raises."""
+    need_gpu(qkv, "qkv")
+    stripes = cswin_stripes(H, W, splits)
+    nb = len(stripes)
+    if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[1] != H * W or qkv.shape[2] % (3 * heads) or nb not in (1, 2) or heads % nb:
+        raise RuntimeError(f"cswin_attention: qkv (B, H*W, 3C) = ({B}, {H * W}, 3C) with C a multiple of heads = {heads} and 1 or 2 branches "
+                           f"that split the heads evenly are expected, got {tuple(qkv.shape)} and {nb} branches")
+    if qkv.stride(-1) != 1:
+        raise RuntimeError("cswin_attention: the feature axis must be dense")
+    Cc = qkv.shape[2] // 3
+    if tuple(w_lepe.shape) != (3, 3, Cc) or w_lepe.dtype != qkv.dtype or not w_lepe.is_contiguous():
+        raise RuntimeError(f"cswin_attention: a dense [3][3][{Cc}] LePE filter of qkv's dtype is expected, got {tuple(w_lepe.shape)} {w_lepe.dtype}")
+    if b_lepe is not None and (tuple(b_lepe.shape) != (Cc,) or b_lepe.dtype != torch.float32 or not b_lepe.is_contiguous()):
+        raise RuntimeError(f"cswin_attention: the LePE bias is fp32 [{Cc}]")
+    for hs, ws in stripes:
+        if hs < 1 or ws < 1 or H % hs or W % ws:
+            raise RuntimeError(f"cswin_attention: a {hs} x {ws} stripe does not divide the {H} x {W} image")
+    q, k, v = qkv[..., :Cc], qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:]
+    out = torch.empty((B, H * W, Cc), dtype=qkv.dtype, device=qkv.device)
+    es = qkv.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(out.numel() * es, qkv.numel() * es)
+    hd = Cc // heads
+    d = _cswin_desc(qkv.dtype, B, H, W, heads, hd, stripes, scale, q, k, v, out)
+    if fused is None:
+        fused = bool(_options["cswin_attn"] and qkv.dtype == torch.float16 and _lib.load().tlxmi_cswin_attention_supported(C.byref(d))
+                     and all(t.data_ptr() % 16 == 0 for t in (q, k, v, out, w_lepe) + ((b_lepe,) if b_lepe is not None else ())))
+    if _probe is not None:
+        e0, e1 = _probe_pair()
+    _lib.call("tlxmi_cswin_attention" if fused else "tlxmi_cswin_attention_plain", C.byref(d), _p(q), _p(k), _p(v), _p(w_lepe), _p(b_lepe),
+              _p(out), _stream())
+    if _probe is not None:
+        e1.record()
+        keys = sum(hs * ws for hs, ws in stripes) / nb                  # keys a query meets, averaged over the branches
+        _probe.append((e0, e1, 4 * B * H * W * Cc * es + w_lepe.numel() * es, int(4 * B * H * W * keys * Cc) + 18 * B * H * W * Cc,
+                       (B, H, W, heads, hd, tuple(stripes), "cswin_attn" if fused else "cswin_plain")))
     return out
 
 

@@ -23,3 +23,6 @@ from .densenet import (DenseNet, densenet121, densenet161, densenet169, densenet
 from .pvt_v2 import PyramidVisionTransformerV2, pvt_v2, OverlapPatchEmbed  # noqa: F401
 # (the VAN file's Mlp / LKA / Attention / Block / OverlapPatchEmbed / DWConv stay in their module, like PVTv2's)
 from .van import VAN, VAN_B0, van  # noqa: F401
+# (the CSWin file's Mlp stays in its module)
+from .cswin_transformer import (CSwinTransformer, CSwintransformer_thiny, PatchEmbedding, LePEAttention, CSwinBlock, MergeBlock,  # noqa: F401
+                                CSwinStage)
