@@ -268,6 +268,41 @@ int tlxmi_bottleneck_seam(const tlxmi_seam_desc* d, const void* t2, const void* 
                           const float* shift1, void* t1, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Expand conv of a ResNet transition block with its 1x1 projection shortcut as extra K (resnet.py:142-156 with the downsample of
+ * :246-261), one launch, fp16:
+ *     y[m][n] = act( sum_{k < K1} x[m][k] * W'[n][k]  +  sum_{k < K2} x2[pix(m)][k] * W'[n][K1 + k]  +  shift[n] )
+ * for output row m = (img, ho, wo) of an N x Ho x Wo map, pix(m) = pixel (ho * stride, wo * stride) of image img in the
+ * N x H2 x W2 map x2 (no padding; Ho = (H2 - 1) / stride + 1, Wo likewise).  fp32 accumulation, ONE rounding on store: the shortcut
+ * map is neither written nor read.  The caller folds both BatchNorm scales into the filter, W' = [diag(s3) W3 | diag(sd) Wd] as one
+ * [Cout][K1 + K2][1][1] filter through tlxmi_pack_filter, and passes shift = h3 + hd (fp32 [Cout], or NULL for 0).
+ * x: rows of pitch x_ld (K1 columns read), x2: pixels of pitch x2_ld (K2 columns read), y: rows of pitch y_ld (Cout columns
+ * written, nothing else).  d->flags: TLXMI_PLAN_SHARED_* planning hints only.
+ * tlxmi_conv1x1_proj_supported() is pure host code (no HIP call) and answers 1 exactly when the call is taken:
+ *   - d->dtype == TLXMI_F16; N, Ho, Wo, H2, W2 positive with Ho / Wo as above; stride 1 or 2; act a valid tlxmi_act;
+ *   - K1 and K2 positive multiples of 64 (a 128-byte K tile never straddles the two sources), Cout a positive multiple of 8;
+ *   - x_ld >= K1, x2_ld >= K2, y_ld >= Cout, all multiples of 8; x, x2, w_packed, y non-null and 16-byte aligned;
+ *   - rows * x_ld * 2, N * H2 * W2 * x2_ld * 2, rows * y_ld * 2 and ceil(Cout / 256) * 256 * (K1 + K2) * 2 all below 2^31
+ *     (32-bit buffer offsets), rows = N * Ho * Wo;
+ *   - the bytes of y do not overlap those of x or x2.
+ * tlxmi_conv1x1_proj() checks the same before any HIP call: null pointers, non-positive or inconsistent extents and a bad act
+ * return TLXMI_ERR_BAD_ARG, a misaligned pointer or pitch TLXMI_ERR_ALIGNMENT, every other limit TLXMI_ERR_UNSUPPORTED (run the
+ * shortcut as tlxmi_conv2d and hand it to the expand conv as its residual instead).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_proj_desc {
+    int32_t dtype;
+    int32_t N, Ho, Wo;            /* output map; rows = N * Ho * Wo */
+    int32_t K1, K2, Cout;
+    int32_t H2, W2, stride;       /* extent of x2 and the stride it is read at */
+    int32_t x_ld, x2_ld, y_ld;    /* elements between rows / pixels */
+    int32_t act;
+    float act_param;
+    uint32_t flags;
+} tlxmi_proj_desc;
+int tlxmi_conv1x1_proj_supported(const tlxmi_proj_desc* d, const void* x, const void* x2, const void* w_packed, const void* y);
+int tlxmi_conv1x1_proj(const tlxmi_proj_desc* d, const void* x, const void* x2, const void* w_packed, const float* shift, void* y,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Grouped convolution, 1 < groups < C: nn.GroupConv2d(n_group=cardinality) of the ResNeXt bottleneck,
  * resnext.py:30-40 (constructed at :83-91 with groups = 32 / 64), + BatchNorm(act='relu') :46-52.
  * d->C / d->Cout are the TOTAL input / output channels (both divisible by groups), x_ld / y_ld the pixel

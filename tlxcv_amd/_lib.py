@@ -76,6 +76,11 @@ class SeamDesc(C.Structure):
         "K1", "N1", "N2", "t2_ld", "skip_ld", "y_ld", "t1_ld", "act")]
 
 
+class ProjDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "Ho", "Wo", "K1", "K2", "Cout", "H2", "W2", "stride", "x_ld", "x2_ld", "y_ld", "act")] + [
+        ("act_param", C.c_float), ("flags", C.c_uint32)]
+
+
 class PreprocDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "H", "W", "C", "out_h", "out_w", "kh", "kw", "out_dtype", "layout", "fold_b",
                                          "cpad", "normalize")]
@@ -97,6 +102,7 @@ PROTOTYPES = {
     "tlxmi_conv2d_splitk": [C.POINTER(ConvDesc), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_bottleneck_seam": [C.POINTER(SeamDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_bottleneck_seam_proj": [C.POINTER(SeamDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_conv1x1_proj": [C.POINTER(ProjDesc), _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_preprocess_u8": [C.POINTER(PreprocDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_preprocess_linear_u8": [C.POINTER(PreprocDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_yolo_iou_aware": [_vp, _vp, _i, _l, _i, _i, _f, _vp],
@@ -157,6 +163,7 @@ _SPECIAL = {
     "tlxmi_preprocess_u8_workspace_bytes": ([C.POINTER(PreprocDesc)], C.c_size_t),
     "tlxmi_multiclass_nms_workspace_bytes": ([_i, _i], C.c_size_t),
     "tlxmi_bottleneck_seam_supported": ([_i, _i, _i, _i], C.c_int),
+    "tlxmi_conv1x1_proj_supported": ([C.POINTER(ProjDesc), _vp, _vp, _vp, _vp], C.c_int),
     "tlxmi_linear_ln_supported": ([_i, _l, _i, _i, _i, _i], C.c_int),
     "tlxmi_mlp_seam_supported": ([_i, _i, _i, _i], C.c_int),
     "tlxmi_sepconv2d_supported": ([C.POINTER(SepConvDesc)], C.c_int),

@@ -588,6 +588,9 @@ static bool pp_conv_offsets_ok(int W, int R, int S, int ph, int pw, int dh, int 
     return lead < (1ll << 30) && reach < (1ll << 30);
 }
 
+// shape efficiency of gemm_pp.hip's 256 x 256 and 128 x 256 tiles in the tile prices (dispatch<T>'s candidates 7 and 9, tlxmi_conv1x1_proj)
+constexpr float kEffPP256 = 1.40f, kEffPP128 = 1.25f;
+
 template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, bool allow_stream = true, bool allow_split = true) {
     // Tile choice = max over the four shapes of (grid quantisation efficiency) x (shape efficiency):
     // a launch of B blocks on S = CUs x resident-blocks-per-CU slots runs ceil(B/S) rounds, so B/(rounds*S)
@@ -668,7 +671,7 @@ template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, boo
     // candidate 11 = gemm_w4.hip: 256 x 256 persistent, four waves with 128 x 128 wave tiles (pure GEMM rows)
     constexpr int NC = 12;
     Cand cands[NC] = {{128, 128, 1.00f}, {64, 128, 0.85f}, {128, 64, 0.85f}, {64, 64, 0.70f}, {256, 128, 0.90f},
-                      {256, 256, 1.12f}, {256, 128, 1.20f}, {256, 256, 1.40f}, {256, 256, 1.50f}, {128, 256, 1.25f},
+                      {256, 256, 1.12f}, {256, 128, 1.20f}, {256, 256, kEffPP256}, {256, 256, 1.50f}, {128, 256, kEffPP128},
                       {256, 128, 1.25f}, {256, 256, 0.f}};
     const bool gemm128_ok = a.nchunk == 1 && a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && a.sh == 1 && a.sw == 1 && !a.strided_n &&
                             a.vec_io && a.Cout % 8 == 0 && a.y_bytes != 0 && a.Cout >= 128 && a.ktiles >= 2 &&
@@ -1371,6 +1374,84 @@ extern "C" int tlxmi_linear_splitk(int dtype, int64_t rows, int K, int Cout, int
         hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3(grid), dim3(256), 0, as_stream(stream), (const float*)partials, splits, (long)rows, Cout,
                            (long)pstride, scale, shift, (const float*)res, res_ld, act, act_param, flags, (float*)y, y_ld);
     return check_launch("linear_splitk");
+}
+
+// ------------------------------------------------------------------------------------------
+// Expand conv of a ResNet transition block with the projection shortcut as extra K (include/tlxmi.h, tlxmi_conv1x1_proj): the
+// antiphase GEMM kernel's DUAL instances (gemm_pp.hip) — K tiles of the block's conv2 output, then K tiles gathered from the
+// block's input at the shortcut's stride, against one filter [diag(s3) W3 | diag(sd) Wd].
+// ------------------------------------------------------------------------------------------
+namespace tlxmi {
+// TLXMI_OK when the call is taken, else the status the call returns; `why` names the first limit missed.  Pure host arithmetic.
+static int proj_check(const tlxmi_proj_desc* d, const void* x, const void* x2, const void* w, const void* y, const char** why) {
+    *why = "null descriptor or buffer";
+    if (!d || !x || !x2 || !w || !y) return TLXMI_ERR_BAD_ARG;
+    *why = "non-positive extent";
+    if (d->N <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->H2 <= 0 || d->W2 <= 0 || d->K1 <= 0 || d->K2 <= 0 || d->Cout <= 0 || d->stride <= 0) return TLXMI_ERR_BAD_ARG;
+    *why = "pitch below the channel count";
+    if (d->x_ld < d->K1 || d->x2_ld < d->K2 || d->y_ld < d->Cout) return TLXMI_ERR_BAD_ARG;
+    *why = "bad dtype or activation";
+    if ((d->dtype != TLXMI_F16 && d->dtype != TLXMI_F32) || d->act < TLXMI_ACT_NONE || d->act > TLXMI_ACT_SILU) return TLXMI_ERR_BAD_ARG;
+    *why = "Ho / Wo are not (H2 - 1) / stride + 1, (W2 - 1) / stride + 1";
+    if (d->Ho != (d->H2 - 1) / d->stride + 1 || d->Wo != (d->W2 - 1) / d->stride + 1) return TLXMI_ERR_BAD_ARG;
+    *why = "pointers and pitches must be multiples of 16 bytes";
+    if (!aligned16(x) || !aligned16(x2) || !aligned16(w) || !aligned16(y) || d->x_ld % 8 || d->x2_ld % 8 || d->y_ld % 8) return TLXMI_ERR_ALIGNMENT;
+    *why = "fp16, stride 1 or 2, K1 and K2 multiples of 64, Cout a multiple of 8";
+    if (d->dtype != TLXMI_F16 || d->stride > 2 || d->K1 % 64 || d->K2 % 64 || d->Cout % 8) return TLXMI_ERR_UNSUPPORTED;
+    const long long big = 1ll << 31;
+    const long long rows = (long long)d->N * d->Ho * d->Wo, pix2 = (long long)d->N * d->H2 * d->W2;
+    const long long xb = rows * d->x_ld * 2, x2b = pix2 * d->x2_ld * 2, yb = rows * d->y_ld * 2;
+    const long long wb = ((long long)d->Cout + 255) / 256 * 256 * ((long long)d->K1 + d->K2) * 2;
+    *why = "a tensor of 2 GiB or more (32-bit buffer offsets)";
+    if (xb >= big || x2b >= big || yb >= big || wb >= big) return TLXMI_ERR_UNSUPPORTED;
+    *why = "y overlaps x or x2";
+    const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (uintptr_t)yb;
+    if ((y0 < (uintptr_t)x + (uintptr_t)xb && (uintptr_t)x < y1) || (y0 < (uintptr_t)x2 + (uintptr_t)x2b && (uintptr_t)x2 < y1)) return TLXMI_ERR_UNSUPPORTED;
+    *why = "";
+    return TLXMI_OK;
+}
+}  // namespace tlxmi
+
+extern "C" int tlxmi_conv1x1_proj_supported(const tlxmi_proj_desc* d, const void* x, const void* x2, const void* w_packed, const void* y) {
+    const char* why;
+    return tlxmi::proj_check(d, x, x2, w_packed, y, &why) == TLXMI_OK ? 1 : 0;
+}
+
+extern "C" int tlxmi_conv1x1_proj(const tlxmi_proj_desc* d, const void* x, const void* x2, const void* w_packed, const float* shift, void* y,
+                                  void* stream) {
+    using namespace tlxmi;
+    const char* why;
+    if (const int rc = proj_check(d, x, x2, w_packed, y, &why)) return fail(rc, "conv1x1_proj: %s", why);
+    const long long rows = (long long)d->N * d->Ho * d->Wo;
+    Gemm256Args g;
+    g.debug = 0; g.conv = 0;
+    g.x = (const char*)x; g.w = (const char*)w_packed; g.y = (char*)y; g.scale = nullptr; g.shift = shift; g.res = nullptr;
+    g.M = (int)rows; g.Cout = d->Cout; g.x_ld = d->x_ld; g.y_ld = d->y_ld; g.res_ld = 0;
+    g.k1_tiles = d->K1 / 64; g.k2_tiles = d->K2 / 64;
+    g.ksteps = g.k1_tiles + g.k2_tiles; g.kchunks = g.ksteps * 8; g.Kp_bytes = g.ksteps * 128;
+    g.act = d->act; g.act_param = d->act_param; g.flags = d->flags & (TLXMI_PLAN_SHARED_HALF | TLXMI_PLAN_SHARED_FULL);
+    g.mtiles = g.ntiles = 0; g.gn = 1;
+    g.x_bytes = (unsigned)(rows * d->x_ld * 2);
+    g.y_bytes = (unsigned)(((rows - 1) * d->y_ld + d->Cout) * 2);
+    g.res_bytes = 0;
+    g.w_bytes = (unsigned)(((size_t)(d->Cout + 127) / 128 * 128) * (size_t)g.Kp_bytes);
+    g.x2 = (const char*)x2; g.x2_ld = d->x2_ld;
+    g.x2_bytes = (unsigned)((long long)d->N * d->H2 * d->W2 * d->x2_ld * 2);
+    g.dH2 = d->H2; g.dW2 = d->W2; g.dWo = d->Wo; g.dHoWo = d->Ho * d->Wo; g.ds = d->stride;
+    // Tile height by the dispatcher's price (dispatch<T>, candidates 7 and 9): rounds of one workgroup per CU on the CUs this launch is
+    // planned for, times the fill of the last row tile, times the shape efficiency (kEffPP256 / kEffPP128, the dispatcher's own)
+    const int cus = (d->flags & TLXMI_PLAN_SHARED_HALF) ? (num_cus() / 2 > 0 ? num_cus() / 2 : 1) : num_cus();
+    const long nt = (d->Cout + 255) / 256;
+    auto price = [&](int bm, float eff) {
+        const long mt = (long)((rows + bm - 1) / bm), blocks = mt * nt, rounds = (blocks + cus - 1) / cus;
+        return (float)blocks / (float)(rounds * cus) * ((float)rows / (float)(mt * bm)) * eff;
+    };
+    // TLXMI_PROJ_TILE (tuning flavour): 1 = 256 x 256 tiles, 2 = 128 x 256 (the tests run either form at sizes the price would not pick it)
+    const long forced = tune_int("TLXMI_PROJ_TILE", 0);
+    const bool half_height = forced == 1 ? false : forced == 2 ? true : price(128, kEffPP128) > price(256, kEffPP256);
+    trace_launched(half_height ? "pp_dual128" : "pp_dual256", g.M, g.Cout);
+    if (int rc = launch_gemm_pp_dual(g, half_height, as_stream(stream))) return rc;
+    return check_launch("conv1x1_proj");
 }
 
 // ------------------------------------------------------------------------------------------

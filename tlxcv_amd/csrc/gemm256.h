@@ -47,6 +47,13 @@ struct Gemm256Args {
     // gemm_pp.hip CONV mode — dilation: tap (r, s) reads input pixel (hi0 + r * cdh, wi0 + s * cdw).  Read only by the dilated
     // instances (launch_gemm_pp* pick them when cdh | cdw != 1); kept last so the other fields keep their kernel-argument offsets.
     int cdh = 1, cdw = 1;
+    // gemm_pp.hip DUAL instances (launch_gemm_pp_dual) — a second A operand: K tiles [k1_tiles, k1_tiles + k2_tiles) are rows of x2, an
+    // NHWC map of dH2 x dW2 pixels (pitch x2_ld, x2_bytes in all) read at pixel (ho * ds, wo * ds) for output row (n, ho, wo) of a
+    // dHoWo = Ho * dWo pixel output image.  Read by those instances only; last, so the fields above keep their kernel-argument offsets.
+    const char* x2 = nullptr;
+    unsigned x2_bytes = 0;
+    int x2_ld = 0, k1_tiles = 0, k2_tiles = 0;
+    int dH2 = 1, dW2 = 1, dWo = 1, dHoWo = 1, ds = 1;
 };
 
 int launch_gemm256(int dtype, int variant, const Gemm256Args& a, hipStream_t st);
@@ -54,6 +61,7 @@ int launch_gemm256(int dtype, int variant, const Gemm256Args& a, hipStream_t st)
 int launch_gemm_pp(int dtype, const Gemm256Args& a, hipStream_t st);
 int launch_gemm_pp128(int dtype, const Gemm256Args& a, hipStream_t st);   // 128 x 256 tiles (tails)
 int launch_gemm_pp_n128(int dtype, const Gemm256Args& a, hipStream_t st); // 256 x 128 tiles (128 output channels)
+int launch_gemm_pp_dual(const Gemm256Args& a, bool half_height, hipStream_t st);   // fp16, two A operands (a.x2); 256 x 256 or 128 x 256 tiles
 // gemm_stream.hip: persistent version (one workgroup per CU walks its tiles as one K-tile stream)
 bool gemm_stream_ok(int dtype, const Gemm256Args& a);
 int launch_gemm_stream(int dtype, const Gemm256Args& a, hipStream_t st, int cus);

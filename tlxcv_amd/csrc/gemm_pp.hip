@@ -77,9 +77,15 @@ template <> struct MmaPP<float> {
 // wc waves of a row are added through LDS).  Used where the persistent kernel does not apply: a residual with fewer than 11 K tiles
 // (Swin-B stage 3 proj: K = 512), fewer tiles than half the CUs.
 // DIL (CONV only): the dilated instances read a.cdh / a.cdw; the undilated ones keep the dilation-1 arithmetic (and ISA).
-template <typename T, int HM, int HN, bool CONV, bool LNF = false, bool DIL = false>
+// DUAL (fp16, plain GEMM rows, no split K, no LNF): a second A operand.  K tiles [0, a.k1_tiles) are rows of x as above; K tiles
+// [a.k1_tiles, a.k1_tiles + a.k2_tiles) are rows of a.x2, an NHWC map of a.dH2 x a.dW2 pixels of pitch a.x2_ld read at pixel
+// (ho * a.ds, wo * a.ds) of image n for output row m = (n, ho, wo) — the 1x1 projection shortcut of a ResNet transition block
+// (resnet.py:246-261) as extra K of the block's expand conv.  Both K extents are whole K tiles, so the source of a K tile is
+// wave-uniform: one scalar compare per stage_x picks the descriptor and the row offsets.  Every other instance ignores the fields.
+template <typename T, int HM, int HN, bool CONV, bool LNF = false, bool DIL = false, bool DUAL = false>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
     static_assert(HM + HN >= 3 && HM <= 2 && HN <= 2, "tile is 256x256, 128x256 or 256x128");
+    static_assert(!DUAL || (!CONV && !LNF && !DIL && sizeof(T) == 2), "DUAL: fp16 GEMM rows plus one gathered operand");
     constexpr int ES = (int)sizeof(T);
     constexpr int BM = 128 * HM, BN = 128 * HN;
     constexpr int HALF = 128 * 128;            // bytes of a half tile
@@ -111,12 +117,14 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
     const int kt0 = slice * a.kt_slice;
     const int ks = a.kslices > 1 ? (a.ksteps - kt0 < a.kt_slice ? a.ksteps - kt0 : a.kt_slice) : a.ksteps;
     const __amdgpu_buffer_rsrc_t xsrd = pp_srd(a.x, a.x_bytes), wsrd = pp_srd(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t x2srd = DUAL ? pp_srd(a.x2, a.x2_bytes) : xsrd;
 
     // ---- loader: a piece = 8 rows x 128 B (one wave instruction); wave w fills pieces w and w+8 of a half
     // tile; lane l -> row 8*piece + (l>>3), slot (l&7).  (row>>1)&7 = (4*(w&1) + (l>>4)) & 7 for both pieces.
     const int lrow = lane >> 3;
     const int lc = (lane & 7) ^ ((4 * (wid & 1) + (lane >> 4)) & 7);   // logical K chunk behind this lane's slot
     int xo[2][2], wo[2][2];
+    int xo2[2][2];            // DUAL: this row's pixel in x2
     unsigned tapmask[2][2];   // CONV: taps of this row that lie inside the image
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -144,6 +152,14 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
                 xo[h][j] = (h < HM && m < a.M) ? m * a.x_ld * ES : OOB;
                 tapmask[h][j] = 0;
             }
+            if constexpr (DUAL) {
+                const bool live = h < HM && m < a.M;
+                const int mm = live ? m : 0;
+                const int n = mm / a.dHoWo, rem = mm - n * a.dHoWo;
+                const int ho = rem / a.dWo, wo_ = rem - ho * a.dWo;
+                // (a live row's pixel lies inside x2: its byte offset is below a.x2_bytes < 2^31)
+                xo2[h][j] = live ? ((n * a.dH2 + ho * a.ds) * a.dW2 + wo_ * a.ds) * a.x2_ld * ES : OOB;
+            }
             const int rho = 128 * h + 8 * (wid + 8 * j) + lrow;    // LDS row; holds channel perm(rho) (conv_igemm.hip)
             const int n = (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3);
             wo[h][j] = (bn0 + n) * a.Kp_bytes;
@@ -160,6 +176,17 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
             const int d = (DIL ? r * a.cdh * a.cW + s_ * a.cdw : r * a.cW + s_) * a.x_ld * ES + (((kt - (tap << a.ctshift)) * 8 + lc) << 4);
 #pragma unroll
             for (int j = 0; j < 2; ++j) pp_dma16(xsrd, b + j * 8192, (mine && ((tapmask[h][j] >> tap) & 1u)) ? xo[h][j] + d : OOB);
+        } else if constexpr (DUAL) {
+            if (kt < a.k1_tiles) {                                 // wave-uniform
+                const int q = kt * 8 + lc;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) pp_dma16(xsrd, b + j * 8192, mine ? xo[h][j] + q * 16 : OOB);
+            } else {
+                const int q = (kt - a.k1_tiles) * 8 + lc;
+                const bool in = mine && kt < a.k1_tiles + a.k2_tiles;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) pp_dma16(x2srd, b + j * 8192, in ? xo2[h][j] + q * 16 : OOB);
+            }
         } else {
             const int q = kt * 8 + lc;
             const bool in = mine && q < a.kchunks;
@@ -529,7 +556,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
 }
 
 // Preconditions as launch_gemm256 (checked by conv_igemm.hip's dispatcher); a.ksteps = packed pitch / 128.
-template <typename T, int HM, int HN, bool CONV, bool LNF = false, bool DIL = false> static int launch_pp_t(const Gemm256Args& a0, hipStream_t st) {
+template <typename T, int HM, int HN, bool CONV, bool LNF = false, bool DIL = false, bool DUAL = false> static int launch_pp_t(const Gemm256Args& a0, hipStream_t st) {
     Gemm256Args a = a0;
     a.debug = (int)tune_int("TLXMI_DEBUG", 0);     // ablation bits: tuning flavour only (TLXMI_DBG is `false` in the product)
     a.mtiles = (a.M + 128 * HM - 1) / (128 * HM);
@@ -537,7 +564,7 @@ template <typename T, int HM, int HN, bool CONV, bool LNF = false, bool DIL = fa
     a.gn = a.ntiles;
     if (const long g = tune_int("TLXMI_GS_PANEL", 3); !CONV && g > 0 && g < a.ntiles) a.gn = (int)g;
     const size_t lds = (size_t)(HM + HN == 4 ? 8 : 9) * 128 * 128 + 2 * 256 * sizeof(float);
-    const void* fn = reinterpret_cast<const void*>(&gemm_pp_kernel<T, HM, HN, CONV, LNF, DIL>);
+    const void* fn = reinterpret_cast<const void*>(&gemm_pp_kernel<T, HM, HN, CONV, LNF, DIL, DUAL>);
     if (int rc = raise_lds_limit(fn, (int)lds, "gemm_pp")) return rc;
     void* args[] = {&a};
     hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(a.mtiles * a.ntiles * (a.kslices > 1 ? a.kslices : 1))), dim3(512), args, lds, st);
@@ -580,6 +607,14 @@ int launch_gemm_pp_n128(int dtype, const Gemm256Args& a, hipStream_t st) {
     if (a.conv) return launch_pp_conv<2, 1>(dtype, a, st);
     if (dtype == TLXMI_F16) return launch_pp_t<half_t, 2, 1, false>(a, st);
     return launch_pp_t<float, 2, 1, false>(a, st);
+}
+
+// DUAL instances (fp16): 256 x 256 tiles, or 128 x 256 (half_height) for launches of few row tiles.  Preconditions checked by
+// tlxmi_conv1x1_proj (conv_igemm.hip): a.x2 and its geometry set, both K extents whole K tiles, a.ksteps = k1_tiles + k2_tiles.
+int launch_gemm_pp_dual(const Gemm256Args& a, bool half_height, hipStream_t st) {
+    if (a.conv || a.kslices > 1 || a.rowstats || a.stats_out || !a.x2 || a.k1_tiles < 1 || a.k2_tiles < 1 || a.ksteps != a.k1_tiles + a.k2_tiles)
+        return fail(TLXMI_ERR_UNSUPPORTED, "gemm_pp: the two-operand form takes plain rows plus one gathered operand (no split K, no LayerNorm fold)");
+    return half_height ? launch_pp_t<half_t, 1, 2, false, false, false, true>(a, st) : launch_pp_t<half_t, 2, 2, false, false, false, true>(a, st);
 }
 
 }  // namespace tlxmi

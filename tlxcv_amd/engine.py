@@ -24,6 +24,11 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
             "seams": True,        # block-to-block seams of the bottleneck families as one launch (tlxmi_bottleneck_seam); off = the
                                   # expand conv and the next block's reduce conv as two launches (the A/B and the parity tests' other arm)
             "seam256": True,      # bottleneck seams with a 256-channel conv3 input (ResNet-50 layer3, 14 x 14) fused too
+            "proj_fold": 7,       # (a bit mask) ResNet transition blocks (layer2.0 / layer3.0 / layer4.0 = bits 1 / 2 / 4): the 1x1 projection
+                                  # shortcut as extra K of the block's expand conv (tlxmi_conv1x1_proj, fp16), its map neither written nor
+                                  # read; a clear bit = the shortcut as its own launch, read back as the expand conv's residual (the A/B and
+                                  # the parity tests' other arm).  All on: bits 1 and 2 each win alone; bit 4 is inside the noise
+                                  # end to end but removes a launch and trades no seam for it (137 -> 84 us); mask 7 has the best mean (+1.9 .. 2.1 %)
             "two_streams": True,  # large batches as two half batches on two HIP streams (two_streams(), below)
             "conv_splitk": True,  # convs with few pixels and a long K on K slices (tlxmi_conv2d_splitk)
             "patch_linear": True, # ViT patch embedding as one Linear over all token rows (tlxmi_patchify + the persistent GEMM); off = the
@@ -723,6 +728,58 @@ def bottleneck_seam(t2, pk3, scale3, shift3, skip, pk1, scale1, shift1, proj=Non
     e1.record()
     _probe.append((e0, e1, alg_bytes, flops, (N, H, W, pk3.Cin, pk3.Cout, pk1.Cout, "seam" if proj is None else "seam+proj", True)))
     return y, t1
+
+
+def _proj_desc(t2, x2, pk, stride, out_ld, act, act_param, k2):
+    N, Ho, Wo, ld = t2.shape
+    k2 = x2.shape[-1] if k2 is None else int(k2)
+    return _lib.ProjDesc(dtype=dt_code(t2.dtype), N=N, Ho=Ho, Wo=Wo, K1=pk.Cin - k2, K2=k2, Cout=pk.Cout, H2=x2.shape[1],
+                         W2=x2.shape[2], stride=int(stride), x_ld=ld, x2_ld=x2.shape[-1], y_ld=out_ld, act=act, act_param=float(act_param),
+                         flags=plan_flags())
+
+
+def conv1x1_proj_supported(t2, x2, pk, stride, out=None, k2=None):
+    """Whether conv1x1_proj takes these operands (tlxmi_conv1x1_proj_supported: pure host code)."""
+    if (t2.dim() != 4 or x2.dim() != 4 or t2.dtype != pk.dtype or x2.dtype != pk.dtype or pk.R != 1 or pk.S != 1 or t2.shape[0] != x2.shape[0]
+            or pk.Cin <= (x2.shape[-1] if k2 is None else k2) or not t2.is_contiguous() or not x2.is_contiguous() or t2.dtype not in (torch.float16, torch.float32)):
+        return False
+    N, Ho, Wo, _ = t2.shape
+    # (the output is allocated by the call: any 16-byte aligned address apart from the inputs stands in for it here)
+    d = _proj_desc(t2, x2, pk, stride, pk.Cout if out is None else out.shape[-1], ACT_NONE, 0.0, k2)
+    y = C.c_void_p(16) if out is None else _p(out)
+    return bool(_lib.load().tlxmi_conv1x1_proj_supported(C.byref(d), _p(t2), _p(x2), _p(pk.buf), y))
+
+
+def conv1x1_proj(t2, x2, pk, stride, shift=None, act=ACT_NONE, act_param=0.0, out=None, k2=None):
+    """y = act([t2 | x2 at `stride`] . W'^T + shift) in one launch (tlxmi_conv1x1_proj): the expand conv of a ResNet transition block
+    with its 1x1 projection shortcut as extra K.  t2 (N,Ho,Wo,>=K1), x2 (N,H2,W2,>=K2) dense NHWC fp16 maps (their last extent is the
+    pitch; k2: the channels of x2 that are read, default all; K1 = pk.Cin - K2), pk = PackedFilter of [Cout][K1 + K2] with both BatchNorm scales folded in -> y (N,Ho,Wo,Cout), or `out` (a wider map)."""
+    need_gpu(t2, "input")
+    need_gpu(x2, "shortcut input")
+    if t2.dim() != 4 or x2.dim() != 4 or not t2.is_contiguous() or not x2.is_contiguous() or t2.shape[0] != x2.shape[0]:
+        raise RuntimeError("conv1x1_proj: t2 / x2 must be dense NHWC maps of one batch")
+    if t2.dtype != pk.dtype or x2.dtype != pk.dtype:
+        raise RuntimeError(f"conv1x1_proj: input dtypes {t2.dtype} / {x2.dtype} != packed filter dtype {pk.dtype}")
+    N, Ho, Wo, _ = t2.shape
+    if out is None:
+        out = torch.empty((N, Ho, Wo, pk.Cout), dtype=t2.dtype, device=t2.device)
+    d = _proj_desc(t2, x2, pk, stride, out.shape[-1], act, act_param, k2)
+    M = N * Ho * Wo
+    es = t2.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(t2.numel() * es, x2.numel() * es, M * d.y_ld * es)
+    args = (C.byref(d), _p(t2), _p(x2), _p(pk.buf), _p(shift), _p(out), _stream())
+    if _probe is None:
+        _lib.call("tlxmi_conv1x1_proj", *args)
+        return out
+    # algorithmic bytes: the rows of t2, the pixels of x2 the stride selects, the output, the filter
+    alg_bytes = (M * (d.K1 + d.K2) + M * pk.Cout + pk.Cout * pk.Cin) * es
+    flops = 2 * M * pk.Cout * pk.Cin
+    e0, e1 = _probe_pair()
+    _lib.call("tlxmi_conv1x1_proj", *args)
+    e1.record()
+    _probe.append((e0, e1, alg_bytes, flops, (N, Ho, Wo, d.K1, pk.Cout, d.K2, "expand+proj", int(stride))))
+    return out
 
 
 def group_conv2d(x, pk, stride=1, padding=0, dilation=1, scale=None, shift=None, res=None, act=ACT_NONE,

@@ -60,6 +60,9 @@ class BasicBlock(nn.Module):
 class BottleneckBlock(nn.Module):
     """resnet.py:80-156: 1x1 -> 3x3 (stride here) -> 1x1 (x4), BN after each, add, ReLU."""
     expansion = 4
+    # bits of E.option("proj_fold") that let this block fold its projection shortcut into conv3 (finish_folded): any bit for a block on
+    # its own; ResNet gives the first block of layer2 / layer3 / layer4 its own bit (1 / 2 / 4) and layer1.0 none (its seam computes it)
+    proj_fold_bit = 7
 
     def __init__(self, in_channels, out_channels, stride=1, downsample=None, groups=1, base_width=64, dilation=1,
                  batch_norm=None, data_format='channels_first'):
@@ -104,6 +107,45 @@ class BottleneckBlock(nn.Module):
     def finish(self, out, identity):
         return self.conv3.run_nhwc(out, self.bn3, E.ACT_RELU, res=identity)
 
+    def folded_filter(self):
+        """(PackedFilter of W' = [diag(s3) W3 | diag(sd) Wd], shift h3 + hd): conv3 + bn3 and the projection shortcut conv_d + bn_d as
+        ONE filter over [conv2's output | the block's input], the BatchNorm scales multiplied in fp32 before the one rounding to the
+        storage type.  Built once and kept on conv3; rebuilt when either filter or either BatchNorm changes."""
+        c3, cd, bnd = self.conv3, self.downsample[0], self.downsample[1]
+        dt = E.precision()
+
+        def build():
+            s3, h3 = self.bn3.folded(None)
+            sd, hd = bnd.folded(None)
+            w3 = E._f32(c3.filters).reshape(c3.out_channels, c3.in_channels) * s3[:, None]
+            wd = E._f32(cd.filters).reshape(cd.out_channels, cd.in_channels) * sd[:, None]
+            return E.PackedFilter(torch.cat([w3, wd], dim=1), dt), h3 + hd
+        return c3._cached(("projfold", id(cd), id(self.bn3), id(bnd)), build, deps=(cd, self.bn3, bnd))
+
+    def finish_folded(self, out, v):
+        """relu(bn3(conv3(out)) + bn_d(conv_d(v))) as ONE launch (E.conv1x1_proj): the projection shortcut is extra K of the expand
+        conv, its map is neither written nor read.  None when the block has no such shortcut, the option bit is clear, or the library
+        does not take the shapes (fp32, channel counts that are not whole K tiles) — the caller runs shortcut() + finish()."""
+        ds = self.downsample
+        if ds is None or E.precision() != torch.float16 or not (E.option_value("proj_fold") & self.proj_fold_bit):
+            return None
+        if len(ds) != 2 or not isinstance(ds[0], nn.GroupConv2d) or not isinstance(ds[1], nn.BatchNorm2d):
+            return None
+        # (one shift h3 + hd in front of one ReLU: neither BatchNorm, nor either conv, may carry an activation of its own)
+        if any(getattr(m, "act", None) is not None for m in (self.bn3, ds[1], self.conv3, ds[0])):
+            return None
+        c3, cd = self.conv3, ds[0]
+        plain = lambda c: (c.kernel_size == (1, 1) and c.padding == (0, 0) and c.dilation == (1, 1) and c.n_group == 1
+                           and c.biases is None and not c.same)
+        if (not plain(c3) or not plain(cd) or c3.stride != (1, 1) or cd.stride not in ((1, 1), (2, 2)) or cd.out_channels != c3.out_channels
+                or c3.in_channels % 64 or cd.in_channels % 64 or c3.out_channels % 8
+                or out.shape[-1] != c3.in_channels or v.shape[-1] != cd.in_channels):
+            return None
+        pk, shift = self.folded_filter()
+        if not E.conv1x1_proj_supported(out, v, pk, cd.stride[0]):
+            return None
+        return E.conv1x1_proj(out, v, pk, cd.stride[0], shift=shift, act=E.ACT_RELU)
+
     def seam_with(self, nxt, out, v):
         """(block output, nxt's conv1 output) in one launch — `v` is the block's input, the skip or the projection shortcut's
         source — or None when there is no fused kernel for these layers."""
@@ -147,15 +189,22 @@ def run_bottleneck_chain(blocks, v):
     kernel (fp16; resnet.py:142-156 per block).  Falls back block by block to conv3 + skip as its own launch."""
     t1 = None
     for i, blk in enumerate(blocks):
-        out = blk.run_head(v, t1)
-        t1 = None
-        nxt = blocks[i + 1] if i + 1 < len(blocks) else None
-        fused = blk.seam_with(nxt, out, v) if isinstance(nxt, BottleneckBlock) else None
-        if fused is not None:
-            v, t1 = fused
-        else:
-            v = blk.finish(out, blk.shortcut(v))
+        v, t1 = bottleneck_step(blk, blocks[i + 1] if i + 1 < len(blocks) else None, v, t1)
     return v
+
+
+def bottleneck_step(blk, nxt, v, t1=None):
+    """One block of run_bottleneck_chain: v = the block's input, t1 = its conv1 output if the previous step computed it, nxt = the block
+    that follows (or None).  -> (the block's output, nxt's conv1 output when this step's launch computed it, else None)."""
+    out = blk.run_head(v, t1)
+    # a stage transition: the projection shortcut inside the expand conv's launch, the next block's conv1 a launch of its own
+    folded = blk.finish_folded(out, v)
+    if folded is not None:
+        return folded, None
+    fused = blk.seam_with(nxt, out, v) if isinstance(nxt, BottleneckBlock) else None
+    if fused is not None:
+        return fused
+    return blk.finish(out, blk.shortcut(v)), None
 
 
 class ResNet(nn.Module):
@@ -181,6 +230,10 @@ class ResNet(nn.Module):
         self.layer2 = self._make_layer(block, 128, layers[1], stride=2, data_format=data_format)
         self.layer3 = self._make_layer(block, 256, layers[2], stride=2, data_format=data_format)
         self.layer4 = self._make_layer(block, 512, layers[3], stride=2, data_format=data_format)
+        if block is BottleneckBlock:      # E.option("proj_fold"): one bit per stage transition; layer1.0's shortcut is part of its seam
+            self.layer1[0].proj_fold_bit = 0
+            for bit, layer in ((1, self.layer2), (2, self.layer3), (4, self.layer4)):
+                layer[0].proj_fold_bit = bit
         if with_pool:
             self.avgpool = nn.AdaptiveAvgPool2d((1, 1), data_format=data_format)
         self.flatten = FlattenReshape()
