@@ -14,7 +14,7 @@
 //                      transposing LDS read (two ds_read_b64_tr_b16 per fragment).
 // The N x N score matrix never leaves registers.  HBM traffic per (b, head): Q, K, V read once,
 // O written once.
-#include "common.h"
+#include "kernel_util.h"
 
 namespace tlxmi {
 
@@ -294,7 +294,6 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(const AttnArgs a) {
 template <int NT, int KF, int NTL>
 __global__ __launch_bounds__(256, 2) void attn_dma_kernel(const AttnArgs a) {
     constexpr int HD = 64, SR = 128, NP = 16 * NTL, KS = 2, DT = 4;
-    constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;
     char* Vs = smem + NP * SR;
@@ -322,21 +321,18 @@ __global__ __launch_bounds__(256, 2) void attn_dma_kernel(const AttnArgs a) {
     // ---- K and V: piece p = keys 8p .. 8p + 7; lane l -> key 8p + (l >> 3), slot l & 7, source chunk (l & 7) ^ f(key); wave w
     // takes pieces w, w + 4, ...; keys past the sequence are an out-of-range offset (zero rows, no traffic)
     {
-        const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<void*>(a.qkv), 0, (unsigned)((size_t)a.B * N * tok_ld * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t srd = buf_srd(a.qkv, (unsigned)((size_t)a.B * N * tok_ld * 2));
         const int lc = (lane & 7) ^ (((lane >> 4) & 3) << 1);
         const int base = (int)(((size_t)b * N * tok_ld + (size_t)h * HD) * 2) + lc * 16;
         const int krow = lane >> 3;
-        typedef __attribute__((address_space(3))) void* lds_ptr_t;
 #pragma unroll
         for (int which = 1; which <= 2; ++which)      // 1: K, 2: V (the packed qkv row is [q | k | v] x [heads][hd])
 #pragma unroll
             for (int j = 0; j < (NP / 8 + 3) / 4; ++j) {
                 const int p = wv + 4 * j;
                 const int key = 8 * p + krow;
-                const int off = (p < NP / 8 && key < N && !TLXMI_DBG(a, 1)) ? base + (int)(key * tok_ld * 2) + which * heads * HD * 2 : OOB;      // (ablation bit 1, tuning flavour: no K / V traffic — zero rows)
-                if (p < NP / 8)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (lds_ptr_t)((which == 1 ? Ks : Vs) + p * 1024), 16, off, 0, 0, 0);
+                const int off = (p < NP / 8 && key < N && !TLXMI_DBG(a, 1)) ? base + (int)(key * tok_ld * 2) + which * heads * HD * 2 : BUF_OOB;      // (ablation bit 1, tuning flavour: no K / V traffic — zero rows)
+                if (p < NP / 8) buf_dma16(srd, (which == 1 ? Ks : Vs) + p * 1024, off);
             }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

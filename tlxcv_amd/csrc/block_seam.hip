@@ -22,7 +22,7 @@
 // The activation streams (t2, skip in; y, t1 out) are 16-byte-per-lane accesses whose four lane groups cover whole
 // 128-byte lines; the filters are staged through LDS per step (below).
 // Bound: HBM.  Algorithmic bytes per pixel: (K1 + 2*N1 + N2) * 2.
-#include "common.h"
+#include "kernel_util.h"
 #include <stdio.h>
 #include "block_seam.h"
 #ifdef TLXMI_TUNING
@@ -32,22 +32,6 @@
 #endif
 
 namespace tlxmi {
-
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t bs_srd(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-static __device__ __forceinline__ u32x4 bs_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-}
-static __device__ __forceinline__ void bs_store16_nt(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 2);
-}
-static __device__ __forceinline__ void bs_store16(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 0);
-}
-static __device__ __forceinline__ f32x4 bs_mma(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, a), __builtin_bit_cast(half8v, b), c, 0, 0, 0);
-}
 
 // Weight staging.  Every wave needs every filter element, so the filters go through LDS once per workgroup instead of
 // once per wave (as A fragments straight from L2 the fragment-shaped reads — 16 rows x 64 bytes per instruction — ran at
@@ -124,7 +108,6 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
     constexpr int NP = CB + Q2 + CD;
     constexpr int T2 = N2 / 16;          // MFMA row tiles of GEMM2
     constexpr int PANEL = 64 * 128;
-    constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const wbuf = smem;                                                   // two step buffers of NP panels
     float* const tab3 = reinterpret_cast<float*>(smem + 2 * NP * PANEL);       // scale3[N1], shift3[N1]
@@ -135,9 +118,9 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
     const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
     const int fr = lane & 15, g = lane >> 4;
 
-    const __amdgpu_buffer_rsrc_t xsrd = bs_srd(a.x, a.x_bytes), w3srd = bs_srd(a.w3, a.w3_bytes), w1srd = bs_srd(a.w1, a.w1_bytes);
-    const __amdgpu_buffer_rsrc_t rsrd = bs_srd(a.res, a.res_bytes), ysrd = bs_srd(a.y, a.y_bytes), zsrd = bs_srd(a.z, a.z_bytes);
-    const __amdgpu_buffer_rsrc_t wdsrd = bs_srd(PROJ ? a.wd : a.w3, PROJ ? a.wd_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), w3srd = buf_srd(a.w3, a.w3_bytes), w1srd = buf_srd(a.w1, a.w1_bytes);
+    const __amdgpu_buffer_rsrc_t rsrd = buf_srd(a.res, a.res_bytes), ysrd = buf_srd(a.y, a.y_bytes), zsrd = buf_srd(a.z, a.z_bytes);
+    const __amdgpu_buffer_rsrc_t wdsrd = buf_srd(PROJ ? a.wd : a.w3, PROJ ? a.wd_bytes : 0u);
 
     // staging: chunk k of this thread in every panel = (row, physical slot) of index k*NT + t; the logical chunks it fetches
     auto stage_load = [&](int c, u32x4 (&st)[NP][IPT]) {
@@ -146,11 +129,11 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
             const int idx = k * NT + t, srow = idx >> 3, sslot = idx & 7;
             const int sl1 = sslot ^ bs_f1(srow), sl2 = sslot ^ bs_f2(srow);
 #pragma unroll
-            for (int cb = 0; cb < CB; ++cb) st[cb][k] = bs_load16(w3srd, ((64 * c + srow) * K1 + 64 * cb + 8 * sl1) * 2);
+            for (int cb = 0; cb < CB; ++cb) st[cb][k] = buf_load16(w3srd, ((64 * c + srow) * K1 + 64 * cb + 8 * sl1) * 2);
 #pragma unroll
-            for (int q = 0; q < Q2; ++q) st[CB + q][k] = bs_load16(w1srd, ((64 * q + srow) * a.N1 + 64 * c + 8 * sl2) * 2);
+            for (int q = 0; q < Q2; ++q) st[CB + q][k] = buf_load16(w1srd, ((64 * q + srow) * a.N1 + 64 * c + 8 * sl2) * 2);
 #pragma unroll
-            for (int cb = 0; cb < CD; ++cb) st[CB + Q2 + cb][k] = bs_load16(wdsrd, ((64 * c + srow) * K1 + 64 * cb + 8 * sl1) * 2);
+            for (int cb = 0; cb < CD; ++cb) st[CB + Q2 + cb][k] = buf_load16(wdsrd, ((64 * c + srow) * K1 + 64 * cb + 8 * sl1) * 2);
         }
     };
     auto stage_write = [&](int buf, const u32x4 (&st)[NP][IPT]) {
@@ -176,14 +159,14 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
     for (int pw = 0; pw < PW; ++pw)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-            xf[ks][pw] = bs_load16(xsrd, pok[pw] ? (pix[pw] * a.x_ld + 32 * ks + 8 * g) * 2 : OOB);
+            xf[ks][pw] = buf_load16(xsrd, pok[pw] ? (pix[pw] * a.x_ld + 32 * ks + 8 * g) * 2 : BUF_OOB);
     u32x4 xpf[PROJ ? KS : 1][PW];      // PROJ: fragments of the block input (B operand of the shortcut product)
     if constexpr (PROJ) {
 #pragma unroll
         for (int pw = 0; pw < PW; ++pw)
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
-                xpf[ks][pw] = bs_load16(rsrd, pok[pw] ? (pix[pw] * a.res_ld + 32 * ks + 8 * g) * 2 : OOB);
+                xpf[ks][pw] = buf_load16(rsrd, pok[pw] ? (pix[pw] * a.res_ld + 32 * ks + 8 * g) * 2 : BUF_OOB);
     }
     auto skip_load = [&](int c, u32x4 (&sk)[PW][2]) {
         if constexpr (PROJ || MLP) return;
@@ -191,7 +174,7 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
         for (int pw = 0; pw < PW; ++pw)
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                sk[pw][h] = bs_load16(rsrd, pok[pw] ? (pix[pw] * a.res_ld + 64 * c + 16 * g + 8 * h) * 2 : OOB);
+                sk[pw][h] = buf_load16(rsrd, pok[pw] ? (pix[pw] * a.res_ld + 64 * c + 16 * g + 8 * h) * 2 : BUF_OOB);
     };
     u32x4 sk[PW][2];
     skip_load(0, sk);
@@ -261,7 +244,7 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
             for (int ks = 0; ks < KS; ++ks) {
                 const u32x4 af = *reinterpret_cast<const u32x4*>(wb + (ks >> 1) * PANEL + (a1off[ci] ^ ((ks & 1) << 6)));
 #pragma unroll
-                for (int pw = 0; pw < PW; ++pw) acc1[ci][pw] = bs_mma(af, xf[ks][pw], acc1[ci][pw]);
+                for (int pw = 0; pw < PW; ++pw) acc1[ci][pw] = Mma<half_t>::run(af, xf[ks][pw], acc1[ci][pw]);
             }
         }
         f32x4 accd[PROJ ? 4 : 1][PW];
@@ -274,7 +257,7 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
                 for (int ks = 0; ks < KS; ++ks) {
                     const u32x4 af = *reinterpret_cast<const u32x4*>(wb + (CB + Q2 + (ks >> 1)) * PANEL + (a1off[ci] ^ ((ks & 1) << 6)));
 #pragma unroll
-                    for (int pw = 0; pw < PW; ++pw) accd[ci][pw] = bs_mma(af, xpf[ks][pw], accd[ci][pw]);
+                    for (int pw = 0; pw < PW; ++pw) accd[ci][pw] = Mma<half_t>::run(af, xpf[ks][pw], accd[ci][pw]);
                 }
             }
         }
@@ -316,8 +299,8 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
                     const u32x4 o = u32x4{o0[0], o0[1], o1[0], o1[1]};
                     yf[pw][h] = o;
                     if (TLXMI_DBG(a, 1)) continue;
-                    if (TLXMI_DBG_NT(a.y_nt)) bs_store16_nt(ysrd, yf[pw][h], pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * h) * 2 : OOB);
-                    else bs_store16(ysrd, yf[pw][h], pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * h) * 2 : OOB);
+                    if (TLXMI_DBG_NT(a.y_nt)) buf_store16<BUF_NT>(ysrd, yf[pw][h], pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * h) * 2 : BUF_OOB);
+                    else buf_store16(ysrd, yf[pw][h], pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * h) * 2 : BUF_OOB);
                 }
             }
         }
@@ -330,7 +313,7 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
             for (int s = 0; s < 2; ++s) {
                 const u32x4 af = *reinterpret_cast<const u32x4*>(wb + (CB + (tt >> 2)) * PANEL + (a2off[tt & 3] ^ (s << 4)));
 #pragma unroll
-                for (int pw = 0; pw < PW; ++pw) acc2[tt][pw] = bs_mma(af, yf[pw][s], acc2[tt][pw]);
+                for (int pw = 0; pw < PW; ++pw) acc2[tt][pw] = Mma<half_t>::run(af, yf[pw][s], acc2[tt][pw]);
             }
         }
 
@@ -355,7 +338,7 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
             for (int pw = 0; pw < PW; ++pw) {
                 u32x2 o0, o1;
                 if constexpr (MLP) {      // + the residual rows, no activation
-                    const half8v rv = __builtin_bit_cast(half8v, bs_load16(rsrd, pok[pw] ? (pix[pw] * a.res_ld + 64 * q + 16 * g + 8 * h) * 2 : OOB));
+                    const half8v rv = __builtin_bit_cast(half8v, buf_load16(rsrd, pok[pw] ? (pix[pw] * a.res_ld + 64 * q + 16 * g + 8 * h) * 2 : BUF_OOB));
                     o0 = bs_bn_res4(acc2[4 * q + 2 * h][pw], s0, h0, half4v{rv[0], rv[1], rv[2], rv[3]});
                     o1 = bs_bn_res4(acc2[4 * q + 2 * h + 1][pw], s1, h1, half4v{rv[4], rv[5], rv[6], rv[7]});
                 } else {
@@ -364,8 +347,8 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
                 }
                 const u32x4 o = u32x4{o0[0], o0[1], o1[0], o1[1]};
                 if (TLXMI_DBG(a, 4)) continue;
-                if (TLXMI_DBG_NT(a.z_nt)) bs_store16_nt(zsrd, o, pok[pw] ? (pix[pw] * a.z_ld + 64 * q + 16 * g + 8 * h) * 2 : OOB);
-                else bs_store16(zsrd, o, pok[pw] ? (pix[pw] * a.z_ld + 64 * q + 16 * g + 8 * h) * 2 : OOB);
+                if (TLXMI_DBG_NT(a.z_nt)) buf_store16<BUF_NT>(zsrd, o, pok[pw] ? (pix[pw] * a.z_ld + 64 * q + 16 * g + 8 * h) * 2 : BUF_OOB);
+                else buf_store16(zsrd, o, pok[pw] ? (pix[pw] * a.z_ld + 64 * q + 16 * g + 8 * h) * 2 : BUF_OOB);
             }
         }
     }
@@ -391,7 +374,6 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
     constexpr int NP = CB + Q2;
     constexpr int T2H = N2 / 32;         // row tiles of GEMM2 per wave (half of N2 / 16)
     constexpr int PANEL = 64 * 128;
-    constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const wbuf = smem;
     float* const tab3 = reinterpret_cast<float*>(smem + 2 * NP * PANEL);
@@ -403,8 +385,8 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
     const int hh = wid & 1, pp = wid >> 1;
     const int fr = lane & 15, g = lane >> 4;
 
-    const __amdgpu_buffer_rsrc_t xsrd = bs_srd(a.x, a.x_bytes), w3srd = bs_srd(a.w3, a.w3_bytes), w1srd = bs_srd(a.w1, a.w1_bytes);
-    const __amdgpu_buffer_rsrc_t rsrd = bs_srd(a.res, a.res_bytes), ysrd = bs_srd(a.y, a.y_bytes), zsrd = bs_srd(a.z, a.z_bytes);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), w3srd = buf_srd(a.w3, a.w3_bytes), w1srd = buf_srd(a.w1, a.w1_bytes);
+    const __amdgpu_buffer_rsrc_t rsrd = buf_srd(a.res, a.res_bytes), ysrd = buf_srd(a.y, a.y_bytes), zsrd = buf_srd(a.z, a.z_bytes);
 
     auto stage_load = [&](int c, u32x4 (&st)[NP][IPT]) {
 #pragma unroll
@@ -412,9 +394,9 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
             const int idx = k * NT + t, srow = idx >> 3, sslot = idx & 7;
             const int sl1 = sslot ^ bs_f1(srow), sl2 = sslot ^ bs_f2(srow);
 #pragma unroll
-            for (int cb = 0; cb < CB; ++cb) st[cb][k] = bs_load16(w3srd, ((64 * c + srow) * K1 + 64 * cb + 8 * sl1) * 2);
+            for (int cb = 0; cb < CB; ++cb) st[cb][k] = buf_load16(w3srd, ((64 * c + srow) * K1 + 64 * cb + 8 * sl1) * 2);
 #pragma unroll
-            for (int q = 0; q < Q2; ++q) st[CB + q][k] = bs_load16(w1srd, ((64 * q + srow) * a.N1 + 64 * c + 8 * sl2) * 2);
+            for (int q = 0; q < Q2; ++q) st[CB + q][k] = buf_load16(w1srd, ((64 * q + srow) * a.N1 + 64 * c + 8 * sl2) * 2);
         }
     };
     auto stage_write = [&](int buf, const u32x4 (&st)[NP][IPT]) {
@@ -437,10 +419,10 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
     for (int pw = 0; pw < PW; ++pw)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-            xf[ks][pw] = bs_load16(xsrd, pok[pw] ? (pix[pw] * a.x_ld + 32 * ks + 8 * g) * 2 : OOB);
+            xf[ks][pw] = buf_load16(xsrd, pok[pw] ? (pix[pw] * a.x_ld + 32 * ks + 8 * g) * 2 : BUF_OOB);
     auto skip_load = [&](int c, u32x4 (&sk)[PW]) {
 #pragma unroll
-        for (int pw = 0; pw < PW; ++pw) sk[pw] = bs_load16(rsrd, pok[pw] ? (pix[pw] * a.res_ld + 64 * c + 16 * g + 8 * hh) * 2 : OOB);
+        for (int pw = 0; pw < PW; ++pw) sk[pw] = buf_load16(rsrd, pok[pw] ? (pix[pw] * a.res_ld + 64 * c + 16 * g + 8 * hh) * 2 : BUF_OOB);
     };
     u32x4 sk[PW];
     skip_load(0, sk);
@@ -500,7 +482,7 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
             for (int ks = 0; ks < KS; ++ks) {
                 const u32x4 af = *reinterpret_cast<const u32x4*>(wb + (ks >> 1) * PANEL + (a1off[e] ^ ((ks & 1) << 6)));
 #pragma unroll
-                for (int pw = 0; pw < PW; ++pw) acc1[e][pw] = bs_mma(af, xf[ks][pw], acc1[e][pw]);
+                for (int pw = 0; pw < PW; ++pw) acc1[e][pw] = Mma<half_t>::run(af, xf[ks][pw], acc1[e][pw]);
             }
         }
         // ---- epilogue 1 of the half: BN, + skip, ReLU; stored to y and handed to the partner wave
@@ -516,7 +498,7 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
                 const u32x2 o0 = bs_bn_skip_relu4(acc1[0][pw], s0, h0, half4v{rv[0], rv[1], rv[2], rv[3]});
                 const u32x2 o1 = bs_bn_skip_relu4(acc1[1][pw], s1, h1, half4v{rv[4], rv[5], rv[6], rv[7]});
                 const u32x4 o = u32x4{o0[0], o0[1], o1[0], o1[1]};
-                bs_store16(ysrd, o, pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * hh) * 2 : OOB);
+                buf_store16(ysrd, o, pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * hh) * 2 : BUF_OOB);
                 *reinterpret_cast<u32x4*>(ymine + pw * 1024) = o;
                 if (hh == 0) yf[pw][0] = o; else yf[pw][1] = o;
             }
@@ -534,7 +516,7 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
             for (int s = 0; s < 2; ++s) {
                 const u32x4 af = *reinterpret_cast<const u32x4*>(wb + (CB + hh * (Q2 / 2) + (tt >> 2)) * PANEL + (a2off[tt & 3] ^ (s << 4)));
 #pragma unroll
-                for (int pw = 0; pw < PW; ++pw) acc2[tt][pw] = bs_mma(af, yf[pw][s], acc2[tt][pw]);
+                for (int pw = 0; pw < PW; ++pw) acc2[tt][pw] = Mma<half_t>::run(af, yf[pw][s], acc2[tt][pw]);
             }
         }
         if (more) {
@@ -558,7 +540,7 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
             for (int pw = 0; pw < PW; ++pw) {
                 const u32x2 o0 = bs_bn_relu4(acc2[4 * q + 2 * h][pw], s0, h0), o1 = bs_bn_relu4(acc2[4 * q + 2 * h + 1][pw], s1, h1);
                 const u32x4 o = u32x4{o0[0], o0[1], o1[0], o1[1]};
-                bs_store16(zsrd, o, pok[pw] ? (pix[pw] * a.z_ld + 64 * (hh * (Q2 / 2) + q) + 16 * g + 8 * h) * 2 : OOB);
+                buf_store16(zsrd, o, pok[pw] ? (pix[pw] * a.z_ld + 64 * (hh * (Q2 / 2) + q) + 16 * g + 8 * h) * 2 : BUF_OOB);
             }
         }
     }

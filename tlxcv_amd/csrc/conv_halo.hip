@@ -33,35 +33,15 @@
 // — the other wave group, one barrier later — combines rows 2j-1, 2j, 2j+1 (the first from tile j-1's ring slot) and
 // stores pooled row j with full-line 16-byte stores.  A workgroup whose range starts inside an image first recomputes
 // the tile before it (no store) to obtain row 2j-1.  Padding of the pool is "skip", which equals -inf padding.
-#include "common.h"
+#include "kernel_util.h"
 #include "conv_halo.h"
 #include <stdlib.h>
 
 namespace tlxmi {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_ch_t;
-static __device__ __forceinline__ void ch_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_ch_t)lds, 16, voff, 0, 0, 0);
-}
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t ch_srd(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-static __device__ __forceinline__ u32x4 ch_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-}
-static __device__ __forceinline__ void ch_store16_nt(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 2);
-}
-static __device__ __forceinline__ void ch_store16_wb(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 0);
-}
-
 // R x S taps, PB = bytes per input pixel (C * 2); S * PB must be a multiple of 64 (one MFMA K slice)
 // PI = MFMA pixel sub-tiles per wave: a tile is TP = 32 * PI consecutive pixels (8 where the filter registers
 // leave room)
-template <int CTRL> static __device__ __forceinline__ unsigned ch_dpp(unsigned v) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
 // packed fp16 maximum as ONE instruction (the builtin maximum canonicalises both operands first: three instructions)
 static __device__ __forceinline__ unsigned ch_pkmax(unsigned a, unsigned b) {
     unsigned r;
@@ -80,7 +60,6 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const HaloArgs a) {
     constexpr int TP = 32 * PI;          // pixels of a tile (2 pixel halves x PI sub-tiles of 16)
     constexpr int KR = S * PB / 64;      // K slices per filter row
     constexpr int NKK = R * KR;          // K slices in all
-    constexpr int OOB = (int)0x80000000;
     constexpr int PSH = PB == 128 ? 7 : PB == 64 ? 6 : 5;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -90,9 +69,9 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const HaloArgs a) {
     const int pg = wid & 1, cg = (wid >> 1) & 1;  // pixel half, channel half inside the group
     const int frow = lane & 15, fg = lane >> 4;
 
-    const __amdgpu_buffer_rsrc_t xsrd = ch_srd(a.x, a.x_bytes), wsrd = ch_srd(a.w, a.w_bytes);
-    const __amdgpu_buffer_rsrc_t ysrd = ch_srd(a.y, a.y_bytes);
-    const __amdgpu_buffer_rsrc_t rsrd = ch_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrd = buf_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
 
     // one channel tile (a.nt) per launch: the filters are loaded once, before the tile loop.  Workgroup b takes
     // the contiguous tile range [b*T/G, (b+1)*T/G) in (image, first pixel) order: consecutive tiles of an image.
@@ -141,7 +120,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const HaloArgs a) {
             const int ix = x0 + lpix;
             const bool in = iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
             const int rowoff = ((n * a.H + iy) * a.W + x0) * a.x_ld * 2;
-            ch_dma16(xsrd, smem + ((slot0 + py) & rmask) * row_bytes + (pc << 10), in ? rowoff + loff : OOB);
+            buf_dma16(xsrd, smem + ((slot0 + py) & rmask) * row_bytes + (pc << 10), in ? rowoff + loff : BUF_OOB);
             pc += 4;
             while (pc >= PR) { pc -= PR; ++py; }
         }
@@ -177,7 +156,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const HaloArgs a) {
             const int ch = cbase + 8 * (frow >> 2) + 4 * ci + (frow & 3);
             const int woff = ch * a.Kp_bytes + fg * 16;
 #pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) wreg[ci][kk] = ch_load16(wsrd, woff + kk * 64);
+            for (int kk = 0; kk < NKK; ++kk) wreg[ci][kk] = buf_load16(wsrd, woff + kk * 64);
         }
         // scale / shift of the launch's 64 channels -> LDS table behind the ring (read back in the epilogues)
         if (t < 64) {
@@ -237,8 +216,8 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const HaloArgs a) {
                             if (jrow > 0) m = ch_pkmax4(m, *reinterpret_cast<const u32x4*>(rp + off));
                         }
                         const int opix = (tj.n * a.tpi + jrow) * (16 * PI / 2) + xh;     // pooled pixel index (N, Ho/2, Wo/2)
-                        if (!TLXMI_DBG(a, 0x8000)) ch_store16_wb(ysrd, m, (in && st_ok && ch * 8 < a.Cout && !TLXMI_DBG(a, 2)) ? (opix * a.y_ld + a.nt * 64 + ch * 8) * 2 : OOB);
-                        else ch_store16_nt(ysrd, m, (in && st_ok && ch * 8 < a.Cout && !TLXMI_DBG(a, 2)) ? (opix * a.y_ld + a.nt * 64 + ch * 8) * 2 : OOB);
+                        if (!TLXMI_DBG(a, 0x8000)) buf_store16<BUF_WB>(ysrd, m, (in && st_ok && ch * 8 < a.Cout && !TLXMI_DBG(a, 2)) ? (opix * a.y_ld + a.nt * 64 + ch * 8) * 2 : BUF_OOB);
+                        else buf_store16<BUF_NT>(ysrd, m, (in && st_ok && ch * 8 < a.Cout && !TLXMI_DBG(a, 2)) ? (opix * a.y_ld + a.nt * 64 + ch * 8) * 2 : BUF_OOB);
                     }
                 }
         }
@@ -351,8 +330,8 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const HaloArgs a) {
                         for (int q = 0; q < 4; ++q) {
                             // row_ror:1 — lane l takes lane l-1 of its 16-lane row, lane 0 takes lane 15: feed lane 15 the
                             // previous sub-tile's value, so that lane 0 receives pixel x-1 across the sub-tile seam
-                            const unsigned left = ch_dpp<0x121>(frow == 15 ? prev[q] : cur4[q]);
-                            const unsigned right = ch_dpp<0x12F>(cur4[q]);      // row_ror:15 — lane l takes lane l+1
+                            const unsigned left = dpp<0x121>(frow == 15 ? prev[q] : cur4[q]);
+                            const unsigned right = dpp<0x12F>(cur4[q]);      // row_ror:15 — lane l takes lane l+1
                             const unsigned m = ch_pkmax(cur4[q], right);
                             hm[q] = (pi == 0 && frow == 0) ? m : ch_pkmax(m, left);   // x = 0: the left tap is padding
                         }
@@ -377,7 +356,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const HaloArgs a) {
                         for (int p2 = 0; p2 < 4; ++p2) {
                             const int pt2 = pg * (16 * PI) + (pi + p2) * 16 + frow;
                             const int mg2 = cur.n * a.HoWo + cur.m0 + pt2;
-                            rr[p2] = ch_load16(rsrd, (chok && pt2 < cur.npx) ? (mg2 * a.res_ld + ch0) * 2 : OOB);
+                            rr[p2] = buf_load16(rsrd, (chok && pt2 < cur.npx) ? (mg2 * a.res_ld + ch0) * 2 : BUF_OOB);
                         }
                     }
                     const int pt = pg * (16 * PI) + pi * 16 + frow;
@@ -424,8 +403,8 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const HaloArgs a) {
                     half8v hv;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) hv[e] = (half_t)v[e];
-                    if (!TLXMI_DBG(a, 0x8000)) ch_store16_wb(ysrd, __builtin_bit_cast(u32x4, hv), (ok && !TLXMI_DBG(a, 2)) ? (mg * a.y_ld + ch0) * 2 : OOB);
-                    else ch_store16_nt(ysrd, __builtin_bit_cast(u32x4, hv), (ok && !TLXMI_DBG(a, 2)) ? (mg * a.y_ld + ch0) * 2 : OOB);
+                    if (!TLXMI_DBG(a, 0x8000)) buf_store16<BUF_WB>(ysrd, __builtin_bit_cast(u32x4, hv), (ok && !TLXMI_DBG(a, 2)) ? (mg * a.y_ld + ch0) * 2 : BUF_OOB);
+                    else buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, hv), (ok && !TLXMI_DBG(a, 2)) ? (mg * a.y_ld + ch0) * 2 : BUF_OOB);
                 }
             }
             // the rows of tile p+2 have landed; the PI stores just issued (and nothing else) may stay in flight

@@ -26,7 +26,7 @@
 // DMA destination is lane-linear, the swizzle is applied to the source: lane l of a piece fetches
 // chunk (l&7) ^ ((r>>1)&7) of its row.  Pieces are dealt to waves so that this chunk index is
 // the same for every piece a lane loads (one im2col position per lane per step).
-#include "common.h"
+#include "kernel_util.h"
 #include <stdio.h>
 #include "gemm256.h"
 #include "conv_halo.h"
@@ -77,22 +77,6 @@ struct ConvArgs {
 
 __device__ __attribute__((aligned(16))) unsigned g_zero_page[4];  // source of padding / tail chunks
 
-template <typename T> struct Mma;
-template <> struct Mma<half_t> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, a),
-                                                      __builtin_bit_cast(half8v, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<float> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-        return c;
-    }
-};
-
 __device__ __forceinline__ int lds_off(int row, int chunk) {
     return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
 }
@@ -124,20 +108,6 @@ template <> __device__ __forceinline__ void store8<float>(char* p, const float* 
     reinterpret_cast<f32x4*>(p)[1] = b;
 }
 
-// One LDS-DMA wave instruction: 64 lanes x 16 B from buffer offsets `voff` to the 1-KiB piece at `lds`
-// (wave-uniform).  Kept out of the kernel template: the builtin must not see template-dependent
-// operands (the host pass of hipcc cannot re-check it at instantiation time).
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-static __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
-template <int AUX> static __device__ __forceinline__ void buf_store16(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, AUX);
-}
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const char* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, bytes, 0x00020000);
-}
-
 // WGM = waves along the pixel axis (2 or 4; always 2 along channels), STAGES = LDS-DMA ring depth.
 // RESP = the residual tile is prefetched into registers at kernel entry (dense, 16-byte-aligned residual):
 // its HBM latency then overlaps the first DMA stage instead of starting after the last MFMA.
@@ -160,7 +130,6 @@ __global__ __launch_bounds__(WGM * 128) void conv_igemm_kernel(const ConvArgs a0
     constexpr int PI = WM / 16, CI = WN / 16;
     constexpr int XP = BM / 8 / NW, WP = BN / 8 / NW;  // 1-KiB pieces per wave per K-step
     constexpr int BUF = (BM + BN) * 128;
-    constexpr int OOB = (int)0x80000000;       // any offset >= 2^31 fails the descriptor range check -> zeros
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int t = threadIdx.x, lane = t & 63;
@@ -186,29 +155,29 @@ __global__ __launch_bounds__(WGM * 128) void conv_igemm_kernel(const ConvArgs a0
     const int bm0 = tile_m * BM, bn0 = tile_n * BN;
 
     // Buffer descriptors: 32-bit per-lane byte offsets, and the hardware range check supplies the
-    // zeros of padding taps / tail rows / tail K chunks (offset OOB) with no select on the data path.
-    const __amdgpu_buffer_rsrc_t xsrd = make_srd(a.x, a.x_bytes);
-    const __amdgpu_buffer_rsrc_t wsrd = make_srd(a.w, a.w_bytes);
-    const __amdgpu_buffer_rsrc_t ysrd = make_srd(a.y, a.y_bytes);
+    // zeros of padding taps / tail rows / tail K chunks (offset BUF_OOB) with no select on the data path.
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t wsrd = buf_srd(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes);
 
     // ---- loader state.  Wave `wid` fills pieces wid, wid+4, ... ; inside a piece lane l owns tile row
     // 8*piece + (l>>3), LDS slot (l&7).  (row>>1)&7 = (4*(wid&1) + (l>>4)) & 7 for all of them, so the
     // logical K chunk a lane fetches is the same for every piece it loads.
     const int lr = lane >> 3;
     const int lchunk = (lane & 7) ^ ((((wid & 1) << 2) + (lane >> 4)) & 7);
-    int xo[XP];             // byte offset of (pixel row i, tap (0,0), chunk 0); OOB for tail rows (1x1 path)
+    int xo[XP];             // byte offset of (pixel row i, tap (0,0), chunk 0); BUF_OOB for tail rows (1x1 path)
     int hi0[XP], wi0[XP];   // top-left input coordinate of the pixel's receptive field (general path)
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
         const int m = bm0 + 8 * (wid + NW * i) + lr;
         if constexpr (IS_1X1) {
             if (a.sh == 1 && a.sw == 1) {
-                xo[i] = m < a.M ? m * a.x_ld * ES : OOB;
+                xo[i] = m < a.M ? m * a.x_ld * ES : BUF_OOB;
             } else {
                 const int mm = m < a.M ? m : 0;
                 const int n = mm / a.HoWo, rem = mm - n * a.HoWo;
                 const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-                xo[i] = m < a.M ? ((n * a.H + ho * a.sh) * a.W + wo * a.sw) * a.x_ld * ES : OOB;
+                xo[i] = m < a.M ? ((n * a.H + ho * a.sh) * a.W + wo * a.sw) * a.x_ld * ES : BUF_OOB;
             }
             hi0[i] = wi0[i] = 0;
         } else {
@@ -244,22 +213,22 @@ __global__ __launch_bounds__(WGM * 128) void conv_igemm_kernel(const ConvArgs a0
         char* b = smem + buf * BUF;
         const bool kv = q < a.kchunks;
         if constexpr (IS_1X1) {
-            const int d = kv ? q * 16 : OOB;
+            const int d = kv ? q * 16 : BUF_OOB;
 #pragma unroll
             for (int i = 0; i < XP; ++i)
-                lds_dma16(xsrd, b + (wid + NW * i) * 1024, xo[i] + d);
+                buf_dma16(xsrd, b + (wid + NW * i) * 1024, xo[i] + d);
         } else {
             const int hoff = r * a.dh, woff = s * a.dw;
             const int d = (hoff * a.W + woff) * a.x_ld * ES + cc * 16;
 #pragma unroll
             for (int i = 0; i < XP; ++i) {
                 const bool ok = kv && (unsigned)(hi0[i] + hoff) < (unsigned)a.H && (unsigned)(wi0[i] + woff) < (unsigned)a.W;
-                lds_dma16(xsrd, b + (wid + NW * i) * 1024, ok ? xo[i] + d : OOB);
+                buf_dma16(xsrd, b + (wid + NW * i) * 1024, ok ? xo[i] + d : BUF_OOB);
             }
         }
 #pragma unroll
         for (int j = 0; j < WP; ++j)
-            lds_dma16(wsrd, b + BM * 128 + (wid + NW * j) * 1024, wo_[j] + q * 16);
+            buf_dma16(wsrd, b + BM * 128 + (wid + NW * j) * 1024, wo_[j] + q * 16);
     };
     auto advance = [&]() {
         q += 8;

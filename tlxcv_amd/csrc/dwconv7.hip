@@ -18,7 +18,7 @@
 //   reduce   thread p < TH * TW adds the parked pairs of pixel p in chunk order to the running pair it keeps in registers.
 // After the last block thread p writes pixel p's pair.  Every sum has a fixed order: two launches give the same bits.
 // Resource usage (profiles/convnext/dwconv7_resource_usage.txt): no scratch.
-#include "common.h"
+#include "kernel_util.h"
 
 namespace tlxmi {
 
@@ -36,25 +36,12 @@ struct Dw7Args {
     unsigned x_bytes, y_bytes;
 };
 
-static __device__ __forceinline__ float dw7_mix_lo(unsigned x2, unsigned w2, float acc) {
-    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x2), "v"(w2));
-    return acc;
-}
-static __device__ __forceinline__ float dw7_mix_hi(unsigned x2, unsigned w2, float acc) {
-    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x2), "v"(w2));
-    return acc;
-}
-template <int CTRL> static __device__ __forceinline__ float dw7_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-
 template <bool STATS>
 __global__ __launch_bounds__(256) void dwconv7_kernel(const Dw7Args a) {
-    constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x;
-    const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes);
 
     int b = (int)blockIdx.x;
     const int tw = b % a.tiles_w; b /= a.tiles_w;
@@ -87,8 +74,8 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const Dw7Args a) {
                 const int pr = pix / IW, pcx = pix - pr * IW;
                 const int gh = h0 - 3 + pr, gw = w0 - 3 + pcx;
                 const bool in = (unsigned)gh < (unsigned)a.H && (unsigned)gw < (unsigned)a.W;
-                const int off = in ? ((img + gh * a.W + gw) * a.x_ld + c0) * 2 + j * 16 : OOB;
-                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xsrd, off, 0, 0);
+                const int off = in ? ((img + gh * a.W + gw) * a.x_ld + c0) * 2 + j * 16 : BUF_OOB;
+                const u32x4 v = buf_load16(xsrd, off);
                 *reinterpret_cast<u32x4*>(smem + pix * pitch + j * 16) = v;
             }
         }
@@ -123,10 +110,10 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const Dw7Args a) {
 #pragma unroll
                         for (int o = 0; o < 4; ++o) {
                             const u32x2 v = xv[o + q], w2 = wt[r * 7 + q];
-                            acc[o][0] = dw7_mix_lo(v[0], w2[0], acc[o][0]);
-                            acc[o][1] = dw7_mix_hi(v[0], w2[0], acc[o][1]);
-                            acc[o][2] = dw7_mix_lo(v[1], w2[1], acc[o][2]);
-                            acc[o][3] = dw7_mix_hi(v[1], w2[1], acc[o][3]);
+                            acc[o][0] = fma_mix_lo(v[0], w2[0], acc[o][0]);
+                            acc[o][1] = fma_mix_hi(v[0], w2[0], acc[o][1]);
+                            acc[o][2] = fma_mix_lo(v[1], w2[1], acc[o][2]);
+                            acc[o][3] = fma_mix_hi(v[1], w2[1], acc[o][3]);
                         }
                     }
                 }
@@ -141,16 +128,16 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const Dw7Args a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) hv[e] = (half_t)v[e];
                     const bool in = gh < a.H && gw < a.W;
-                    const int yo = in ? ((img + gh * a.W + gw) * a.y_ld + c0 + chunk * 4) * 2 : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hv), ysrd, yo, 0, 0);
+                    const int yo = in ? ((img + gh * a.W + gw) * a.y_ld + c0 + chunk * 4) * 2 : BUF_OOB;
+                    buf_store8(ysrd, __builtin_bit_cast(u32x2, hv), yo);
                     if (STATS) {
                         float s1 = (v[0] + v[1]) + (v[2] + v[3]);
                         float s2 = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-                        s1 += dw7_dpp<0xB1>(s1);        // quad_perm [1, 0, 3, 2]: the neighbouring chunk (same slot: Q is even)
-                        s2 += dw7_dpp<0xB1>(s2);
+                        s1 += dpp<0xB1>(s1);        // quad_perm [1, 0, 3, 2]: the neighbouring chunk (same slot: Q is even)
+                        s2 += dpp<0xB1>(s2);
                         if (a.G == 4) {
-                            s1 += dw7_dpp<0x4E>(s1);    // quad_perm [2, 3, 0, 1]: chunks 4 k .. 4 k + 3 (every block is whole quads)
-                            s2 += dw7_dpp<0x4E>(s2);
+                            s1 += dpp<0x4E>(s1);    // quad_perm [2, 3, 0, 1]: chunks 4 k .. 4 k + 3 (every block is whole quads)
+                            s2 += dpp<0x4E>(s2);
                         }
                         if ((chunk & (a.G - 1)) == 0) red[(chunk / a.G) * Ppad + row * a.TW + col + o] = make_float2(s1, s2);
                     }

@@ -14,43 +14,11 @@
 //   fragment reads); applied on the DMA source side, where it is the same for every piece of a lane.
 //   Epilogue straight from registers: each lane owns 8 consecutive channels of a pixel per sub-tile
 //   pair (filter rows are permuted inside groups of 32 as in conv_igemm.hip), 16-byte non-temporal stores.
-#include "common.h"
+#include "kernel_util.h"
 #include "gemm256.h"
 #include <stdlib.h>
 
 namespace tlxmi {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-static __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t srd(const char* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, bytes, 0x00020000);
-}
-static __device__ __forceinline__ u32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-}
-static __device__ __forceinline__ void buf_store16_nt(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 2);
-}
-static __device__ __forceinline__ void buf_store16_wb(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 0);
-}
-
-template <typename T> struct Mma256;
-template <> struct Mma256<half_t> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, a), __builtin_bit_cast(half8v, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma256<float> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-        return c;
-    }
-};
 
 // BN = 256 with WGN = 4 (8 waves, ring of 4, one workgroup per CU) or BN = 128 with WGN = 2 (4 waves, ring
 // of 3 x 24 KiB, two independent workgroups per CU: their barriers drift apart and one's epilogue overlaps
@@ -62,7 +30,6 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
     constexpr int WM = 128, WN = 64, PI = WM / 16, CI = WN / 16;
     constexpr int STEP = (BM + BN) * 64;          // bytes per K step
     constexpr int XPW = (BM / 16) / NW, WPW = (BN / 16) / NW, DPS = XPW + WPW;   // DMA pieces per wave and step
-    constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int t = threadIdx.x, lane = t & 63;
@@ -86,7 +53,7 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
         tile_n = grp * a.gn + rem % gn_here;
     }
     const int bm0 = tile_m * BM, bn0 = tile_n * BN;
-    const __amdgpu_buffer_rsrc_t xsrd = srd(a.x, a.x_bytes), wsrd = srd(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.w, a.w_bytes);
 
     // loader: one piece = 16 rows x 64 B; lane l -> row (l>>2), LDS slot (l&3); wave w fills pieces w, w+8
     const int lr = lane >> 2;
@@ -95,7 +62,7 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
 #pragma unroll
     for (int i = 0; i < XPW; ++i) {
         const int m = bm0 + 16 * (wid + NW * i) + lr;
-        xo[i] = m < a.M ? m * a.x_ld * ES : OOB;
+        xo[i] = m < a.M ? m * a.x_ld * ES : BUF_OOB;
     }
 #pragma unroll
     for (int i = 0; i < WPW; ++i) {
@@ -106,11 +73,11 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
     int q = lchunk;   // chunk index along K of the next step to stage
     auto stage = [&](int slot) {
         char* b = smem + slot * STEP;
-        const int d = q < a.kchunks ? q * 16 : OOB;
+        const int d = q < a.kchunks ? q * 16 : BUF_OOB;
 #pragma unroll
-        for (int i = 0; i < XPW; ++i) dma16(xsrd, b + (wid + NW * i) * 1024, xo[i] + d);
+        for (int i = 0; i < XPW; ++i) buf_dma16(xsrd, b + (wid + NW * i) * 1024, xo[i] + d);
 #pragma unroll
-        for (int i = 0; i < WPW; ++i) dma16(wsrd, b + BM * 64 + (wid + NW * i) * 1024, wo[i] + q * 16);
+        for (int i = 0; i < WPW; ++i) buf_dma16(wsrd, b + BM * 64 + (wid + NW * i) * 1024, wo[i] + q * 16);
         q += 4;
     };
 
@@ -156,14 +123,14 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
 #pragma unroll
         for (int ci = 0; ci < CI; ++ci)
 #pragma unroll
-            for (int pi = 0; pi < PI; ++pi) acc[ci][pi] = Mma256<T>::run(wf[ci], xf[pi], acc[ci][pi]);
+            for (int pi = 0; pi < PI; ++pi) acc[ci][pi] = Mma<T>::run(wf[ci], xf[pi], acc[ci][pi]);
         slot = slot + 1 == NSLOT ? 0 : slot + 1;
     }
 
     // ---- epilogue from registers: lane (g, px) owns channels 32cp + 8g .. +7 of pixel 16pi + px
     const int g = lane >> 4, px = lane & 15;
     const bool res_after = (a.flags & TLXMI_EPI_RES_AFTER_ACT) != 0;
-    const __amdgpu_buffer_rsrc_t ysrd = srd(a.y, a.y_bytes), rsrd = srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes), rsrd = buf_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
     auto epi = [&](auto act_tag) {
     constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
@@ -183,7 +150,7 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
 #pragma unroll
             for (int pi = 0; pi < PI; ++pi) {
                 const int m = bm0 + wave_m0 + pi * 16 + px;
-                const int ro = m < a.M ? (m * a.res_ld + ch0) * ES : OOB;
+                const int ro = m < a.M ? (m * a.res_ld + ch0) * ES : BUF_OOB;
 #pragma unroll
                 for (int hh = 0; hh < ES / 2; ++hh) rr[pi][hh] = buf_load16(rsrd, ro + 16 * hh);
             }
@@ -227,21 +194,21 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] += rv[e];
             }
-            const int yo = m < a.M ? (m * a.y_ld + ch0) * ES : OOB;   // OOB stores are dropped by the range check
+            const int yo = m < a.M ? (m * a.y_ld + ch0) * ES : BUF_OOB;   // BUF_OOB stores are dropped by the range check
             if constexpr (ES == 2) {
                 half8v h;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) h[e] = (half_t)v[e];
-                if (!TLXMI_NT_STORES(a)) buf_store16_wb(ysrd, __builtin_bit_cast(u32x4, h), yo);
-                else buf_store16_nt(ysrd, __builtin_bit_cast(u32x4, h), yo);
+                if (!TLXMI_NT_STORES(a)) buf_store16<BUF_WB>(ysrd, __builtin_bit_cast(u32x4, h), yo);
+                else buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, h), yo);
             } else {
                 f32x4 f0, f1;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { f0[e] = v[e]; f1[e] = v[4 + e]; }
-                if (!TLXMI_NT_STORES(a)) buf_store16_wb(ysrd, __builtin_bit_cast(u32x4, f0), yo);
-                else buf_store16_nt(ysrd, __builtin_bit_cast(u32x4, f0), yo);
-                if (!TLXMI_NT_STORES(a)) buf_store16_wb(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
-                else buf_store16_nt(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
+                if (!TLXMI_NT_STORES(a)) buf_store16<BUF_WB>(ysrd, __builtin_bit_cast(u32x4, f0), yo);
+                else buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, f0), yo);
+                if (!TLXMI_NT_STORES(a)) buf_store16<BUF_WB>(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
+                else buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
             }
         }
     }

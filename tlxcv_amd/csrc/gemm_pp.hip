@@ -21,43 +21,11 @@
 // exactly the half tiles the NEXT phase reads (the wait sits before a barrier every wave passes before
 // that read).  K tiles past the end are fetched at an out-of-range descriptor offset (zero fill, no
 // memory traffic), which keeps the counts uniform to the last phase.
-#include "common.h"
+#include "kernel_util.h"
 #include "gemm256.h"
 #include <stdlib.h>
 
 namespace tlxmi {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_pp_t;
-static __device__ __forceinline__ void pp_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_pp_t)lds, 16, voff, 0, 0, 0);
-}
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t pp_srd(const char* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, bytes, 0x00020000);
-}
-static __device__ __forceinline__ u32x4 pp_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-}
-static __device__ __forceinline__ void pp_store16_nt(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 2);
-}
-static __device__ __forceinline__ void pp_store16_wb(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 0);
-}
-
-template <typename T> struct MmaPP;
-template <> struct MmaPP<half_t> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, a), __builtin_bit_cast(half8v, b), c, 0, 0, 0);
-    }
-};
-template <> struct MmaPP<float> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-        return c;
-    }
-};
 
 // HM = X half tiles per K tile: 2 -> the 256 x 256 tile described above; 1 -> a 128 x 256 tile (tails: a launch
 // whose last round would hold fewer than half the CUs runs those rows as twice as many half-height tiles).
@@ -92,7 +60,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
     constexpr int RX0 = 0, RX1 = HALF, RW0 = HM * HALF, RW1 = (HM + 1) * HALF;   // regions of a K tile (RX1: HM == 2, RW1: HN == 2)
     constexpr int KTB = (HM + HN) * HALF;      // bytes of a K tile
     constexpr int NBUF = (HM + HN == 4) ? 2 : 3;   // resident K tiles
-    constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int t = threadIdx.x, lane = t & 63;
@@ -116,8 +83,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
     const int slice = a.kslices > 1 ? (int)blockIdx.x / (a.mtiles * a.ntiles) : 0;
     const int kt0 = slice * a.kt_slice;
     const int ks = a.kslices > 1 ? (a.ksteps - kt0 < a.kt_slice ? a.ksteps - kt0 : a.kt_slice) : a.ksteps;
-    const __amdgpu_buffer_rsrc_t xsrd = pp_srd(a.x, a.x_bytes), wsrd = pp_srd(a.w, a.w_bytes);
-    const __amdgpu_buffer_rsrc_t x2srd = DUAL ? pp_srd(a.x2, a.x2_bytes) : xsrd;
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t x2srd = DUAL ? buf_srd(a.x2, a.x2_bytes) : xsrd;
 
     // ---- loader: a piece = 8 rows x 128 B (one wave instruction); wave w fills pieces w and w+8 of a half
     // tile; lane l -> row 8*piece + (l>>3), slot (l&7).  (row>>1)&7 = (4*(w&1) + (l>>4)) & 7 for both pieces.
@@ -149,7 +116,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
                 }
                 tapmask[h][j] = mk;
             } else {
-                xo[h][j] = (h < HM && m < a.M) ? m * a.x_ld * ES : OOB;
+                xo[h][j] = (h < HM && m < a.M) ? m * a.x_ld * ES : BUF_OOB;
                 tapmask[h][j] = 0;
             }
             if constexpr (DUAL) {
@@ -158,7 +125,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
                 const int n = mm / a.dHoWo, rem = mm - n * a.dHoWo;
                 const int ho = rem / a.dWo, wo_ = rem - ho * a.dWo;
                 // (a live row's pixel lies inside x2: its byte offset is below a.x2_bytes < 2^31)
-                xo2[h][j] = live ? ((n * a.dH2 + ho * a.ds) * a.dW2 + wo_ * a.ds) * a.x2_ld * ES : OOB;
+                xo2[h][j] = live ? ((n * a.dH2 + ho * a.ds) * a.dW2 + wo_ * a.ds) * a.x2_ld * ES : BUF_OOB;
             }
             const int rho = 128 * h + 8 * (wid + 8 * j) + lrow;    // LDS row; holds channel perm(rho) (conv_igemm.hip)
             const int n = (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3);
@@ -175,23 +142,23 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
             const int r = (tap * 11) >> 5, s_ = tap - 3 * r;       // tap / 3 for tap <= 8
             const int d = (DIL ? r * a.cdh * a.cW + s_ * a.cdw : r * a.cW + s_) * a.x_ld * ES + (((kt - (tap << a.ctshift)) * 8 + lc) << 4);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) pp_dma16(xsrd, b + j * 8192, (mine && ((tapmask[h][j] >> tap) & 1u)) ? xo[h][j] + d : OOB);
+            for (int j = 0; j < 2; ++j) buf_dma16(xsrd, b + j * 8192, (mine && ((tapmask[h][j] >> tap) & 1u)) ? xo[h][j] + d : BUF_OOB);
         } else if constexpr (DUAL) {
             if (kt < a.k1_tiles) {                                 // wave-uniform
                 const int q = kt * 8 + lc;
 #pragma unroll
-                for (int j = 0; j < 2; ++j) pp_dma16(xsrd, b + j * 8192, mine ? xo[h][j] + q * 16 : OOB);
+                for (int j = 0; j < 2; ++j) buf_dma16(xsrd, b + j * 8192, mine ? xo[h][j] + q * 16 : BUF_OOB);
             } else {
                 const int q = (kt - a.k1_tiles) * 8 + lc;
                 const bool in = mine && kt < a.k1_tiles + a.k2_tiles;
 #pragma unroll
-                for (int j = 0; j < 2; ++j) pp_dma16(x2srd, b + j * 8192, in ? xo2[h][j] + q * 16 : OOB);
+                for (int j = 0; j < 2; ++j) buf_dma16(x2srd, b + j * 8192, in ? xo2[h][j] + q * 16 : BUF_OOB);
             }
         } else {
             const int q = kt * 8 + lc;
             const bool in = mine && q < a.kchunks;
 #pragma unroll
-            for (int j = 0; j < 2; ++j) pp_dma16(xsrd, b + j * 8192, in ? xo[h][j] + q * 16 : OOB);
+            for (int j = 0; j < 2; ++j) buf_dma16(xsrd, b + j * 8192, in ? xo[h][j] + q * 16 : BUF_OOB);
         }
     };
     auto stage_w = [&](int g, int kt, int buf) {
@@ -199,7 +166,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
         char* b = lbase + buf * KTB + (g ? RW1 : RW0);
         const bool in = kt < ks && q * 16 < a.Kp_bytes;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) pp_dma16(wsrd, b + j * 8192, in ? wo[g][j] + q * 16 : OOB);
+        for (int j = 0; j < 2; ++j) buf_dma16(wsrd, b + j * 8192, in ? wo[g][j] + q * 16 : BUF_OOB);
     };
 
     // ---- fragment reads: lane (frow, fg) reads row frow of a 16-row sub-tile, 16-byte chunk 4*ksub + fg
@@ -235,7 +202,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                             \
         _Pragma("unroll") for (int pi = 0; pi < 4; ++pi)                                             \
         _Pragma("unroll") for (int ci = 0; ci < 2; ++ci)                                             \
-            acc[2 * (G) + ci][4 * (H) + pi] = MmaPP<T>::run(WF[ci][ks], xf[pi][ks], acc[2 * (G) + ci][4 * (H) + pi]); \
+            acc[2 * (G) + ci][4 * (H) + pi] = Mma<T>::run(WF[ci][ks], xf[pi][ks], acc[2 * (G) + ci][4 * (H) + pi]); \
         __builtin_amdgcn_s_setprio(0);                                                               \
     }
 #define TLXMI_PP_SYNC()                       \
@@ -375,7 +342,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
     // 128h + 64wr + 16pi + px (the filter rows are permuted so that two MFMA sub-tiles give 8 neighbours)
     const int px = lane & 15;
     if (a.kslices > 1) {      // split K: the accumulators as they are, fp32, to this slice's [M][y_ld] plane
-        const __amdgpu_buffer_rsrc_t psrd = pp_srd(a.y + (long long)slice * a.slice_bytes, (unsigned)a.slice_bytes);
+        const __amdgpu_buffer_rsrc_t psrd = buf_srd(a.y + (long long)slice * a.slice_bytes, (unsigned)a.slice_bytes);
 #pragma unroll
         for (int g = 0; g < HN; ++g) {
             const int ch0 = bn0 + 128 * g + 32 * wc + 8 * fg;
@@ -384,15 +351,15 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
 #pragma unroll
                 for (int pi = 0; pi < 4; ++pi) {
                     const int m = bm0 + 128 * h + 64 * wr + prow(pi) * 16 + px;
-                    const int yo = (m < a.M && ch0 < a.Cout) ? (m * a.y_ld + ch0) * 4 : OOB;
-                    pp_store16_wb(psrd, __builtin_bit_cast(u32x4, acc[2 * g][4 * h + pi]), yo);
-                    pp_store16_wb(psrd, __builtin_bit_cast(u32x4, acc[2 * g + 1][4 * h + pi]), yo + 16);
+                    const int yo = (m < a.M && ch0 < a.Cout) ? (m * a.y_ld + ch0) * 4 : BUF_OOB;
+                    buf_store16<BUF_WB>(psrd, __builtin_bit_cast(u32x4, acc[2 * g][4 * h + pi]), yo);
+                    buf_store16<BUF_WB>(psrd, __builtin_bit_cast(u32x4, acc[2 * g + 1][4 * h + pi]), yo + 16);
                 }
         }
         return;
     }
     const bool res_after = (a.flags & TLXMI_EPI_RES_AFTER_ACT) != 0;
-    const __amdgpu_buffer_rsrc_t ysrd = pp_srd(a.y, a.y_bytes), rsrd = pp_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes), rsrd = buf_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
     auto epi = [&](auto act_tag) {
         constexpr int ACT = decltype(act_tag)::value;
         float hs_[HM], hq_[HM];      // LNF producer: this wave's (sum, sum^2) of row 128 h + 64 wr + lane over its channels of both column halves
@@ -417,9 +384,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
 #pragma unroll
                     for (int pi = 0; pi < 4; ++pi) {
                         const int m = bm0 + 128 * h + 64 * wr + prow(pi) * 16 + px;
-                        const int ro = m < a.M ? (m * a.res_ld + ch0) * ES : OOB;
+                        const int ro = m < a.M ? (m * a.res_ld + ch0) * ES : BUF_OOB;
 #pragma unroll
-                        for (int hh = 0; hh < ES / 2; ++hh) rr[pi][hh] = pp_load16(rsrd, ro + 16 * hh);
+                        for (int hh = 0; hh < ES / 2; ++hh) rr[pi][hh] = buf_load16(rsrd, ro + 16 * hh);
                     }
                 }
                 f32x2 rab[4];
@@ -500,21 +467,21 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const Gemm256Args a) {
                         st_s[pi] = ss;
                         st_q[pi] = qq;
                     }
-                    const int yo = m < a.M ? (m * a.y_ld + ch0) * ES : OOB;   // OOB stores are dropped by the range check
+                    const int yo = m < a.M ? (m * a.y_ld + ch0) * ES : BUF_OOB;   // BUF_OOB stores are dropped by the range check
                     if constexpr (ES == 2) {
                         half8v hv;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) hv[e] = (half_t)v[e];
-                        if (CONV || !TLXMI_NT_STORES(a)) pp_store16_wb(ysrd, __builtin_bit_cast(u32x4, hv), yo);
-                        else pp_store16_nt(ysrd, __builtin_bit_cast(u32x4, hv), yo);
+                        if (CONV || !TLXMI_NT_STORES(a)) buf_store16<BUF_WB>(ysrd, __builtin_bit_cast(u32x4, hv), yo);
+                        else buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, hv), yo);
                     } else {
                         f32x4 f0, f1;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { f0[e] = v[e]; f1[e] = v[4 + e]; }
-                        if (CONV || !TLXMI_NT_STORES(a)) pp_store16_wb(ysrd, __builtin_bit_cast(u32x4, f0), yo);
-                        else pp_store16_nt(ysrd, __builtin_bit_cast(u32x4, f0), yo);
-                        if (CONV || !TLXMI_NT_STORES(a)) pp_store16_wb(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
-                        else pp_store16_nt(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
+                        if (CONV || !TLXMI_NT_STORES(a)) buf_store16<BUF_WB>(ysrd, __builtin_bit_cast(u32x4, f0), yo);
+                        else buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, f0), yo);
+                        if (CONV || !TLXMI_NT_STORES(a)) buf_store16<BUF_WB>(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
+                        else buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
                     }
                 }
                 if constexpr (LNF) {

@@ -48,52 +48,15 @@
 //     p0(L+2) ...                              wait W1(L+2)        : 8      (waits for S10 too: 8 + S would do)
 // (a count = number of operations issued after the target; counts above 63 are clamped, which only waits
 // for more).  A K tile that issues residual loads (R = 2 for fp16) at p0 uses 8 + R in its waits.
-#include "common.h"
+#include "kernel_util.h"
 #include "gemm256.h"
 #include <stdlib.h>
 
 namespace tlxmi {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_gs_t;
-static __device__ __forceinline__ void gs_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_gs_t)lds, 16, voff, 0, 0, 0);
-}
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t gs_srd(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-static __device__ __forceinline__ u32x4 gs_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-}
-static __device__ __forceinline__ void gs_store16_nt(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 2);
-}
-static __device__ __forceinline__ void gs_store16_wb(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 0);
-}
-
 __device__ __attribute__((aligned(16))) float g_ones4[4] = {1.f, 1.f, 1.f, 1.f};
 
-template <typename T> struct MmaGS;
-template <> struct MmaGS<half_t> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, a), __builtin_bit_cast(half8v, b), c, 0, 0, 0);
-    }
-};
-template <> struct MmaGS<float> {
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-        return c;
-    }
-};
-
 enum { GS_K0_FIRST = 0, GS_K0_AFTER, GS_INTERIOR, GS_LAST, GS_R0, GS_RC = GS_R0 + 8 };   // GS_R0 + r: residual step r
-
-template <int N> __device__ __forceinline__ void gs_vmcnt() {
-    constexpr int C = N > 63 ? 63 : N;
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C) : "memory");
-}
 
 // ACT: TLXMI_ACT_NONE / RELU / GELU (other activations, and exact-erf GELU in fp32, stay on gemm_pp.hip).
 // RES: a.res is added (before the activation; a.scale must be null) — needs >= 11 K tiles.
@@ -119,7 +82,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
     constexpr int HALF = 128 * 128;            // bytes of a half tile
     constexpr int RX0 = 0, RX1 = HALF, RW0 = 2 * HALF, RW1 = 3 * HALF;   // regions of a K tile
     constexpr int TABLE = 8 * HALF;            // two tables of 8 x 256 B behind the two K tiles
-    constexpr int OOB = (int)0x80000000;
+    constexpr int OOB = BUF_OOB;               // a local copy on purpose: with the namespace-scope constant hipcc numbers this kernel's registers differently
     constexpr int ROWTAB = TABLE + 2 * 2048;   // ROWAFF: two tables of 4 planes x 256 rows x (sum, sum^2) behind the channel tables
     constexpr int STATSCR = TABLE + 2 * 2048;  // STATS (never with ROWAFF): [H][G][wr][wc][64 lanes] x (sum, sum^2), 16 KB
     constexpr int SY = ES == 2 ? 4 : 8;        // 16-byte stores of a quadrant's outputs
@@ -152,13 +115,13 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         return true;
     };
 
-    const __amdgpu_buffer_rsrc_t xsrd = gs_srd(a.x, a.x_bytes), wsrd = gs_srd(a.w, a.w_bytes);
-    const __amdgpu_buffer_rsrc_t ysrd = gs_srd(a.y, a.y_bytes);
-    const __amdgpu_buffer_rsrc_t rsrd = gs_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
-    const __amdgpu_buffer_rsrc_t hsrd = gs_srd(a.shift, a.shift ? (unsigned)a.Cout * 4u : 0u);   // null: zero fill
-    const __amdgpu_buffer_rsrc_t ssrd = a.scale ? gs_srd(a.scale, (unsigned)a.Cout * 4u) : gs_srd(g_ones4, 16u);
-    const __amdgpu_buffer_rsrc_t rowsrd = gs_srd(a.rowstats, (ROWAFF && a.rowstats) ? (unsigned)a.M * 32u : 0u);   // [M][4 planes][2]; null: zero fill
-    const __amdgpu_buffer_rsrc_t stsrd = gs_srd(a.stats_out, (STATS && a.stats_out) ? (unsigned)a.M * 32u : 0u);   // [M][4 planes][2]; null: dropped
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrd = buf_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t hsrd = buf_srd(a.shift, a.shift ? (unsigned)a.Cout * 4u : 0u);   // null: zero fill
+    const __amdgpu_buffer_rsrc_t ssrd = a.scale ? buf_srd(a.scale, (unsigned)a.Cout * 4u) : buf_srd(g_ones4, 16u);
+    const __amdgpu_buffer_rsrc_t rowsrd = buf_srd(a.rowstats, (ROWAFF && a.rowstats) ? (unsigned)a.M * 32u : 0u);   // [M][4 planes][2]; null: zero fill
+    const __amdgpu_buffer_rsrc_t stsrd = buf_srd(a.stats_out, (STATS && a.stats_out) ? (unsigned)a.M * 32u : 0u);   // [M][4 planes][2]; null: dropped
 
     // ---- loader (gemm_pp.hip): piece = 8 rows x 128 B; wave w fills pieces w, w+8 of a half tile
     const int lrow = lane >> 3;
@@ -184,15 +147,15 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         const int q = kt * 8 + lc;
         const int off = (q < a.kchunks && xo >= 0) ? xo + q * 16 : OOB;
         char* b = lbase + (par << 16) + region;
-        gs_dma16(xsrd, b, off);
-        gs_dma16(xsrd, b + 8192, off >= 0 ? off + x64 : OOB);
+        buf_dma16(xsrd, b, off);
+        buf_dma16(xsrd, b + 8192, off >= 0 ? off + x64 : OOB);
     };
     auto dma_w = [&](int region, int par, int wo, int kt) {
         const int q = kt * 8 + lc;
         const int off = (q * 16 < a.Kp_bytes && wo >= 0) ? wo + q * 16 : OOB;
         char* b = lbase + (par << 16) + region;
-        gs_dma16(wsrd, b, off);
-        gs_dma16(wsrd, b + 8192, off >= 0 ? off + w64 : OOB);
+        buf_dma16(wsrd, b, off);
+        buf_dma16(wsrd, b + 8192, off >= 0 ? off + w64 : OOB);
     };
     // scale / shift table of tile i -> table (i & 1): wave w brings channels 32w..32w+31, [shift 32][scale 32]
     auto dma_table = [&](int i) {
@@ -203,12 +166,12 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         const int lane = lane_now();
         if (lane < 8) {
             const int off = ok ? (bn0 + 32 * wid + 4 * lane) * 4 : OOB;
-            gs_dma16(hsrd, dst, off);
-            gs_dma16(ssrd, dst + 128, a.scale ? off : 0);
+            buf_dma16(hsrd, dst, off);
+            buf_dma16(ssrd, dst + 128, a.scale ? off : 0);
         }
         // ROWAFF: the statistics of rows 32w .. 32w+31 of the tile, [row][4 planes][2] = 32 bytes a row, ONE contiguous kilobyte per wave
         // (rows past M: zero fill; planes past ln_planes were never written and are left out by rowab_convert)
-        if constexpr (ROWAFF) gs_dma16(rowsrd, smem + ROWTAB + (i & 1) * 8192 + wid * 1024, ok ? (bm0 + 32 * wid) * 32 + lane * 16 : OOB);
+        if constexpr (ROWAFF) buf_dma16(rowsrd, smem + ROWTAB + (i & 1) * 8192 + wid * 1024, ok ? (bm0 + 32 * wid) * 32 + lane * 16 : OOB);
     };
 
     // ---- fragment reads (gemm_pp.hip)
@@ -237,7 +200,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
     // the S stores of a quadrant that does not exist (H = 1 of a half-height tile), dropped by the range check: the counts stay
     auto dead_stores = [&]() {
 #pragma unroll
-        for (int q = 0; q < SY; ++q) gs_store16_wb(ysrd, u32x4{0u, 0u, 0u, 0u}, OOB);
+        for (int q = 0; q < SY; ++q) buf_store16<BUF_WB>(ysrd, u32x4{0u, 0u, 0u, 0u}, OOB);
     };
 
     // ROWAFF: the (a, b) pairs of this lane's four rows (sub-tiles pi = 0..3 of half h) are read from the row table in the LOAD segment of
@@ -250,7 +213,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         if constexpr (ROWAFF) {
             // row r of the tile lives at (r / 32) * 1024 + (r % 32) * 32 (rowab_convert): rows 128 h + 64 wr + 16 pi + px -> offsets 0, 512, 1024, 1536
             const int ln = lane_now();
-            const unsigned la = (unsigned)(uintptr_t)(lds_ptr_gs_t)(smem + ROWTAB + tpar * 8192 + (4 * h + 2 * wr) * 1024 + (ln & 15) * 32);
+            const unsigned la = (unsigned)(uintptr_t)(lds_ptr_t)(smem + ROWTAB + tpar * 8192 + (4 * h + 2 * wr) * 1024 + (ln & 15) * 32);
             asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %4 offset:512\n\tds_read_b64 %2, %4 offset:1024\n\tds_read_b64 %3, %4 offset:1536\n\t"
                          "s_waitcnt lgkmcnt(0)"
                          : "=&v"(rab[0]), "=&v"(rab[1]), "=&v"(rab[2]), "=&v"(rab[3])
@@ -266,7 +229,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         if constexpr (ROWAFF) {
             const int ln = lane_now();
             if (ln < 32) {
-                const unsigned la = (unsigned)(uintptr_t)(lds_ptr_gs_t)(smem + ROWTAB + tpar * 8192 + wid * 1024 + ln * 32);
+                const unsigned la = (unsigned)(uintptr_t)(lds_ptr_t)(smem + ROWTAB + tpar * 8192 + wid * 1024 + ln * 32);
                 f32x4 t01, t23;
                 asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)" : "=&v"(t01), "=&v"(t23) : "v"(la) : "memory");
                 const int np = a.ln_planes;
@@ -292,7 +255,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
     auto stats_stage2 = [&](int hp, int sbm, int sbn, bool pend) {
         if constexpr (STATS) {
             const int ln = lane_now();
-            const unsigned la = (unsigned)(uintptr_t)(lds_ptr_gs_t)(smem + STATSCR + hp * 8192 + wr * 2048 + ln * 8);
+            const unsigned la = (unsigned)(uintptr_t)(lds_ptr_t)(smem + STATSCR + hp * 8192 + wr * 2048 + ln * 8);
             // (all eight pairs in flight: ONE LDS round trip in this load segment — four blocks of two cost the producers 6 %)
             f32x2 p0, p1, p2, p3, p4, p5, p6, p7;
             asm volatile("ds_read_b64 %0, %8\n\tds_read_b64 %1, %8 offset:512\n\tds_read_b64 %2, %8 offset:1024\n\tds_read_b64 %3, %8 offset:1536\n\t"
@@ -306,7 +269,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
             const int m = sbm + 128 * hp + 64 * wr + ln;
             const int okm = (pend && wc == 0) ? ((m - a.M) >> 31) : 0;
             const int so = (((m * 4 + (sbn >> 8)) * 8) & okm) | (OOB & ~okm);
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2{__builtin_bit_cast(unsigned, s4), __builtin_bit_cast(unsigned, q4)}, stsrd, so, 0, 0);
+            buf_store8(stsrd, u32x2{__builtin_bit_cast(unsigned, s4), __builtin_bit_cast(unsigned, q4)}, so);
         }
     };
 
@@ -323,7 +286,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         const int chm = (live && !GS_DBG(a, 2)) ? ((ch0 - a.Cout) >> 31) : 0;      // -1: a real channel (Cout is a multiple of 8 on this path)
         if GS_DBG(a, 1) {   // ablation: stores without the arithmetic
 #pragma unroll
-            for (int pi = 0; pi < S; ++pi) gs_store16_nt(ysrd, __builtin_bit_cast(u32x4, acc[2 * G][4 * H + (pi & 3)]), OOB);
+            for (int pi = 0; pi < S; ++pi) buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, acc[2 * G][4 * H + (pi & 3)]), OOB);
             return;
         }
         const float* tb = reinterpret_cast<const float*>(smem + TABLE + tpar * 2048 + (4 * G + wc) * 256) + 8 * fg;
@@ -385,14 +348,14 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
                 half8v hv;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) hv[e] = (half_t)v[e];
-                if (!GS_DBG(a, 4)) gs_store16_wb(ysrd, __builtin_bit_cast(u32x4, hv), yo);      // (bit 4, A/B: non-temporal)
-                else gs_store16_nt(ysrd, __builtin_bit_cast(u32x4, hv), yo);
+                if (!GS_DBG(a, 4)) buf_store16<BUF_WB>(ysrd, __builtin_bit_cast(u32x4, hv), yo);      // (bit 4, A/B: non-temporal)
+                else buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, hv), yo);
             } else {
                 f32x4 f0, f1;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { f0[e] = v[e]; f1[e] = v[4 + e]; }
-                gs_store16_nt(ysrd, __builtin_bit_cast(u32x4, f0), yo);
-                gs_store16_nt(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
+                buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, f0), yo);
+                buf_store16<BUF_NT>(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
             }
         }
         if constexpr (STATS) {
@@ -406,7 +369,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
             // stage-2 store of the half completed one epilogue ago, issued by the load segment of this same phase (stats_stage2)
             // (visible to the other waves from the barrier behind this segment: GS_SYNC_E waits for lgkmcnt(0) in front of it)
             *reinterpret_cast<f32x2*>(smem + STATSCR + H * 8192 + G * 4096 + wr * 2048 + wc * 512 + ln * 8) = f32x2{ts, tq};
-            if constexpr (H != G) __builtin_amdgcn_raw_buffer_store_b64(u32x2{0u, 0u}, stsrd, OOB, 0, 0);
+            if constexpr (H != G) buf_store8(stsrd, u32x2{0u, 0u}, OOB);
         }
     };
     // Residual step r = 0..7 covers quadrant (r>>1) in the phase order (0,0) (0,1) (1,1) (1,0), pixel sub-tiles
@@ -422,7 +385,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
             const int okm = (H == 1 && thalf) ? 0 : (((m - a.M) & (ch0 - a.Cout)) >> 31);      // (H = 1 of a half-height tile: zeros)
             const int ro = (((m * a.res_ld + ch0) * ES) & okm) | (OOB & ~okm);
 #pragma unroll
-            for (int hh = 0; hh < ES / 2; ++hh) rr[p * (ES / 2) + hh] = gs_load16(rsrd, ro + 16 * hh);
+            for (int hh = 0; hh < ES / 2; ++hh) rr[p * (ES / 2) + hh] = buf_load16(rsrd, ro + 16 * hh);
         }
     };
     auto res_add = [&](auto r_tag) {
@@ -466,11 +429,11 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         __builtin_amdgcn_s_setprio(1);                                                                      \
         _Pragma("unroll") for (int pi = 0; pi < 4; ++pi)                                                    \
         _Pragma("unroll") for (int ci = 0; ci < 2; ++ci)                                                    \
-            acc[2 * G + ci][4 * H + pi] = MmaGS<T>::run(WF[ci][0], xf[pi][0],                               \
-                                                        (ZERO) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[2 * G + ci][4 * H + pi]); \
+            acc[2 * G + ci][4 * H + pi] = Mma<T>::run(WF[ci][0], xf[pi][0],                                 \
+                                                      (ZERO) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[2 * G + ci][4 * H + pi]); \
         _Pragma("unroll") for (int pi = 0; pi < 4; ++pi)                                                    \
         _Pragma("unroll") for (int ci = 0; ci < 2; ++ci)                                                    \
-            acc[2 * G + ci][4 * H + pi] = MmaGS<T>::run(WF[ci][1], xf[pi][1], acc[2 * G + ci][4 * H + pi]); \
+            acc[2 * G + ci][4 * H + pi] = Mma<T>::run(WF[ci][1], xf[pi][1], acc[2 * G + ci][4 * H + pi]);   \
         EPI;                                                                                                \
         _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                                    \
             __builtin_amdgcn_sched_group_barrier(0x008, sizeof(T) == 2 ? 1 : 4, 0);                         \
@@ -505,10 +468,9 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
     dma_x(RX0, 1, xb, 1);
     dma_w(RW0, 1, wb, 1);
     if (ks == 2) { ktb = 0; ib = 1; set_rows(1, 0, xb, wb); }
-    gs_vmcnt<8>();
+    wait_vmcnt<8>();
     GS_SYNC();
     if (wr == 1) { GS_SYNC(); }   // group 1 runs one barrier behind
-
 
     // HF: the tile is half-height (compile time: a run-time test around the MFMA blocks makes the register allocator split the
     // accumulators' live ranges at every join — 80 - 120 spilled registers; a half-height tile is always a workgroup's last)
@@ -529,7 +491,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
             res_load(IntTag<MODE - GS_R0>{}, bm0, bn0, HF);
         }
         dma_w(RW1, para, wa, kta);
-        gs_vmcnt<(MODE == GS_K0_AFTER ? 8 + 3 * S + TT : 8 + RQ)>();
+        wait_vmcnt<(MODE == GS_K0_AFTER ? 8 + 3 * S + TT : 8 + RQ)>();
         GS_SYNC();
         if constexpr (MODE == GS_K0_AFTER) { GS_MMA_E(0, 0, w0f, K0, epi(IntTag<1>{}, IntTag<0>{}, pbm0, pbn0, (i - 1) & 1, true)); }      // (the tile before is never half-height)
         else { GS_MMA(0, 0, w0f, K0); }
@@ -540,7 +502,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         dma_x(RX1, para, xa, kta);
         if constexpr (MODE == GS_LAST) stats_stage2(1, pbm0, pbn0, have_prev);      // half 1 of the tile before (completed by its E10): E00's extra store
         adv_a();
-        gs_vmcnt<(MODE == GS_K0_AFTER ? 8 + 4 * S + TT : 8 + RQ)>();
+        wait_vmcnt<(MODE == GS_K0_AFTER ? 8 + 4 * S + TT : 8 + RQ)>();
         GS_SYNC();
         if constexpr (MODE == GS_LAST) { GS_MMA_E(0, 1, w1f, K0, epi(IntTag<0>{}, IntTag<0>{}, bm0, bn0, i & 1, true)); }
         else { GS_MMA(0, 1, w1f, K0); }
@@ -562,7 +524,7 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(const Gemm256Args a) {
         dma_w(RW0, parb, wb, ktb);
         if constexpr (MODE == GS_LAST) stats_stage2(0, bm0, bn0, true);      // half 0 of this tile (completed by E01): E11's extra store (also of a half-height tile)
         adv_b();
-        gs_vmcnt<(MODE == GS_K0_AFTER ? 8 + 2 * S : MODE == GS_LAST ? 8 + 2 * S + TT : 8 + RQ)>();
+        wait_vmcnt<(MODE == GS_K0_AFTER ? 8 + 2 * S : MODE == GS_LAST ? 8 + 2 * S + TT : 8 + RQ)>();
         GS_SYNC();
         if constexpr (!HF) {
             if constexpr (MODE == GS_LAST) { GS_MMA_E(1, 0, w0f, K0, epi(IntTag<1>{}, IntTag<1>{}, bm0, bn0, i & 1, true)); }

@@ -26,49 +26,12 @@
 // i.e. a buffer is refilled right after the barrier behind its last read, and a piece is in flight for >= one k-step
 // (>= 1000 cycles) + the rest of the k-step it was issued in before anybody waits for it.  The K-tile stream runs across
 // output tiles (DMA cursor = compute position + 2), K tiles past the end are fetched at an out-of-range offset (zero fill).
-#include "common.h"
+#include "kernel_util.h"
 #include "gemm256.h"
 
 namespace tlxmi {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_w4_t;
-static __device__ __forceinline__ void w4_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_w4_t)lds, 16, voff, 0, 0, 0);
-}
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t w4_srd(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-static __device__ __forceinline__ u32x4 w4_load16(__amdgpu_buffer_rsrc_t rsrc, int voff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-}
-// POL: cache policy bits of the store (gfx950: 1 = sc0, 2 = nt, 16 = sc1)
-template <int POL> static __device__ __forceinline__ void w4_store16(__amdgpu_buffer_rsrc_t rsrc, u32x4 v, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, POL);
-}
-
 __device__ __attribute__((aligned(16))) float g_w4_ones[4] = {1.f, 1.f, 1.f, 1.f};
-
-template <typename T> struct MmaW4;
-template <> struct MmaW4<half_t> {
-    static constexpr int N = 1;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, a), __builtin_bit_cast(half8v, b), c, 0, 0, 0);
-    }
-};
-template <> struct MmaW4<float> {
-    static constexpr int N = 4;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-        return c;
-    }
-};
-
-template <int N> __device__ __forceinline__ void w4_vmcnt() {
-    constexpr int C = N > 63 ? 63 : N;
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C) : "memory");
-}
 
 // ACT: compile-time activation (TLXMI_ACT_*; GELU in fp16 = gelu_fast2, in fp32 = erff).  RES: a.res added before the activation.
 // DBG (tuning flavour only, timing ablations; results are wrong): 1 no LDS-DMA in the loop, 2 no fragment reads in the loop, 4 no
@@ -77,9 +40,8 @@ template <typename T, int ACT, bool RES, int DBG = 0>
 __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
     constexpr int ES = (int)sizeof(T);
     constexpr int XR = 0, WR = 32768, KTB = 65536;      // regions of a K tile, bytes of a K tile
-    constexpr int OOB = (int)0x80000000;
     constexpr int SPT = 32 * (ES / 2);                  // 16-byte stores of a wave's tile per lane
-    constexpr int MPF = MmaW4<T>::N;                    // MFMA instructions per fragment pair
+    constexpr int MPF = Mma<T>::N;                      // MFMA instructions per fragment pair
     constexpr int STP = (DBG & 64 ? 16 : 0) | (DBG & 128 ? 2 : 0) | (DBG & 256 ? 1 : 0);      // store policy under test
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -102,11 +64,11 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
         return true;
     };
 
-    const __amdgpu_buffer_rsrc_t xsrd = w4_srd(a.x, a.x_bytes), wsrd = w4_srd(a.w, a.w_bytes);
-    const __amdgpu_buffer_rsrc_t ysrd = w4_srd(a.y, a.y_bytes);
-    const __amdgpu_buffer_rsrc_t rsrd = w4_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
-    const __amdgpu_buffer_rsrc_t hsrd = w4_srd(a.shift, a.shift ? (unsigned)a.Cout * 4u : 0u);      // null: zero fill
-    const __amdgpu_buffer_rsrc_t ssrd = a.scale ? w4_srd(a.scale, (unsigned)a.Cout * 4u) : w4_srd(g_w4_ones, 16u);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrd = buf_srd(a.res ? a.res : a.y, a.res ? a.res_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t hsrd = buf_srd(a.shift, a.shift ? (unsigned)a.Cout * 4u : 0u);      // null: zero fill
+    const __amdgpu_buffer_rsrc_t ssrd = a.scale ? buf_srd(a.scale, (unsigned)a.Cout * 4u) : buf_srd(g_w4_ones, 16u);
 
     // ---- loader: a piece = 8 rows x 128 B (one wave instruction).  Wave w fills pieces w + 4j (j = 0..7) of the X region and of
     // the W region: rows 32j + 8w + (lane >> 3), slot lane & 7; (row >> 1) & 7 = (4 (w & 1) + (lane >> 4)) & 7 for all of them, so
@@ -126,14 +88,14 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
         wf0 = WR + wc * 128 * 128 + foff;
     };
     const int xs32 = 32 * a.x_ld * ES, ws32 = 32 * a.Kp_bytes;
-    int xo, wo;                                    // cursor tile: byte offsets of X row 8w + lrow / of its filter row (OOB: no tile)
+    int xo, wo;                                    // cursor tile: byte offsets of X row 8w + lrow / of its filter row (BUF_OOB: no tile)
     auto set_rows = [&](int i) {
         int bm0 = 0, bn0 = 0;
         const bool ok = tile_origin(i, bm0, bn0);
         const int row = lrow_w;                    // < 32: the channel permutation acts inside groups of 32 rows
         const int n = (((row >> 2) & 3) << 3) | (((row >> 4) & 1) << 2) | (row & 3);
-        xo = ok ? (bm0 + row) * a.x_ld * ES : OOB;
-        wo = ok ? (bn0 + n) * a.Kp_bytes : OOB;
+        xo = ok ? (bm0 + row) * a.x_ld * ES : BUF_OOB;
+        wo = ok ? (bn0 + n) * a.Kp_bytes : BUF_OOB;
     };
     char* const lbase = smem + wid * 1024;
     // Offsets of piece 0 of both operands for the cursor's K tile (once per K tile; an offset with bit 31 set is out of range for
@@ -144,13 +106,13 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
         const int q = kt * 8 + lc;
         // (branch-free on purpose: a select that hipcc turns into an exec-masked branch cuts the K tile's scheduling region in two)
         const int xok = ((q - a.kchunks) & ~xo) >> 31, wok = ((q * 16 - a.Kp_bytes) & ~wo) >> 31;      // -1: inside K and a real tile
-        xb = ((xo + q * 16) & xok) | (OOB & ~xok);
-        wb = ((wo + q * 16) & wok) | (OOB & ~wok);
+        xb = ((xo + q * 16) & xok) | (BUF_OOB & ~xok);
+        wb = ((wo + q * 16) & wok) | (BUF_OOB & ~wok);
     };
     auto dma_pair = [&](int j, int par) {
         char* b = lbase + par * KTB + j * 4096;
-        w4_dma16(xsrd, b + XR, xb + j * xs32);
-        w4_dma16(wsrd, b + WR, wb + j * ws32);
+        buf_dma16(xsrd, b + XR, xb + j * xs32);
+        buf_dma16(wsrd, b + WR, wb + j * ws32);
     };
 
     f32x4 acc[8][8];          // [ci][pi]
@@ -172,16 +134,16 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
         for (int cp = 0; cp < 4; ++cp) {
             const int ch0 = bn0 + 128 * wc + 32 * cp + 8 * fq;
             const bool chok = ch0 < a.Cout;                      // Cout is a multiple of 8 on this path
-            const f32x4 h0 = __builtin_bit_cast(f32x4, w4_load16(hsrd, ch0 * 4)), h1 = __builtin_bit_cast(f32x4, w4_load16(hsrd, ch0 * 4 + 16));
-            const f32x4 s0 = __builtin_bit_cast(f32x4, w4_load16(ssrd, a.scale ? ch0 * 4 : 0)), s1 = __builtin_bit_cast(f32x4, w4_load16(ssrd, a.scale ? ch0 * 4 + 16 : 0));
+            const f32x4 h0 = __builtin_bit_cast(f32x4, buf_load16(hsrd, ch0 * 4)), h1 = __builtin_bit_cast(f32x4, buf_load16(hsrd, ch0 * 4 + 16));
+            const f32x4 s0 = __builtin_bit_cast(f32x4, buf_load16(ssrd, a.scale ? ch0 * 4 : 0)), s1 = __builtin_bit_cast(f32x4, buf_load16(ssrd, a.scale ? ch0 * 4 + 16 : 0));
             u32x4 rr[8][ES / 2];
             if constexpr (RES) {
 #pragma unroll
                 for (int pi = 0; pi < 8; ++pi) {
                     const int m = bm0 + 128 * wr + 16 * pi + px;
-                    const int ro = (m < a.M && chok) ? (m * a.res_ld + ch0) * ES : OOB;
+                    const int ro = (m < a.M && chok) ? (m * a.res_ld + ch0) * ES : BUF_OOB;
 #pragma unroll
-                    for (int hh = 0; hh < ES / 2; ++hh) rr[pi][hh] = w4_load16(rsrd, ro + 16 * hh);
+                    for (int hh = 0; hh < ES / 2; ++hh) rr[pi][hh] = buf_load16(rsrd, ro + 16 * hh);
                 }
             }
 #pragma unroll
@@ -215,18 +177,18 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = apply_act_t<ACT>(v[e], a.act_param);
                 }
-                const int yo = (m < a.M && chok && !(DBG & 16)) ? (m * a.y_ld + ch0) * ES : OOB;      // out-of-range stores are dropped
+                const int yo = (m < a.M && chok && !(DBG & 16)) ? (m * a.y_ld + ch0) * ES : BUF_OOB;      // out-of-range stores are dropped
                 if constexpr (ES == 2) {
                     half8v hv;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) hv[e] = (half_t)v[e];
-                    w4_store16<STP>(ysrd, __builtin_bit_cast(u32x4, hv), yo);
+                    buf_store16<STP>(ysrd, __builtin_bit_cast(u32x4, hv), yo);
                 } else {
                     f32x4 f0, f1;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { f0[e] = v[e]; f1[e] = v[4 + e]; }
-                    w4_store16<STP>(ysrd, __builtin_bit_cast(u32x4, f0), yo);
-                    w4_store16<STP>(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
+                    buf_store16<STP>(ysrd, __builtin_bit_cast(u32x4, f0), yo);
+                    buf_store16<STP>(ysrd, __builtin_bit_cast(u32x4, f1), yo + 16);
                 }
             }
         }
@@ -250,7 +212,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) dma_pair(j, 1);
     advance();
-    w4_vmcnt<16>();
+    wait_vmcnt<16>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -279,7 +241,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
             if constexpr (!(DBG & 8)) {
 #pragma unroll
                 for (int pi = 0; pi < 8; ++pi)
-                    acc[r][pi] = MmaW4<T>::run(wfA[r], xfA[pi], ZERO ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[r][pi]);
+                    acc[r][pi] = Mma<T>::run(wfA[r], xfA[pi], ZERO ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[r][pi]);
             } else {
                 asm volatile("" ::"v"(wfA[r]), "v"(xfA[r]));
             }
@@ -291,7 +253,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
         }
         if constexpr (!(DBG & 4)) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's reads of buffer `par` are done ...
-            w4_vmcnt<NST>();                                          // ... and its pieces of the next K tile have landed
+            wait_vmcnt<NST>();                                          // ... and its pieces of the next K tile have landed
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
@@ -306,7 +268,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const Gemm256Args a) {
             if constexpr (!(DBG & 1)) dma_pair(r, par);
             if constexpr (!(DBG & 8)) {
 #pragma unroll
-                for (int pi = 0; pi < 8; ++pi) acc[r][pi] = MmaW4<T>::run(wfB[r], xfB[pi], acc[r][pi]);
+                for (int pi = 0; pi < 8; ++pi) acc[r][pi] = Mma<T>::run(wfB[r], xfB[pi], acc[r][pi]);
             } else {
                 asm volatile("" ::"v"(wfB[r]), "v"(xfB[r]));
             }

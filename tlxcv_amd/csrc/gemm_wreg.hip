@@ -13,21 +13,14 @@
 // permutation gives a lane 8 consecutive channels of each 32-channel half).  X is read once, Y written once.
 // Bound: HBM.  Algorithmic bytes per row: (K + N) * 2.  Plain (cacheable) stores: with the non-temporal policy and 16-byte pieces
 // at a 32-byte stride the same kernel ran 131 us on Swin-B's qkv (80.5 us as it is: 5.1 TB/s).
-#include "common.h"
+#include "kernel_util.h"
 #include "gemm256.h"
 
 namespace tlxmi {
 
-typedef __attribute__((address_space(3))) void* wr_lds_ptr_t;
-static __device__ __forceinline__ void wr_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (wr_lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
 #ifndef WR_AUX
-#define WR_AUX 0        // store policy of the output rows (0 plain, 2 non-temporal)
+#define WR_AUX BUF_WB   // store policy of the output rows (or BUF_NT)
 #endif
-static __device__ __forceinline__ f32x4 wr_mma(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, a), __builtin_bit_cast(half8v, b), c, 0, 0, 0);
-}
 
 // K: input channels (128 or 256); NCG: column groups of 64 output channels (N = 64 * NCG); NRG: row groups; a wave = (cg, rg) owns
 // 64 channels x PB 16-row blocks of every tile; tile = 16 * PB * NRG rows.
@@ -42,7 +35,6 @@ __global__ __launch_bounds__(64 * NCG * NRG, K == 128 ? 3 : 2) void gemm_wreg_ke
     constexpr int CPR = RB / 16;                // 16-byte chunks per row
     constexpr int TR = 16 * PB * NRG;           // rows per tile
     constexpr int TBYTES = TR * RB;
-    constexpr int OOB = (int)0x80000000;
     constexpr int N = 64 * NCG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* const tab = reinterpret_cast<float*>(smem + 2 * TBYTES);      // scale[N], shift[N]
@@ -52,8 +44,8 @@ __global__ __launch_bounds__(64 * NCG * NRG, K == 128 ? 3 : 2) void gemm_wreg_ke
     const int cg = wid % NCG, rg = wid / NCG;
     const int cbase = (int)blockIdx.y * N;      // wide layers: column slices of N channels as blockIdx.y (X is re-read per slice, from L2)
     const int fr = lane & 15, g = lane >> 4;
-    const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes);
 
     // X rows of a tile -> LDS: row r at r * RB, slot s holds chunk s ^ (r & 15) (low four bits): the 16 lanes of a
     // ds_read_b128 group (16 rows, one chunk) hit 16 distinct 16-byte bank slots
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(64 * NCG * NRG, K == 128 ? 3 : 2) void gemm_wreg_ke
             if (TR * CPR % NT == 0 || idx < TR * CPR) {
                 const int r = idx / CPR, s = idx % CPR;
                 const int c = s ^ (r & 15);
-                wr_dma16(xsrd, smem + buf * TBYTES + (base + wid * 64) * 16, m0 + r < a.M ? ((m0 + r) * a.x_ld) * 2 + c * 16 : OOB);
+                buf_dma16(xsrd, smem + buf * TBYTES + (base + wid * 64) * 16, m0 + r < a.M ? ((m0 + r) * a.x_ld) * 2 + c * 16 : BUF_OOB);
             }
         }
     };
@@ -116,7 +108,7 @@ __global__ __launch_bounds__(64 * NCG * NRG, K == 128 ? 3 : 2) void gemm_wreg_ke
                 for (int ci = 0; ci < 4; ++ci) {
                     acc[ci] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) acc[ci] = wr_mma(wf[ci][ks], xf[ks], acc[ci]);
+                    for (int ks = 0; ks < KS; ++ks) acc[ci] = Mma<half_t>::run(wf[ci][ks], xf[ks], acc[ci]);
                 }
                 // epilogue: lane (row fr, group g) holds channels ch0 + 32 (ci >> 1) + 4 (ci & 1) + r
                 float v[16];
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(64 * NCG * NRG, K == 128 ? 3 : 2) void gemm_wreg_ke
                 half8v o0, o1;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { o0[e] = (half_t)v[e]; o1[e] = (half_t)v[8 + e]; }
-                const int yo = m < a.M ? (m * a.y_ld + cbase + ch0) * 2 : OOB;
+                const int yo = m < a.M ? (m * a.y_ld + cbase + ch0) * 2 : BUF_OOB;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), ysrd, yo, 0, WR_AUX);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), ysrd, yo, 64, WR_AUX);
             }

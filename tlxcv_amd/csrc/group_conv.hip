@@ -23,15 +23,10 @@
 // runs in flight (independent accumulators between dependent MFMAs).  Epilogue: folded BatchNorm / bias, activation, fp16.
 // Algorithmic bytes per output pixel and chunk: 128 * (stride^2 + 1); the halo rows are re-read from L2 / the Infinity Cache
 // ((TH * stride + 2) / (TH * stride) of the input).
-#include "common.h"
+#include "kernel_util.h"
 #include "group_conv.h"
 
 namespace tlxmi {
-
-typedef __attribute__((address_space(3))) void* gc_lds_ptr_t;
-static __device__ __forceinline__ void gc_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (gc_lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
 
 struct GconvArgs {
     const char* x; const char* w; char* y;
@@ -62,7 +57,7 @@ __global__ __launch_bounds__(64 * NW) void gconv_kernel(const GconvArgs a) {
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int chunk = blockIdx.y;
     const int IWp = a.W + 2;
-    const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.x), 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes);
 
     // the input rows of a tile -> LDS buffer: pixel ip = iy * IWp + ix at ip * 128, 16-byte slot c = lane & 7.  Row by row
     // (the row index and its validity are scalar): per LDS-DMA a lane spends one compare and one add; lanes past the end of
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(64 * NW) void gconv_kernel(const GconvArgs a) {
                 const int idx = base + t;
                 if (idx < rowchunks) {
                     const int gx = (idx >> 3) - 1;
-                    gc_dma16(xsrd, dst + (iy * rowchunks + base) * 16, rowok && (unsigned)gx < (unsigned)a.W ? rowoff + (base >> 3) * a.x_ld * 2 : (int)0x80000000);
+                    buf_dma16(xsrd, dst + (iy * rowchunks + base) * 16, rowok && (unsigned)gx < (unsigned)a.W ? rowoff + (base >> 3) * a.x_ld * 2 : BUF_OOB);
                 }
             }
         }

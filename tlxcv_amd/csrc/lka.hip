@@ -29,7 +29,7 @@
 // operands agree.  Filter fragments come straight from the packed image (L1 / L2: 2 C^2 * 2 bytes a wave, at most 256 KiB);
 // rows past M read as zeros through out-of-range buffer offsets and are not stored.
 // Resource usage (profiles/van/lka_resource_usage.txt): no scratch.
-#include "common.h"
+#include "kernel_util.h"
 
 namespace tlxmi {
 
@@ -54,24 +54,13 @@ struct LkaDwArgs {
     unsigned x_bytes, y_bytes;
 };
 
-// acc + fp16 x * fp16 w in fp32 (both halves converted exactly, one rounding): the low / the high half of each packed pair
-static __device__ __forceinline__ float lka_mix_lo(unsigned x2, unsigned w2, float acc) {
-    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x2), "v"(w2));
-    return acc;
-}
-static __device__ __forceinline__ float lka_mix_hi(unsigned x2, unsigned w2, float acc) {
-    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x2), "v"(w2));
-    return acc;
-}
-
 __global__ __launch_bounds__(256, 2) void lka_dw_kernel(const char* __restrict__ x, const half_t* __restrict__ w0, const float* __restrict__ b0,
                                                      const half_t* __restrict__ w1, const float* __restrict__ b1, char* __restrict__ y,
                                                      const LkaDwArgs a) {
-    constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x;
-    const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc(y, 0, a.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(y, a.y_bytes);
 
     int b = (int)blockIdx.x;
     const int slab = b % a.slabs; b /= a.slabs;
@@ -90,8 +79,8 @@ __global__ __launch_bounds__(256, 2) void lka_dw_kernel(const char* __restrict__
         const int pr = i / TWp, pc = i - pr * TWp;
         const int gh = h0 - 11 + pr, gw = pc - 2;
         const bool in = (unsigned)gh < (unsigned)a.H && (unsigned)gw < (unsigned)a.W;
-        const int off = in ? ((img + gh * a.W + gw) * a.x_ld + c0) * 2 : OOB;
-        st[i] = __builtin_amdgcn_raw_buffer_load_b128(xsrd, off, 0, 0);
+        const int off = in ? ((img + gh * a.W + gw) * a.x_ld + c0) * 2 : BUF_OOB;
+        st[i] = buf_load16(xsrd, off);
     }
     __syncthreads();
 
@@ -117,10 +106,10 @@ __global__ __launch_bounds__(256, 2) void lka_dw_kernel(const char* __restrict__
 #pragma unroll
                     for (int q = 0; q < 5; ++q) {
                         const u32x2 v = *reinterpret_cast<const u32x2*>(base + (r * TWp + q) * 16), w2 = wt[r * 5 + q];
-                        acc[0] = lka_mix_lo(v[0], w2[0], acc[0]);
-                        acc[1] = lka_mix_hi(v[0], w2[0], acc[1]);
-                        acc[2] = lka_mix_lo(v[1], w2[1], acc[2]);
-                        acc[3] = lka_mix_hi(v[1], w2[1], acc[3]);
+                        acc[0] = fma_mix_lo(v[0], w2[0], acc[0]);
+                        acc[1] = fma_mix_hi(v[0], w2[0], acc[1]);
+                        acc[2] = fma_mix_lo(v[1], w2[1], acc[2]);
+                        acc[3] = fma_mix_hi(v[1], w2[1], acc[3]);
                     }
                 }
                 half4v hv;
@@ -151,17 +140,17 @@ __global__ __launch_bounds__(256, 2) void lka_dw_kernel(const char* __restrict__
 #pragma unroll
                 for (int q = 0; q < 7; ++q) {
                     const u32x2 v = *reinterpret_cast<const u32x2*>(base + (3 * r * AWp + 3 * q) * 16), w2 = wt[r * 7 + q];
-                    acc[0] = lka_mix_lo(v[0], w2[0], acc[0]);
-                    acc[1] = lka_mix_hi(v[0], w2[0], acc[1]);
-                    acc[2] = lka_mix_lo(v[1], w2[1], acc[2]);
-                    acc[3] = lka_mix_hi(v[1], w2[1], acc[3]);
+                    acc[0] = fma_mix_lo(v[0], w2[0], acc[0]);
+                    acc[1] = fma_mix_hi(v[0], w2[0], acc[1]);
+                    acc[2] = fma_mix_lo(v[1], w2[1], acc[2]);
+                    acc[3] = fma_mix_hi(v[1], w2[1], acc[3]);
                 }
             }
             half4v hv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) hv[e] = (half_t)(acc[e] + bs[e]);
             const int yo = ((img + (h0 + orow) * a.W + ow) * a.y_ld + cc) * 2;
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hv), ysrd, yo, 0, 0);
+            buf_store8(ysrd, __builtin_bit_cast(u32x2, hv), yo);
         }
     }
 }
@@ -197,18 +186,13 @@ struct LkaGateArgs {
     unsigned a1_bytes, t_bytes, res_bytes, y_bytes, w_bytes;
 };
 
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t lka_srd(const char* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, bytes, 0x00020000);
-}
-
 template <int NT>           // 16-channel sub-tiles: C = 16 NT, NT even
 __global__ __launch_bounds__(256) void lka_gate_kernel(const LkaGateArgs a) {
-    constexpr int OOB = (int)0x80000000;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int px = lane & 15, fg = lane >> 4;
     const int m0 = (int)blockIdx.x * 128 + wid * 32;
-    const __amdgpu_buffer_rsrc_t asrd = lka_srd(a.a1, a.a1_bytes), tsrd = lka_srd(a.t, a.t_bytes), rsrd = lka_srd(a.res, a.res_bytes);
-    const __amdgpu_buffer_rsrc_t ysrd = lka_srd(a.y, a.y_bytes), w1srd = lka_srd(a.w1, a.w_bytes), w2srd = lka_srd(a.w2, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t asrd = buf_srd(a.a1, a.a1_bytes), tsrd = buf_srd(a.t, a.t_bytes), rsrd = buf_srd(a.res, a.res_bytes);
+    const __amdgpu_buffer_rsrc_t ysrd = buf_srd(a.y, a.y_bytes), w1srd = buf_srd(a.w1, a.w_bytes), w2srd = buf_srd(a.w2, a.w_bytes);
     const bool live[2] = {m0 + px < a.M, m0 + 16 + px < a.M};
     const int wrow = px * a.Kp_bytes;                   // + 16 nt rows
 
@@ -223,10 +207,10 @@ __global__ __launch_bounds__(256) void lka_gate_kernel(const LkaGateArgs a) {
         u32x4 xf[2];
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-            xf[p] = __builtin_amdgcn_raw_buffer_load_b128(asrd, live[p] ? (m0 + 16 * p + px) * a.a1_ld * 2 + ks * 64 + fg * 16 : OOB, 0, 0);
+            xf[p] = buf_load16(asrd, live[p] ? (m0 + 16 * p + px) * a.a1_ld * 2 + ks * 64 + fg * 16 : BUF_OOB);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const u32x4 wf = __builtin_amdgcn_raw_buffer_load_b128(w1srd, wrow + nt * 16 * a.Kp_bytes + ks * 64 + fg * 16, 0, 0);
+            const u32x4 wf = buf_load16(w1srd, wrow + nt * 16 * a.Kp_bytes + ks * 64 + fg * 16);
 #pragma unroll
             for (int p = 0; p < 2; ++p)
                 acc[p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, wf), __builtin_bit_cast(half8v, xf[p]), acc[p][nt], 0, 0, 0);
@@ -246,7 +230,7 @@ __global__ __launch_bounds__(256) void lka_gate_kernel(const LkaGateArgs a) {
         }
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            const u32x2 tv = __builtin_amdgcn_raw_buffer_load_b64(tsrd, live[p] ? ((m0 + 16 * p + px) * a.t_ld + ch) * 2 : OOB, 0, 0);
+            const u32x2 tv = buf_load8(tsrd, live[p] ? ((m0 + 16 * p + px) * a.t_ld + ch) * 2 : BUF_OOB);
             const half4v th = __builtin_bit_cast(half4v, tv);
             half4v g;
 #pragma unroll
@@ -272,8 +256,8 @@ __global__ __launch_bounds__(256) void lka_gate_kernel(const LkaGateArgs a) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int wo = wrow + nt * 16 * a.Kp_bytes + ks * 64 + fg * 8;
-            const u32x2 lo = __builtin_amdgcn_raw_buffer_load_b64(w2srd, wo, 0, 0);
-            const u32x2 hi = __builtin_amdgcn_raw_buffer_load_b64(w2srd, wo + 32, 0, 0);
+            const u32x2 lo = buf_load8(w2srd, wo);
+            const u32x2 hi = buf_load8(w2srd, wo + 32);
             const u32x4 wf = u32x4{lo[0], lo[1], hi[0], hi[1]};
 #pragma unroll
             for (int p = 0; p < 2; ++p)
@@ -295,12 +279,12 @@ __global__ __launch_bounds__(256) void lka_gate_kernel(const LkaGateArgs a) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const int m = m0 + 16 * p + px;
-            const u32x2 rv = __builtin_amdgcn_raw_buffer_load_b64(rsrd, live[p] ? (m * a.res_ld + ch) * 2 : OOB, 0, 0);
+            const u32x2 rv = buf_load8(rsrd, live[p] ? (m * a.res_ld + ch) * 2 : BUF_OOB);
             const half4v rh = __builtin_bit_cast(half4v, rv);
             half4v o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (half_t)((float)rh[e] * rs[e] + (acc2[p][nt][e] * s2[e] + h2[e]));
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), ysrd, live[p] ? (m * a.y_ld + ch) * 2 : OOB, 0, 0);
+            buf_store8(ysrd, __builtin_bit_cast(u32x2, o), live[p] ? (m * a.y_ld + ch) * 2 : BUF_OOB);
         }
     }
 }

@@ -17,11 +17,9 @@
 //   x all 128 rows) | barrier.  The closing barrier is a raw s_barrier behind lgkmcnt(0): __syncthreads() there would drain the LDS-DMA
 //   in flight (it is a pending LDS write on the vector-memory counter).
 // 48 KiB of LDS and 64 accumulator registers a lane: three workgroups share a CU, whose loads overlap one another's MFMAs.
-#include "common.h"
+#include "kernel_util.h"
 
 namespace tlxmi {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_pre_t;
 
 struct PreArgs {
     const char* x;
@@ -35,13 +33,8 @@ struct PreArgs {
     unsigned x_bytes, w_bytes, y_bytes;
 };
 
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t pre_srd(const char* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, bytes, 0x00020000);
-}
-
 template <bool PRE_RELU, bool RELU>
 __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
-    constexpr int OOB = (int)0x80000000;
     __shared__ __attribute__((aligned(16))) char sa[128 * 128];       // A: 128 rows x 128 B
     __shared__ __attribute__((aligned(16))) char sb[2][128 * 128];    // B: 2 x (128 filter rows x 128 B)
 
@@ -58,7 +51,7 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
     }
     const int mt = tile / a.ntiles, nt = tile - mt * a.ntiles;
     const int bm0 = mt * 128;
-    const __amdgpu_buffer_rsrc_t xsrd = pre_srd(a.x, a.x_bytes), wsrd = pre_srd(a.wp, a.w_bytes), ysrd = pre_srd(a.y, a.y_bytes);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.wp, a.w_bytes), ysrd = buf_srd(a.y, a.y_bytes);
 
     // ---- A role: chunk c of rows pr + 32 i
     const int c = t & 7, pr = t >> 3;
@@ -66,7 +59,7 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int m = bm0 + pr + 32 * i;
-        xo[i] = m < a.M ? m * a.x_ld * 2 + c * 16 : OOB;      // < 2^31: tlxmi_preact_conv1x1_supported
+        xo[i] = m < a.M ? m * a.x_ld * 2 + c * 16 : BUF_OOB;      // < 2^31: tlxmi_preact_conv1x1_supported
     }
     char* const arow = sa + pr * 128 + ((c ^ ((pr >> 1) & 7)) << 4);      // + 32 * 128 * i: (r >> 1) & 7 is the same for all i
 
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
         const bool cl = ch0 < a.K;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            xr[i] = __builtin_amdgcn_raw_buffer_load_b128(xsrd, (cl && xo[i] != OOB) ? xo[i] + kt * 128 : OOB, 0, 0);
+            xr[i] = buf_load16(xsrd, (cl && xo[i] != BUF_OOB) ? xo[i] + kt * 128 : BUF_OOB);
         const int cs = cl ? ch0 : 0;                           // (a chunk past K is zeroed below whatever it was scaled by)
         sc[0] = *reinterpret_cast<const f32x4*>(a.ps + cs);
         sc[1] = *reinterpret_cast<const f32x4*>(a.ps + cs + 4);
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
         char* const dst = sb[kt & 1];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wsrd, (lds_ptr_pre_t)(dst + (wid + 4 * j) * 1024), 16, wo + j * wstep + kt * 128, 0, 0, 0);
+            buf_dma16(wsrd, dst + (wid + 4 * j) * 1024, wo + j * wstep + kt * 128);
     };
 
     issue_b(0);
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
                     if (PRE_RELU) v = fmaxf(v, 0.f);
                     hv[e] = (half_t)v;
                 }
-                if (!cl || xo[i] == OOB) hv = half8v{0, 0, 0, 0, 0, 0, 0, 0};
+                if (!cl || xo[i] == BUF_OOB) hv = half8v{0, 0, 0, 0, 0, 0, 0, 0};
                 *reinterpret_cast<half8v*>(arow + 32 * 128 * i) = hv;
             }
         }
@@ -189,8 +182,8 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
             hv[e] = (half_t)v0;
             hv[4 + e] = (half_t)v1;
         }
-        const int yo = (chl && m < a.M) ? (m * a.y_ld + ch0) * 2 : OOB;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hv), ysrd, yo, 0, 0);
+        const int yo = (chl && m < a.M) ? (m * a.y_ld + ch0) * 2 : BUF_OOB;
+        buf_store16(ysrd, __builtin_bit_cast(u32x4, hv), yo);
     }
 }
 

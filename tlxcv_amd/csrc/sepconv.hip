@@ -19,11 +19,9 @@
 // scratch), and only the other workgroup's stages overlap one's depthwise stage — its tap loads are not prefetched across K tiles.
 // Measured at DeepLabV3+'s ASPP shape: 0.42 ms against 0.80 ms for the dwconv + conv pair, ~165 TFLOP/s, far from the
 // MFMA bound; at dilation 1 the pair (dwconv_strip_kernel + gemm_pp) is faster and the engine keeps it there.
-#include "common.h"
+#include "kernel_util.h"
 
 namespace tlxmi {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_sep_t;
 
 struct SepArgs {
     const char* x;
@@ -39,25 +37,8 @@ struct SepArgs {
     unsigned x_bytes, w_bytes, y_bytes;
 };
 
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t sep_srd(const char* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, bytes, 0x00020000);
-}
-
-// fmaf((float)x.lo / .hi, (float)w.lo / .hi, acc) as ONE v_fma_mix_f32 (fp16 operands converted exactly, one rounding): hipcc
-// otherwise converts both operands with v_cvt_f32_f16 and packs the FMAs into v_pk_fma_f32 — twice the registers for the filter
-// (it hoists the filter's conversion out of the pixel loop) and the packed-fp32 form that costs extra beside MFMAs.
-static __device__ __forceinline__ float fma_mix_lo(unsigned x2, unsigned w2, float acc) {
-    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x2), "v"(w2));
-    return acc;
-}
-static __device__ __forceinline__ float fma_mix_hi(unsigned x2, unsigned w2, float acc) {
-    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x2), "v"(w2));
-    return acc;
-}
-
 template <bool RELU>
 __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
-    constexpr int OOB = (int)0x80000000;
     __shared__ __attribute__((aligned(16))) char sa[128 * 128];   // A: 128 pixel rows x 128 B
     __shared__ __attribute__((aligned(16))) char sb[256 * 128];   // B: 256 filter rows x 128 B
 
@@ -72,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
         tile = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (id >> 3);
     }
     const int bm0 = tile * 128;
-    const __amdgpu_buffer_rsrc_t xsrd = sep_srd(a.x, a.x_bytes), wsrd = sep_srd(a.wp, a.w_bytes), ysrd = sep_srd(a.y, a.y_bytes);
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.wp, a.w_bytes), ysrd = buf_srd(a.y, a.y_bytes);
 
     // ---- depthwise role: chunk c of pixel rows p_i = (t >> 3) + 32 i; tap (r, s) of row i at byte xo[i] + r * rowb + s * colb
     // (+ the K tile's channel offset) when bit 3 r + s of mk[i] is set.  xo may be negative (the leading padding): the entry point
@@ -126,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
         // B(kt): the barrier that closed K tile kt - 1 retired every fragment read of the old tile
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wsrd, (lds_ptr_sep_t)(sb + (wid + 4 * j) * 1024), 16, wo0 + j * wstep + kt * 128, 0, 0, 0);
+            buf_dma16(wsrd, sb + (wid + 4 * j) * 1024, wo0 + j * wstep + kt * 128);
 
         // A(kt): depthwise
         {
@@ -145,8 +126,8 @@ __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
 #pragma unroll
                 for (int tp = 0; tp < 9; ++tp) {
                     const int r = tp / 3, s = tp - 3 * r;
-                    const int off = (cl && ((mk[i] >> tp) & 1u)) ? xo[i] + r * rowb + s * colb + cb : OOB;
-                    xv[tp] = __builtin_bit_cast(half8v, __builtin_amdgcn_raw_buffer_load_b128(xsrd, off, 0, 0));
+                    const int off = (cl && ((mk[i] >> tp) & 1u)) ? xo[i] + r * rowb + s * colb + cb : BUF_OOB;
+                    xv[tp] = __builtin_bit_cast(half8v, buf_load16(xsrd, off));
                 }
                 float acc1[8];
 #pragma unroll
@@ -233,8 +214,8 @@ __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
                 hv[e] = (half_t)v0;
                 hv[4 + e] = (half_t)v1;
             }
-            const int yo = m < a.M ? (m * a.y_ld + ch0) * 2 : OOB;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hv), ysrd, yo, 0, 0);
+            const int yo = m < a.M ? (m * a.y_ld + ch0) * 2 : BUF_OOB;
+            buf_store16(ysrd, __builtin_bit_cast(u32x4, hv), yo);
         }
     }
 }
