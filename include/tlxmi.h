@@ -266,6 +266,17 @@ int tlxmi_bottleneck_seam_proj(const tlxmi_seam_desc* d, const void* t2, const v
 int tlxmi_bottleneck_seam(const tlxmi_seam_desc* d, const void* t2, const void* w3_packed, const float* scale3,
                           const float* shift3, const void* skip, void* y, const void* w1_packed, const float* scale1,
                           const float* shift1, void* t1, void* stream);
+/* tlxmi_bottleneck_seam_dec: the seam in front of a stage transition (layer1.2 -> layer2.0, layer2.3 -> layer3.0), where the only reader
+ * of y besides this launch is the next block's 1x1 stride-2 projection shortcut.  rows = N * H * W pixels of H x W images; t1 is the
+ * full map as above; y is stored DECIMATED: pixel (n, h, w) only when h and w are both even, at row n*Hc*Wc + (h/2)*Wc + w/2 of a
+ * compact map [N * Hc * Wc][y_ld], Hc = (H+1)/2, Wc = (W+1)/2 — bit for bit those rows of tlxmi_bottleneck_seam's y.  fp16,
+ * (K1, N1, N2) = (64, 256, 128) or (128, 512, 256).  tlxmi_bottleneck_seam_dec_supported (pure host code, dense maps: every pitch its
+ * channel count) answers 1 exactly when the call is taken: fp16, one of the two shapes, rows a whole number of images, every tensor
+ * below 2^31 bytes. */
+int tlxmi_bottleneck_seam_dec_supported(int dtype, int K1, int N1, int N2, int64_t rows, int H, int W);
+int tlxmi_bottleneck_seam_dec(const tlxmi_seam_desc* d, int H, int W, const void* t2, const void* w3_packed, const float* scale3,
+                              const float* shift3, const void* skip, void* y, const void* w1_packed, const float* scale1,
+                              const float* shift1, void* t1, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Expand conv of a ResNet transition block with its 1x1 projection shortcut as extra K (resnet.py:142-156 with the downsample of

@@ -102,6 +102,7 @@ PROTOTYPES = {
     "tlxmi_conv2d_splitk": [C.POINTER(ConvDesc), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_bottleneck_seam": [C.POINTER(SeamDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_bottleneck_seam_proj": [C.POINTER(SeamDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_bottleneck_seam_dec": [C.POINTER(SeamDesc), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_conv1x1_proj": [C.POINTER(ProjDesc), _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_preprocess_u8": [C.POINTER(PreprocDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_preprocess_linear_u8": [C.POINTER(PreprocDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -163,6 +164,7 @@ _SPECIAL = {
     "tlxmi_preprocess_u8_workspace_bytes": ([C.POINTER(PreprocDesc)], C.c_size_t),
     "tlxmi_multiclass_nms_workspace_bytes": ([_i, _i], C.c_size_t),
     "tlxmi_bottleneck_seam_supported": ([_i, _i, _i, _i], C.c_int),
+    "tlxmi_bottleneck_seam_dec_supported": ([_i, _i, _i, _i, _l, _i, _i], C.c_int),
     "tlxmi_conv1x1_proj_supported": ([C.POINTER(ProjDesc), _vp, _vp, _vp, _vp], C.c_int),
     "tlxmi_linear_ln_supported": ([_i, _l, _i, _i, _i, _i], C.c_int),
     "tlxmi_mlp_seam_supported": ([_i, _i, _i, _i], C.c_int),

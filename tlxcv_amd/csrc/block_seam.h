@@ -18,8 +18,15 @@ struct SeamArgs {
     int debug;                         // tuning flavour: ablation bits
 };
 
+// The decimated form (seam_kernel's DEC instances): y is the compact map of the pixels with even h and w.  Its own kernel argument
+// type, so that the argument block — and with it the code — of every other instance stays what it was.
+struct SeamDecArgs : SeamArgs {
+    int HW, W;                         // pixels per image and per image row (M = N * HW)
+};
+
 bool block_seam_shape_ok(int K1, int N1, int N2);
 int launch_block_seam(const SeamArgs& a, int K1, int N2, hipStream_t st);
+int launch_block_seam_dec(const SeamDecArgs& a, int K1, int N2, hipStream_t st);      // y keeps the pixels with even h and w only
 int launch_mlp_seam(const SeamArgs& a, int K1, int N2, hipStream_t st);      // the MLP form: fc1 + GELU + fc2 + residual
 
 }  // namespace tlxmi

@@ -25,6 +25,7 @@
 #include "kernel_util.h"
 #include <stdio.h>
 #include "block_seam.h"
+#include <type_traits>
 #ifdef TLXMI_TUNING
 #define TLXMI_DBG_NT(x) (x)
 #else
@@ -96,9 +97,15 @@ static __device__ __forceinline__ u32x2 bs_bn_relu4(f32x4 acc, f32x4 sc, f32x4 s
 // x = the K1-channel rows (a.x), W3 / shift3 = fc1's filter / bias, W1 / shift1 = fc2's; epilogue 1 is bias + GELU with NO store (y is
 // never written) and no skip, epilogue 2 is bias + the residual rows a.res [M][N2] with no activation.  Per row 3 * 2 * K1 bytes cross
 // HBM instead of (2 K1 + 4 N1) * 2: the hidden map (205 MB per block at half batch 64) is neither written nor read.
-template <int K1, int N2, int PW, int NW, bool PROJ = false, int WPS = 0, bool MLP = false>
-__global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const SeamArgs a) {
+// DEC: y is stored DECIMATED — only the pixels (h, w) with h and w both even, at row n*Hc*Wc + (h/2)*Wc + w/2 of a compact map
+// (Hc = (H+1)/2, Wc = (W+1)/2).  For the seam into a stage transition (layer1.2 -> layer2.0, layer2.3 -> layer3.0): the next block's
+// conv1 is computed here, so the only reader of y left is that block's 1x1 stride-2 projection shortcut, which reads exactly those
+// pixels; the other three quarters of the map (308 of 411 MB at 56 x 56, batch 256) were dead stores.  t1, the skip read and both
+// products are what they are without it.
+template <int K1, int N2, int PW, int NW, bool PROJ = false, int WPS = 0, bool MLP = false, bool DEC = false>
+__global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const std::conditional_t<DEC, SeamDecArgs, SeamArgs> a) {
     static_assert(!(PROJ && MLP), "one form at a time");
+    static_assert(!DEC || !(PROJ || MLP), "the decimated store belongs to the plain seam");
     constexpr int NT = 64 * NW;          // threads
     constexpr int IPT = 512 / NT;        // 16-byte chunks of a panel each thread stages
     constexpr int KS = K1 / 32;          // k-steps of GEMM1
@@ -151,6 +158,17 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
     for (int pw = 0; pw < PW; ++pw) {
         pix[pw] = m0 + 16 * pw + fr;
         pok[pw] = pix[pw] < a.M;
+    }
+    // DEC: the byte offset of this lane's 32 bytes in row (n, h/2, w/2) of the compact y, or BUF_OOB for a pixel that is not kept
+    // (h or w odd, or past M) — the idiom that already drops the rows past M; compact y_bytes < 2^31 keeps OOB + step offset dropped
+    int yoff[DEC ? PW : 1];
+    if constexpr (DEC) {
+        const int Wc = (a.W + 1) >> 1, HcWc = ((a.HW / a.W + 1) >> 1) * Wc;
+#pragma unroll
+        for (int pw = 0; pw < PW; ++pw) {
+            const int n = pix[pw] / a.HW, r = pix[pw] - n * a.HW, h = r / a.W, w = r - h * a.W;
+            yoff[pw] = (pok[pw] && !((h | w) & 1)) ? ((n * HcWc + (h >> 1) * Wc + (w >> 1)) * a.y_ld + 16 * g) * 2 : BUF_OOB;
+        }
     }
 
     // t2 fragments (B operand of GEMM1): lane (pixel fr, group g) holds channels 32*ks + 8g .. + 7
@@ -299,6 +317,10 @@ __global__ __launch_bounds__(64 * NW, WPS ? WPS : 1) void seam_kernel(const Seam
                     const u32x4 o = u32x4{o0[0], o0[1], o1[0], o1[1]};
                     yf[pw][h] = o;
                     if (TLXMI_DBG(a, 1)) continue;
+                    if constexpr (DEC) {
+                        buf_store16(ysrd, yf[pw][h], yoff[pw] + (64 * c + 8 * h) * 2);
+                        continue;
+                    }
                     if (TLXMI_DBG_NT(a.y_nt)) buf_store16<BUF_NT>(ysrd, yf[pw][h], pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * h) * 2 : BUF_OOB);
                     else buf_store16(ysrd, yf[pw][h], pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * h) * 2 : BUF_OOB);
                 }
@@ -561,11 +583,12 @@ template <int K1, int N2, int NW> static int launch_seam_pair_t(const SeamArgs& 
     return TLXMI_OK;
 }
 
-template <int K1, int N2, int PW, int NW, bool PROJ = false, int WPS = 0, bool MLP = false> static int launch_seam_t(const SeamArgs& a, hipStream_t st) {
+template <int K1, int N2, int PW, int NW, bool PROJ = false, int WPS = 0, bool MLP = false, bool DEC = false>
+static int launch_seam_t(const std::conditional_t<DEC, SeamDecArgs, SeamArgs>& a, hipStream_t st) {
     constexpr int NP = K1 / 64 + N2 / 64 + (PROJ ? K1 / 64 : 0);
     const size_t lds = (size_t)2 * NP * 64 * 128 + (size_t)(2 * a.N1 + 2 * N2 + (PROJ ? 2 * a.N1 : 0)) * sizeof(float);
     if (lds > 160 * 1024) return fail(TLXMI_ERR_UNSUPPORTED, "block_seam: %zu bytes of LDS", lds);
-    const void* fn = reinterpret_cast<const void*>(&seam_kernel<K1, N2, PW, NW, PROJ, WPS, MLP>);
+    const void* fn = reinterpret_cast<const void*>(&seam_kernel<K1, N2, PW, NW, PROJ, WPS, MLP, DEC>);
     if (lds > 64 * 1024)
         if (int rc = raise_lds_limit(fn, 160 * 1024, "block_seam")) return rc;
     const long grid = ((long)a.M + NW * 16 * PW - 1) / (NW * 16 * PW);
@@ -577,7 +600,7 @@ template <int K1, int N2, int PW, int NW, bool PROJ = false, int WPS = 0, bool M
         fprintf(stderr, "seam<%d,%d,%d,%d,%d>: lds %zu, grid %ld, occupancy %d workgroups / CU (%s)\n", K1, N2, PW, NW, (int)PROJ, lds, grid, nb, hipGetErrorString(oe));
     }
 #endif
-    SeamArgs b = a;
+    auto b = a;
     void* args[] = {&b};
     hipError_t e = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(64 * NW), args, lds, st);
     if (e != hipSuccess) return fail(TLXMI_ERR_LAUNCH, "block_seam: HIP launch failed: %s", hipGetErrorString(e));
@@ -633,6 +656,20 @@ int launch_block_seam(const SeamArgs& a0, int K1, int N2, hipStream_t st) {
         return v ? launch_seam_t<256, 256, 1, 4>(a, st) : launch_seam_t<256, 256, 1, 8>(a, st);
     }
     return fail(TLXMI_ERR_UNSUPPORTED, "block_seam: no instantiation for %d -> N1 -> %d channels", K1, N2);
+}
+
+// the decimated form (a.HW, a.W set; a.y the compact map): the two seams that end a stage, in the workgroup shapes of their full forms
+static bool block_seam_dec_shape_ok(int K1, int N1, int N2) {
+    return ((K1 == 64 && N1 == 256 && N2 == 128) || (K1 == 128 && N1 == 512 && N2 == 256)) && block_seam_shape_ok(K1, N1, N2);
+}
+
+int launch_block_seam_dec(const SeamDecArgs& a0, int K1, int N2, hipStream_t st) {
+    SeamDecArgs b = a0;
+    b.z_nt = b.y_nt = 0;
+    b.debug = 0;
+    if (K1 == 64 && N2 == 128) return launch_seam_t<64, 128, 2, 4, false, 0, false, true>(b, st);
+    if (K1 == 128 && N2 == 256) return launch_seam_t<128, 256, 1, 8, false, 0, false, true>(b, st);
+    return fail(TLXMI_ERR_UNSUPPORTED, "block_seam_dec: no instantiation for %d -> N1 -> %d channels", K1, N2);
 }
 
 }  // namespace tlxmi
@@ -694,6 +731,56 @@ extern "C" int tlxmi_bottleneck_seam_proj(const tlxmi_seam_desc* d, const void* 
                                           const float* shift1, void* t1, void* stream) {
     TLXMI_REQUIRE(wd_packed, TLXMI_ERR_BAD_ARG, "bottleneck_seam_proj: null shortcut filter");
     return seam_impl(d, t2, w3_packed, scale3, shift3, x, y, w1_packed, scale1, shift1, t1, stream, wd_packed, scale_d, shift_d);
+}
+
+// The seam in front of a stage transition, y stored DECIMATED (seam_kernel's DEC form): rows = N * H * W pixels of H x W images go
+// in; t1 is the full map [rows][t1_ld]; y is the compact map [N * Hc * Wc][y_ld], Hc = (H+1)/2, Wc = (W+1)/2, holding the pixels with
+// even h and even w — what a 1x1 stride-2 unpadded convolution (the next block's projection shortcut) reads, odd extents included.
+// tlxmi_bottleneck_seam_dec_supported is pure host code over dense maps (every pitch = its channel count) and answers 1 exactly
+// when such a call is taken.
+static long long seam_dec_rows(long long rows, int H, int W) { return rows / ((long long)H * W) * ((H + 1) / 2) * ((W + 1) / 2); }
+
+extern "C" int tlxmi_bottleneck_seam_dec_supported(int dtype, int K1, int N1, int N2, int64_t rows, int H, int W) {
+    if (dtype != TLXMI_F16 || !block_seam_dec_shape_ok(K1, N1, N2) || rows <= 0 || H <= 0 || W <= 0) return 0;
+    const long long big = (1ll << 31), hw = (long long)H * W;
+    if (hw >= big || rows % hw) return 0;
+    return rows * K1 * 2 < big && rows * N1 * 2 < big && rows * N2 * 2 < big && seam_dec_rows(rows, H, W) * N1 * 2 < big ? 1 : 0;
+}
+
+extern "C" int tlxmi_bottleneck_seam_dec(const tlxmi_seam_desc* d, int H, int W, const void* t2, const void* w3_packed, const float* scale3,
+                                         const float* shift3, const void* skip, void* y, const void* w1_packed, const float* scale1,
+                                         const float* shift1, void* t1, void* stream) {
+    TLXMI_REQUIRE(d && t2 && w3_packed && skip && y && w1_packed && t1, TLXMI_ERR_BAD_ARG, "bottleneck_seam_dec: null argument");
+    TLXMI_REQUIRE(d->dtype == TLXMI_F16, TLXMI_ERR_UNSUPPORTED, "bottleneck_seam_dec: fp16 only");
+    TLXMI_REQUIRE(d->rows > 0 && d->K1 > 0 && d->N1 > 0 && d->N2 > 0 && H > 0 && W > 0, TLXMI_ERR_BAD_ARG, "bottleneck_seam_dec: bad extent");
+    if (!block_seam_dec_shape_ok(d->K1, d->N1, d->N2))
+        return fail(TLXMI_ERR_UNSUPPORTED, "bottleneck_seam_dec: no kernel for %d -> %d -> %d channels", d->K1, d->N1, d->N2);
+    const long long big = (1ll << 31), rows = d->rows, hw = (long long)H * W;
+    TLXMI_REQUIRE(hw < big && rows % hw == 0, TLXMI_ERR_BAD_ARG, "bottleneck_seam_dec: rows is not a whole number of H x W images");
+    TLXMI_REQUIRE(d->t2_ld >= d->K1 && d->skip_ld >= d->N1 && d->y_ld >= d->N1 && d->t1_ld >= d->N2, TLXMI_ERR_BAD_ARG, "bottleneck_seam_dec: row stride below the channel count");
+    TLXMI_REQUIRE(d->t2_ld % 8 == 0 && d->skip_ld % 8 == 0 && d->y_ld % 8 == 0 && d->t1_ld % 8 == 0 && aligned16(t2) && aligned16(skip) && aligned16(y) &&
+                      aligned16(t1) && aligned16(w3_packed) && aligned16(w1_packed),
+                  TLXMI_ERR_ALIGNMENT, "bottleneck_seam_dec: rows must be whole 16-byte chunks");
+    TLXMI_REQUIRE(d->act == TLXMI_ACT_RELU, TLXMI_ERR_UNSUPPORTED, "bottleneck_seam_dec: ReLU after both convolutions only");
+    const long long yrows = seam_dec_rows(rows, H, W);
+    TLXMI_REQUIRE(rows * d->t2_ld * 2 < big && rows * d->skip_ld * 2 < big && yrows * d->y_ld * 2 < big && rows * d->t1_ld * 2 < big,
+                  TLXMI_ERR_UNSUPPORTED, "bottleneck_seam_dec: a tensor exceeds the 2 GiB the 32-bit buffer offsets address");
+    SeamDecArgs a;
+    a.x = (const char*)t2; a.w3 = (const char*)w3_packed; a.res = (const char*)skip; a.w1 = (const char*)w1_packed;
+    a.y = (char*)y; a.z = (char*)t1;
+    a.scale3 = scale3; a.shift3 = shift3; a.scale1 = scale1; a.shift1 = shift1;
+    a.M = (int)rows; a.N1 = d->N1;
+    a.x_ld = d->t2_ld; a.res_ld = d->skip_ld; a.y_ld = d->y_ld; a.z_ld = d->t1_ld;
+    a.x_bytes = (unsigned)(rows * d->t2_ld * 2); a.res_bytes = (unsigned)(rows * d->skip_ld * 2);
+    a.y_bytes = (unsigned)(yrows * d->y_ld * 2); a.z_bytes = (unsigned)(rows * d->t1_ld * 2);
+    a.wd = nullptr; a.scale_d = a.shift_d = nullptr; a.wd_bytes = 0;
+    a.w3_bytes = (unsigned)(((size_t)(d->N1 + 127) / 128 * 128) * (size_t)d->K1 * 2);
+    a.w1_bytes = (unsigned)(((size_t)(d->N2 + 127) / 128 * 128) * (size_t)d->N1 * 2);
+    a.y_nt = a.z_nt = 0; a.debug = 0;
+    a.HW = (int)hw; a.W = W;
+    const int rc = launch_block_seam_dec(a, d->K1, d->N2, as_stream(stream));
+    if (rc != TLXMI_OK) return rc;
+    return check_launch("bottleneck_seam_dec");
 }
 
 // A transformer MLP as ONE launch (round 5): out = fc2(gelu(fc1(x) + b1)) + b2 + res, the hidden activations never leave the CU

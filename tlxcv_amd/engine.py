@@ -29,6 +29,9 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # read; a clear bit = the shortcut as its own launch, read back as the expand conv's residual (the A/B and
                                   # the parity tests' other arm).  All on: bits 1 and 2 each win alone; bit 4 is inside the noise
                                   # end to end but removes a launch and trades no seam for it (137 -> 84 us); mask 7 has the best mean (+1.9 .. 2.1 %)
+            "seam_decimate": True,  # ResNet seams in front of a stage transition (layer1.2 -> layer2.0, layer2.3 -> layer3.0) store the block output
+                                  # only at the pixels the next block's 1x1 stride-2 folded shortcut reads (tlxmi_bottleneck_seam_dec): a compact
+                                  # (N, H/2, W/2, C) map, a quarter of the stores; off = the full map, read at stride 2 (the A/B and the tests' other arm)
             "two_streams": True,  # large batches as two half batches on two HIP streams (two_streams(), below)
             "conv_splitk": True,  # convs with few pixels and a long K on K slices (tlxmi_conv2d_splitk)
             "patch_linear": True, # ViT patch embedding as one Linear over all token rows (tlxmi_patchify + the persistent GEMM); off = the
@@ -691,23 +694,35 @@ def bottleneck_seam_supported(K1, N1, N2, dtype):
     return bool(_lib.load().tlxmi_bottleneck_seam_supported(dt_code(dtype), int(K1), int(N1), int(N2)))
 
 
-def bottleneck_seam(t2, pk3, scale3, shift3, skip, pk1, scale1, shift1, proj=None):
+def bottleneck_seam_dec_supported(K1, N1, N2, rows, H, W, dtype):
+    """Whether bottleneck_seam(..., y_stride2=True) has a kernel (tlxmi_bottleneck_seam_dec_supported: pure host code)."""
+    return bool(_lib.load().tlxmi_bottleneck_seam_dec_supported(dt_code(dtype), int(K1), int(N1), int(N2), int(rows), int(H), int(W)))
+
+
+def bottleneck_seam(t2, pk3, scale3, shift3, skip, pk1, scale1, shift1, proj=None, y_stride2=False):
     """One launch for the seam between two bottleneck blocks (tlxmi_bottleneck_seam): y = relu(conv3(t2) * scale3 + shift3 +
     skip); t1 = relu(conv1'(y) * scale1 + shift1).  t2 (N,H,W,K1), skip (N,H,W,N1) -> (y (N,H,W,N1), t1 (N,H,W,N2)).
     proj=(pk_d, scale_d, shift_d): `skip` is the block's INPUT (N,H,W,K1) and the projection shortcut conv_d + bn_d is computed
-    inside the launch (tlxmi_bottleneck_seam_proj) instead of being read from a stored map."""
+    inside the launch (tlxmi_bottleneck_seam_proj) instead of being read from a stored map.
+    y_stride2: y is the compact map (N, (H+1)//2, (W+1)//2, N1) of the pixels with even h and w (tlxmi_bottleneck_seam_dec) — for a seam
+    whose y is read by nothing but a 1x1 stride-2 convolution; t1 is the full map all the same."""
     need_gpu(t2, "input")
     N, H, W, ld = t2.shape
+    if y_stride2 and proj is not None:
+        raise RuntimeError("bottleneck_seam: no decimated form of the projection-shortcut seam")
     if skip.shape[:3] != t2.shape[:3] or skip.dtype != t2.dtype or not skip.is_contiguous() or not t2.is_contiguous():
         raise RuntimeError("bottleneck_seam: t2 / skip must be dense NHWC maps of one dtype and extent")
-    y = torch.empty((N, H, W, pk3.Cout), dtype=t2.dtype, device=t2.device)
+    y = torch.empty((N, (H + 1) // 2, (W + 1) // 2, pk3.Cout) if y_stride2 else (N, H, W, pk3.Cout), dtype=t2.dtype, device=t2.device)
     t1 = torch.empty((N, H, W, pk1.Cout), dtype=t2.dtype, device=t2.device)
     rows = N * H * W
     if getattr(_tls, "act_max", None) is not None:
         _note_act(t2.numel() * t2.element_size(), skip.numel() * skip.element_size(), y.numel() * y.element_size(), t1.numel() * t1.element_size())
     d = _lib.SeamDesc(dtype=dt_code(t2.dtype), rows=rows, K1=pk3.Cin, N1=pk3.Cout, N2=pk1.Cout, t2_ld=ld, skip_ld=skip.shape[-1],
                       y_ld=pk3.Cout, t1_ld=pk1.Cout, act=ACT_RELU)
-    if proj is None:
+    if y_stride2:
+        name = "tlxmi_bottleneck_seam_dec"
+        args = (C.byref(d), H, W, _p(t2), _p(pk3.buf), _p(scale3), _p(shift3), _p(skip), _p(y), _p(pk1.buf), _p(scale1), _p(shift1), _p(t1), _stream())
+    elif proj is None:
         name = "tlxmi_bottleneck_seam"
         args = (C.byref(d), _p(t2), _p(pk3.buf), _p(scale3), _p(shift3), _p(skip), _p(y), _p(pk1.buf), _p(scale1), _p(shift1), _p(t1), _stream())
     else:
@@ -720,13 +735,13 @@ def bottleneck_seam(t2, pk3, scale3, shift3, skip, pk1, scale1, shift1, proj=Non
         return y, t1
     es = t2.element_size()
     skip_ch = pk3.Cout if proj is None else proj[0].Cin
-    alg_bytes = (rows * (pk3.Cin + skip_ch + pk3.Cout + pk1.Cout) + pk3.Cout * pk3.Cin + pk1.Cout * pk1.Cin) * es
+    alg_bytes = (rows * (pk3.Cin + skip_ch + pk1.Cout) + y.numel() + pk3.Cout * pk3.Cin + pk1.Cout * pk1.Cin) * es
     flops = 2 * rows * (pk3.Cout * pk3.Cin + pk1.Cout * pk1.Cin + (0 if proj is None else pk3.Cout * proj[0].Cin))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     _lib.call(name, *args)
     e1.record()
-    _probe.append((e0, e1, alg_bytes, flops, (N, H, W, pk3.Cin, pk3.Cout, pk1.Cout, "seam" if proj is None else "seam+proj", True)))
+    _probe.append((e0, e1, alg_bytes, flops, (N, H, W, pk3.Cin, pk3.Cout, pk1.Cout, "seam+dec" if y_stride2 else "seam" if proj is None else "seam+proj", True)))
     return y, t1
 
 
@@ -748,6 +763,18 @@ def conv1x1_proj_supported(t2, x2, pk, stride, out=None, k2=None):
     d = _proj_desc(t2, x2, pk, stride, pk.Cout if out is None else out.shape[-1], ACT_NONE, 0.0, k2)
     y = C.c_void_p(16) if out is None else _p(out)
     return bool(_lib.load().tlxmi_conv1x1_proj_supported(C.byref(d), _p(t2), _p(x2), _p(pk.buf), y))
+
+
+def conv1x1_proj_shapes_supported(t2_shape, x2_shape, pk, stride):
+    """conv1x1_proj_supported for dense maps of these shapes and pk's dtype that do not exist yet (the same host predicate: three
+    16-byte aligned addresses far apart stand in for the buffers, nothing is dereferenced)."""
+    if len(t2_shape) != 4 or len(x2_shape) != 4 or pk.R != 1 or pk.S != 1 or t2_shape[0] != x2_shape[0] or pk.Cin <= x2_shape[-1] or pk.dtype not in (torch.float16, torch.float32):
+        return False
+    N, Ho, Wo, ld = t2_shape
+    d = _lib.ProjDesc(dtype=dt_code(pk.dtype), N=N, Ho=Ho, Wo=Wo, K1=pk.Cin - x2_shape[-1], K2=x2_shape[-1], Cout=pk.Cout, H2=x2_shape[1],
+                      W2=x2_shape[2], stride=int(stride), x_ld=ld, x2_ld=x2_shape[-1], y_ld=pk.Cout, act=ACT_NONE, act_param=0.0, flags=plan_flags())
+    x, x2, y = (C.c_void_p(i << 40) for i in (1, 2, 3))
+    return bool(_lib.load().tlxmi_conv1x1_proj_supported(C.byref(d), x, x2, _p(pk.buf), y))
 
 
 def conv1x1_proj(t2, x2, pk, stride, shift=None, act=ACT_NONE, act_param=0.0, out=None, k2=None):

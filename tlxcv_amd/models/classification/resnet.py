@@ -122,10 +122,12 @@ class BottleneckBlock(nn.Module):
             return E.PackedFilter(torch.cat([w3, wd], dim=1), dt), h3 + hd
         return c3._cached(("projfold", id(cd), id(self.bn3), id(bnd)), build, deps=(cd, self.bn3, bnd))
 
-    def finish_folded(self, out, v):
-        """relu(bn3(conv3(out)) + bn_d(conv_d(v))) as ONE launch (E.conv1x1_proj): the projection shortcut is extra K of the expand
-        conv, its map is neither written nor read.  None when the block has no such shortcut, the option bit is clear, or the library
-        does not take the shapes (fp32, channel counts that are not whole K tiles) — the caller runs shortcut() + finish()."""
+    def fold_stride(self, out_shape, v_shape):
+        """The stride at which finish_folded reads a block input of shape v_shape next to a conv2 output of shape out_shape, or None when
+        it does not fold: the block has no plain 1x1 projection shortcut, the option bit is clear, or the library does not take the
+        shapes (fp32, channel counts that are not whole K tiles).  Shapes only, so that the step BEFORE this block can ask (a seam that
+        stores its output decimated, bottleneck_step).  A stride-2 shortcut whose input already has the output's extent is handed the
+        compact map of such a seam — the pixels it would have picked — and reads it at stride 1."""
         ds = self.downsample
         if ds is None or E.precision() != torch.float16 or not (E.option_value("proj_fold") & self.proj_fold_bit):
             return None
@@ -139,16 +141,40 @@ class BottleneckBlock(nn.Module):
                            and c.biases is None and not c.same)
         if (not plain(c3) or not plain(cd) or c3.stride != (1, 1) or cd.stride not in ((1, 1), (2, 2)) or cd.out_channels != c3.out_channels
                 or c3.in_channels % 64 or cd.in_channels % 64 or c3.out_channels % 8
-                or out.shape[-1] != c3.in_channels or v.shape[-1] != cd.in_channels):
+                or out_shape[-1] != c3.in_channels or v_shape[-1] != cd.in_channels):
+            return None
+        stride = 1 if cd.stride == (2, 2) and tuple(v_shape[1:3]) == tuple(out_shape[1:3]) else cd.stride[0]
+        pk, _ = self.folded_filter()
+        return stride if E.conv1x1_proj_shapes_supported(out_shape, v_shape, pk, stride) else None
+
+    def finish_folded(self, out, v):
+        """relu(bn3(conv3(out)) + bn_d(conv_d(v))) as ONE launch (E.conv1x1_proj): the projection shortcut is extra K of the expand
+        conv, its map is neither written nor read.  None when fold_stride() says so — the caller runs shortcut() + finish()."""
+        if out.dtype != E.precision() or v.dtype != out.dtype or not out.is_contiguous() or not v.is_contiguous():
+            return None
+        stride = self.fold_stride(out.shape, v.shape)
+        if stride is None:
             return None
         pk, shift = self.folded_filter()
-        if not E.conv1x1_proj_supported(out, v, pk, cd.stride[0]):
-            return None
-        return E.conv1x1_proj(out, v, pk, cd.stride[0], shift=shift, act=E.ACT_RELU)
+        return E.conv1x1_proj(out, v, pk, stride, shift=shift, act=E.ACT_RELU)
 
-    def seam_with(self, nxt, out, v):
+    def reads_input_at_stride2_only(self, v_shape):
+        """Whether, given conv1's output from elsewhere, this block reads of its input (v_shape, NHWC) only the pixels with even h and
+        w: its shortcut is the 1x1 stride-(2,2) unpadded conv + BatchNorm that finish_folded takes, and finish_folded WILL take it — on
+        the compact map (N, (H+1)//2, (W+1)//2, C) beside conv2's output, whose shape follows from conv2's geometry."""
+        ds, c2 = self.downsample, self.conv2
+        if ds is None or len(ds) != 2 or getattr(ds[0], "stride", None) != (2, 2) or c2.same:
+            return False
+        N, H, W, ch = v_shape
+        ext = lambda n, i: (n + 2 * c2.padding[i] - c2.dilation[i] * (c2.kernel_size[i] - 1) - 1) // c2.stride[i] + 1
+        out_shape = (N, ext(H, 0), ext(W, 1), c2.out_channels)
+        return self.fold_stride(out_shape, (N, (H + 1) // 2, (W + 1) // 2, ch)) == 1
+
+    def seam_with(self, nxt, out, v, y_stride2=False):
         """(block output, nxt's conv1 output) in one launch — `v` is the block's input, the skip or the projection shortcut's
-        source — or None when there is no fused kernel for these layers."""
+        source — or None when there is no fused kernel for these layers.  y_stride2: the caller vouches that nothing reads the block
+        output but a 1x1 stride-2 conv; where the library has that kernel the block output is then the compact map of the pixels with
+        even h and w (E.bottleneck_seam), else the full map as without it."""
         c3, c1 = self.conv3, nxt.conv1
         dt = E.precision()
         if (not E.option("seams") or dt != torch.float16 or c3.n_group != 1 or c1.n_group != 1 or c1.kernel_size != (1, 1) or c1.stride != (1, 1)
@@ -172,7 +198,9 @@ class BottleneckBlock(nn.Module):
         s3, h3 = c3._cached(("bn", id(self.bn3)), lambda: self.bn3.folded(None), deps=(self.bn3,))
         s1, h1 = c1._cached(("bn", id(nxt.bn1)), lambda: nxt.bn1.folded(None), deps=(nxt.bn1,))
         if self.downsample is None:
-            return E.bottleneck_seam(out, pk3, s3, h3, v, pk1, s1, h1)
+            N, H, W, _ = out.shape
+            dec = y_stride2 and E.bottleneck_seam_dec_supported(c3.in_channels, c3.out_channels, c1.out_channels, N * H * W, H, W, dt)
+            return E.bottleneck_seam(out, pk3, s3, h3, v, pk1, s1, h1, y_stride2=dec)
         cd, bnd = self.downsample[0], self.downsample[1]
         if (cd.kernel_size == (1, 1) and cd.stride == (1, 1) and cd.padding == (0, 0) and cd.n_group == 1 and cd.biases is None
                 and c3.in_channels == 64 and c1.out_channels == 64 and cd.in_channels == 64 and v.shape[-1] == 64):
@@ -201,7 +229,14 @@ def bottleneck_step(blk, nxt, v, t1=None):
     folded = blk.finish_folded(out, v)
     if folded is not None:
         return folded, None
-    fused = blk.seam_with(nxt, out, v) if isinstance(nxt, BottleneckBlock) else None
+    if t1 is not None and v.shape[1:3] != t1.shape[1:3]:
+        # the previous step's seam stored v decimated because this block promised the folded launch; the full map does not exist
+        raise RuntimeError("bottleneck_step: the folded shortcut launch was refused after a decimated seam")
+    # the seam in front of a stage transition: nxt reads this block's output through its strided shortcut alone (conv1 is computed
+    # here), so only those pixels are stored — decided from shapes, before the launch, by the predicate nxt's own step will apply
+    dec = (isinstance(nxt, BottleneckBlock) and E.option("seam_decimate")
+           and nxt.reads_input_at_stride2_only(tuple(out.shape[:3]) + (blk.conv3.out_channels,)))
+    fused = blk.seam_with(nxt, out, v, y_stride2=dec) if isinstance(nxt, BottleneckBlock) else None
     if fused is not None:
         return fused
     return blk.finish(out, blk.shortcut(v)), None
