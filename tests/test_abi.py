@@ -196,6 +196,48 @@ def test_host_dispatch_survives_without_a_device():
                 assert rc in (0, -4), (rc, lib.tlxmi_last_error())
 
 
+def _traced_conv2d(capfd, case, **knobs):
+    """(candidate of the last `-> cand N` line, name of the first `launched` line) of one fp16 tlxmi_conv2d call on fake pointers."""
+    import dispatch_matrix as DM
+    from tlxcv_amd import _lib
+    Ho, Wo, _ = DM.out_hw(case)
+    d = _lib.ConvDesc(dtype=0, N=case.N, H=case.H, W=case.W, C=case.Cin, Cout=case.Cout, R=case.R, S=case.S, stride_h=case.stride[0],
+                      stride_w=case.stride[1], pad_h=case.pad[0], pad_w=case.pad[1], dil_h=case.dil[0], dil_w=case.dil[1], Ho=Ho, Wo=Wo,
+                      x_ld=case.Cin, y_ld=case.Cout, act=case.act, act_param=case.act_param)
+    capfd.readouterr()
+    with _lib.tuning(TLXMI_TRACE_TILES="1", **knobs) as lib:
+        rc = lib.tlxmi_conv2d(ctypes.byref(d), ctypes.c_void_p(1 << 32), ctypes.c_void_p(2 << 32), None, None, None, ctypes.c_void_p(3 << 32), None)
+    assert rc == -4, (rc, lib.tlxmi_last_error())      # no device: the call ends at its first launch
+    lines = capfd.readouterr().err.splitlines()
+    at = next(i for i, ln in enumerate(lines) if ln.startswith("launched "))
+    cands = [int(ln.split("-> cand ")[1].split()[0]) for ln in lines[:at] if "-> cand " in ln]
+    return (cands[-1] if cands else None), lines[at].split()[1]
+
+
+@pytest.mark.parametrize("kernel", ["igemm0", "igemm1", "igemm2", "igemm3", "igemm4", "gemm256_6", "pp7", "stream8", "pp9", "pp10"])
+def test_forced_and_chosen_candidates_launch_the_kernel_they_name(kernel, capfd):
+    """The candidate numbers are public (TLXMI_TILE, dispatch_matrix.TILE_OF): on a dense case of the matrix that admits `kernel`,
+    TLXMI_TILE=<its number> makes the `launched` line name it; unforced, the kernel launched is the one whose number the
+    `-> cand N` line in front of it gives.  Host code only: fake pointers, the launch itself fails."""
+    import torch
+    import dispatch_matrix as DM
+    from tlxcv_amd import _lib
+    if torch.cuda.is_available():
+        pytest.skip("would launch on the device with fake pointers")
+    if not os.path.exists(_lib.TUNE_LIB_PATH):
+        pytest.skip("the tuning flavour is not built")
+    assert list(DM.TILE_OF) == ["igemm0", "igemm1", "igemm2", "igemm3", "igemm4", "gemm256_6", "pp7", "stream8", "pp9", "pp10"]
+    name_of = {v: k for k, v in DM.TILE_OF.items()}
+    cases = [c for c in DM.CASES if c.feat == "a" and c.groups == 1 and kernel in DM.eligible(c, torch.float16)]
+    assert cases
+    for case in cases:
+        # TLXMI_HALO / TLXMI_WREG off: those two kernels are taken before any candidate is chosen
+        cand, launched = _traced_conv2d(capfd, case, TLXMI_TILE=DM.TILE_OF[kernel], TLXMI_HALO="0", TLXMI_WREG="0")
+        assert (cand, launched) == (DM.TILE_OF[kernel], kernel), (case.name, cand, launched)
+        cand, launched = _traced_conv2d(capfd, case, TLXMI_HALO="0", TLXMI_WREG="0")
+        assert cand in name_of and launched == name_of[cand], (case.name, cand, launched)
+
+
 def test_product_library_reads_no_environment_knob():
     """the A/B knobs (TLXMI_TILE / HALO / TAIL / PP128 / STORE / DEBUG ...) exist only in the tuning flavour
     (libtlxmi_tune.so, -DTLXMI_TUNING).  The product library must not even import getenv."""

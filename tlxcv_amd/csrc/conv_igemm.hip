@@ -494,19 +494,64 @@ __global__ __launch_bounds__(WGM * 128) void conv_igemm_kernel(const ConvArgs a0
 }
 
 static int num_cus() { return device_cus(); }      // core.hip: cached per device
+// The CUs a launch is planned for.  TLXMI_PLAN_SHARED_* in the descriptor's flags: the launch will share the device with another
+// stream's — a property of THIS call, carried by its descriptor; the library keeps no planning state
+static int plan_cus(unsigned flags) { return (flags & TLXMI_PLAN_SHARED_HALF) ? (num_cus() / 2 > 0 ? num_cus() / 2 : 1) : num_cus(); }
+template <typename T> constexpr int kDtype = sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32;
 
 // TLXMI_TRACE_TILES (tuning flavour): one stderr line per launch naming the kernel that actually runs, after every fallback
-// of the dispatcher (the "-> cand N" line below is the choice BEFORE them).  Nothing in the product library.
-#ifdef TLXMI_TUNING
-static void trace_launched(const char* name, int M, int N) {
+// of the dispatcher (the "-> cand N" line below is the choice BEFORE them).  Nothing in the product library (tune_int is constant there).
+static inline void trace_launched(const char* name, int M, int N) {
     if (tune_int("TLXMI_TRACE_TILES", 0)) fprintf(stderr, "launched %s M=%d N=%d\n", name, M, N);
 }
-#else
-static inline void trace_launched(const char*, int, int) {}
-#endif
 
-// resident blocks per CU for a tile shape: LDS bound (160 KiB) and the register allocation hipcc
-// reports for this kernel (128x128: 156 -> 3 waves/SIMD, others <= 128 -> 4)
+// The dispatcher's candidates.  The values are public — TLXMI_TILE / TLXMI_FORCE, tests/dispatch_matrix.py's TILE_OF and tools/ use
+// them — so they do not move.
+enum Cand { IGEMM0, IGEMM1, IGEMM2, IGEMM3, IGEMM4, GEMM256_5, GEMM256_6, PP7, STREAM8, PP9, PP10, W4_11, NC };
+static_assert(IGEMM4 == 4 && PP7 == 7 && W4_11 == 11 && NC == 12, "public candidate numbers");
+enum Family { F_IGEMM, F_GEMM256, F_PP, F_STREAM, F_W4 };
+struct CandInfo {
+    const char* name;   // of the `launched` trace line
+    int bm, bn;         // tile: pixels x channels
+    float eff;          // shape efficiency before the regime rules of choose()
+    int lds;            // LDS bytes of a block; F_IGEMM: DMA ring depth instead (the ring or the fp32 epilogue tile, blocks_per_cu)
+    int cap;            // resident blocks per CU that the register allocation hipcc reports leaves (128x128: 156 -> 3 waves/SIMD, others <= 128 -> 4)
+    Family family;
+};
+constexpr CandInfo kCands[NC] = {
+    {"igemm0", 128, 128, 1.00f, 2, 3, F_IGEMM},
+    {"igemm1", 64, 128, 0.85f, 2, 5, F_IGEMM},
+    {"igemm2", 128, 64, 0.85f, 2, 5, F_IGEMM},
+    {"igemm3", 64, 64, 0.70f, 2, 8, F_IGEMM},
+    {"igemm4", 256, 128, 0.90f, 3, 1, F_IGEMM},                  // 8 waves, 3-deep DMA ring (one block per CU): MFMA-bound layers
+    {"gemm256_5", 256, 256, 1.12f, 128 * 1024, 1, F_GEMM256},    // gemm256.hip: 8 waves, 4-deep ring of 64-byte K steps (pure GEMM rows only)
+    {"gemm256_6", 256, 128, 1.20f, 72 * 1024, 2, F_GEMM256},     // gemm256.hip: 4 waves, 3-deep ring, two workgroups per CU
+    {"pp7", 256, 256, 1.40f, 128 * 1024, 1, F_PP},               // gemm_pp.hip: 8 waves in two antiphase groups, 128-byte K tiles
+    {"stream8", 256, 256, 1.50f, 128 * 1024, 1, F_STREAM},       // gemm_stream.hip: pp7 as a persistent kernel (one K-tile stream per CU)
+    {"pp9", 128, 256, 1.25f, 144 * 1024, 1, F_PP},               // gemm_pp.hip (3x3 convs whose 256 x 256 tiles would fill under half the CUs)
+    {"pp10", 256, 128, 1.25f, 144 * 1024, 1, F_PP},              // gemm_pp.hip (3x3 convs with 128 output channels)
+    {"w4_11", 256, 256, 0.f, 128 * 1024, 1, F_W4},               // gemm_w4.hip: persistent, four waves with 128 x 128 wave tiles (pure GEMM rows)
+};
+// resident blocks per CU for a candidate: LDS bound (160 KiB) and the register cap; 0 = does not fit
+static int blocks_per_cu(const CandInfo& k, int ktiles) {
+    size_t lds = (size_t)k.lds;
+    if (k.family == F_IGEMM) {
+        lds = (size_t)(ktiles > 1 ? k.lds : 1) * (k.bm + k.bn) * 128;
+        if (lds < (size_t)k.bm * k.bn * 4) lds = (size_t)k.bm * k.bn * 4;   // fp32 epilogue tile (gemm256 stores from registers)
+    }
+    lds += 2 * k.bn * sizeof(float);                                        // scale / shift table
+    return (int)((160 * 1024) / lds) > k.cap ? k.cap : (int)((160 * 1024) / lds);
+}
+// Price of a tile shape = (grid quantisation efficiency) x (fill) x (shape efficiency): a launch of B blocks on S = CUs x
+// resident-blocks-per-CU slots runs ceil(B/S) rounds, so B/(rounds*S) of the machine does useful work.  tail > 0: the last, partial
+// round costs `tail` of a tile time instead of a whole one; min_quant: a floor under the first factor.
+static float tile_price(long blocks, long slots, float tail, float fill, float eff, float min_quant = 0.f) {
+    const long rounds = (blocks + slots - 1) / slots;
+    const float quant = tail > 0.f ? (float)blocks / (((float)(blocks / slots) + tail) * slots) : (float)blocks / (float)(rounds * slots);
+    return (quant < min_quant ? min_quant : quant) * fill * eff;
+}
+static float tile_fill(float outputs, long tiles, int bm, int bn) { return outputs / ((float)tiles * bm * bn); }   // wasted work inside partial tiles
+
 template <typename T, int BM, int BN, int WGM, int STAGES> static int launch(const ConvArgs& a, hipStream_t st) {
     ConvArgs b = a;
     b.mtiles = (a.M + BM - 1) / BM;
@@ -556,362 +601,333 @@ static bool pp_conv_offsets_ok(int W, int R, int S, int ph, int pw, int dh, int 
     const long long reach = ((long long)(R - 1) * dh * W + (long long)(S - 1) * dw + 1) * px;
     return lead < (1ll << 30) && reach < (1ll << 30);
 }
-
-// shape efficiency of gemm_pp.hip's 256 x 256 and 128 x 256 tiles in the tile prices (dispatch<T>'s candidates 7 and 9, tlxmi_conv1x1_proj)
-constexpr float kEffPP256 = 1.40f, kEffPP128 = 1.25f;
-
-template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, bool allow_stream = true, bool allow_split = true) {
-    // Tile choice = max over the four shapes of (grid quantisation efficiency) x (shape efficiency):
-    // a launch of B blocks on S = CUs x resident-blocks-per-CU slots runs ceil(B/S) rounds, so B/(rounds*S)
-    // of the machine does useful work; bigger tiles re-use operands better (fewer LDS bytes per MFMA).
-    // The shape efficiency depends on the regime (measured on MI355X, tools/conv_micro.py sweep): layers
-    // that move many output/residual bytes per FLOP (the 1x1 "expand" convs with a skip connection) are
-    // latency/HBM-bound and want many small resident blocks; MFMA-bound layers want the 128x128 tile.
-    // Thin inputs (<= 128 bytes per pixel), stride 1, few output channels: the gather of every tap through LDS is
-    // the bound; conv_halo.hip loads the input rows once and keeps the filters in registers.
-    const bool pool = (a.flags & TLXMI_EPI_MAXPOOL_3S2P1) != 0;
-    if constexpr (sizeof(T) == 2) {
-        const int PB = a.C * 2;
-        if (pool) {
-            // conv -> epilogue -> maxpool(3, 2, 1) in one launch (the ResNet stem, resnet.py:287-290): conv_halo's POOL
-            // variant only; y is [N][Ho/2][Wo/2][y_ld]
-            if (!(a.nchunk == 1 && !a.overhang && a.sh == 1 && a.sw == 1 && a.dh == 1 && a.dw == 1 && conv_halo_pool_ok(a.R, a.S, PB, a.Ho, a.Wo) &&
-                  conv_halo_pool_act_ok(a.act) && !a.strided_n && a.vec_io && !a.res && a.Cout % 8 == 0 && a.Cout <= 128 && a.y_bytes != 0))
-                return fail(TLXMI_ERR_UNSUPPORTED, "conv2d: TLXMI_EPI_MAXPOOL_3S2P1 needs the fp16 4x4 / 16-channel stem geometry (Wo = 112, even Ho, no residual)");
-            HaloArgs h;
-            h.x = a.x; h.w = a.w; h.y = a.y; h.scale = a.scale; h.shift = a.shift; h.res = nullptr;
-            h.N = a.N; h.H = a.H; h.W = a.W; h.Cout = a.Cout; h.R = a.R; h.S = a.S; h.ph = a.ph; h.pw = a.pw;
-            h.Ho = a.Ho; h.Wo = a.Wo; h.HoWo = a.HoWo; h.x_ld = a.x_ld; h.y_ld = a.y_ld; h.res_ld = 0;
-            h.PB = PB; h.Kp_bytes = a.Kp_bytes; h.act = a.act; h.act_param = a.act_param; h.flags = a.flags;
-            h.tpi = a.Ho / 2;                      // a tile = two conv rows
-            h.ntn = (a.Cout + 63) / 64; h.nt = 0;
-            h.PW = a.Wo + a.S - 1;
-            const int ppp = 1024 / PB;
-            h.PWp = (h.PW + ppp - 1) / ppp * ppp;
-            h.nring = 16;                          // 2 rows + 3 halo rows per tile, three tiles resident
-            h.x_bytes = a.x_bytes; h.w_bytes = a.w_bytes;
-            h.y_bytes = (unsigned)((long long)a.N * (a.Ho / 2) * (a.Wo / 2) * a.y_ld * 2);
-            h.res_bytes = 0u;
-            h.pool = 1;
-            trace_launched("halo_pool", a.M, a.Cout);
-            return launch_conv_halo(h, st, num_cus());
-        }
-        const int forced_h = (int)tune_int("TLXMI_HALO", -1);   // tuning flavour: 0 = off (A/B runs)
-        if (forced_h != 0 && a.nchunk == 1 && !a.overhang && a.sh == 1 && a.sw == 1 && a.dh == 1 && a.dw == 1 && (a.R > 1 || a.S > 1) && conv_halo_tile_pixels(a.R, a.S, PB) > 0 &&
-            conv_halo_act_ok(a.act) && !a.strided_n && a.vec_io && a.Cout % 8 == 0 && a.Cout <= 128 && a.y_bytes != 0 &&
-            a.HoWo >= 1024 && (!a.res || (long long)a.M * a.res_ld * 2 < (1ll << 31))) {
-            HaloArgs h;
-            h.pool = 0;
-            h.x = a.x; h.w = a.w; h.y = a.y; h.scale = a.scale; h.shift = a.shift; h.res = a.res;
-            h.N = a.N; h.H = a.H; h.W = a.W; h.Cout = a.Cout; h.R = a.R; h.S = a.S; h.ph = a.ph; h.pw = a.pw;
-            h.Ho = a.Ho; h.Wo = a.Wo; h.HoWo = a.HoWo; h.x_ld = a.x_ld; h.y_ld = a.y_ld; h.res_ld = a.res_ld;
-            h.PB = PB; h.Kp_bytes = a.Kp_bytes; h.act = a.act; h.act_param = a.act_param; h.flags = a.flags;
-            const int tp = conv_halo_tile_pixels(a.R, a.S, PB);
-            h.tpi = (a.HoWo + tp - 1) / tp;
-            h.ntn = (a.Cout + 63) / 64; h.nt = 0;
-            h.PW = a.Wo + a.S - 1;
-            const int span = (a.Wo - 1 + tp - 1) / a.Wo + 1;       // output rows a tile of tp consecutive pixels can touch
-            const int ppp = 1024 / PB;
-            h.PWp = (h.PW + ppp - 1) / ppp * ppp;
-            // ring: tile p is read while tile p+1 is resident and tile p+2 lands — the rows of a tile (span + R - 1)
-            // plus those two later tiles add (<= span each, or a whole first tile of the next image) must fit
-            h.nring = 8;
-            while (h.nring < 2 * (span + a.R - 1) + span) h.nring *= 2;
-            h.x_bytes = a.x_bytes; h.w_bytes = a.w_bytes; h.y_bytes = a.y_bytes;
-            h.res_bytes = a.res ? (unsigned)((long long)a.M * a.res_ld * 2) : 0u;
-            if ((long)h.nring * h.PWp * PB + 512 <= 160 * 1024) {
-                trace_launched("halo", a.M, a.Cout);
-                return launch_conv_halo(h, st, num_cus());
-            }
-        }
+// A plain GEMM of M rows with `ktiles` 128-byte K tiles and no epilogue operand; the tile walk is left to the launcher.
+static Gemm256Args gemm_args(const void* x, const void* w, void* y, int M, int Cout, int x_ld, int y_ld, int kchunks, int ktiles, unsigned x_bytes, unsigned y_bytes) {
+    Gemm256Args g;
+    g.debug = 0; g.conv = 0;
+    g.x = (const char*)x; g.w = (const char*)w; g.y = (char*)y; g.scale = nullptr; g.shift = nullptr; g.res = nullptr;
+    g.M = M; g.Cout = Cout; g.x_ld = x_ld; g.y_ld = y_ld; g.res_ld = 0;
+    g.kchunks = kchunks; g.ksteps = ktiles; g.Kp_bytes = ktiles * 128;
+    g.act = TLXMI_ACT_NONE; g.act_param = 0.f; g.flags = 0; g.mtiles = g.ntiles = 0; g.gn = 1;
+    g.x_bytes = x_bytes; g.y_bytes = y_bytes; g.res_bytes = 0;
+    g.w_bytes = (unsigned)(((size_t)(Cout + 127) / 128 * 128) * (size_t)g.Kp_bytes);
+    return g;
+}
+// A dense (nchunk == 1) convolution as GEMM rows with its epilogue; ksteps in 128-byte steps (gemm256.hip's launch: 64)
+template <typename T> static Gemm256Args gemm_args(const ConvArgs& a) {
+    Gemm256Args g = gemm_args(a.x, a.w, a.y, a.M, a.Cout, a.x_ld, a.y_ld, a.kchunks, a.Kp_bytes / 128, a.x_bytes, a.y_bytes);
+    g.scale = a.scale; g.shift = a.shift; g.res = a.res; g.res_ld = a.res_ld;
+    g.act = a.act; g.act_param = a.act_param; g.flags = a.flags; g.w_bytes = a.w_bytes;
+    g.res_bytes = a.res ? (unsigned)((long long)a.M * a.res_ld * (long long)sizeof(T)) : 0u;
+    return g;
+}
+// conv_halo.hip (fp16).  pool: conv -> epilogue -> maxpool(3, 2, 1) in one launch, y is [N][Ho/2][Wo/2][y_ld]
+static HaloArgs halo_args(const ConvArgs& a, bool pool) {
+    const int PB = a.C * 2;
+    HaloArgs h; h.pool = pool ? 1 : 0;
+    h.x = a.x; h.w = a.w; h.y = a.y; h.scale = a.scale; h.shift = a.shift; h.res = a.res;
+    h.N = a.N; h.H = a.H; h.W = a.W; h.Cout = a.Cout; h.R = a.R; h.S = a.S; h.ph = a.ph; h.pw = a.pw;
+    h.Ho = a.Ho; h.Wo = a.Wo; h.HoWo = a.HoWo; h.x_ld = a.x_ld; h.y_ld = a.y_ld; h.res_ld = a.res_ld;
+    h.PB = PB; h.Kp_bytes = a.Kp_bytes; h.act = a.act; h.act_param = a.act_param; h.flags = a.flags;
+    const int ppp = 1024 / PB;
+    h.ntn = (a.Cout + 63) / 64; h.nt = 0; h.PW = a.Wo + a.S - 1; h.PWp = (h.PW + ppp - 1) / ppp * ppp;
+    h.x_bytes = a.x_bytes; h.w_bytes = a.w_bytes; h.y_bytes = a.y_bytes;
+    h.res_bytes = a.res ? (unsigned)((long long)a.M * a.res_ld * 2) : 0u;
+    if (pool) {
+        h.tpi = a.Ho / 2;                      // a tile = two conv rows
+        h.nring = 16;                          // 2 rows + 3 halo rows per tile, three tiles resident
+        h.y_bytes = (unsigned)((long long)a.N * (a.Ho / 2) * (a.Wo / 2) * a.y_ld * 2);
+    } else {
+        const int tp = conv_halo_tile_pixels(a.R, a.S, PB);
+        h.tpi = (a.HoWo + tp - 1) / tp;
+        const int span = (a.Wo - 1 + tp - 1) / a.Wo + 1;       // output rows a tile of tp consecutive pixels can touch
+        // ring: tile p is read while tile p+1 is resident and tile p+2 lands — the rows of a tile (span + R - 1)
+        // plus those two later tiles add (<= span each, or a whole first tile of the next image) must fit
+        h.nring = 8;
+        while (h.nring < 2 * (span + a.R - 1) + span) h.nring *= 2;
     }
-    if (pool) return fail(TLXMI_ERR_UNSUPPORTED, "conv2d: TLXMI_EPI_MAXPOOL_3S2P1 is an fp16-only fusion");
-    struct Cand { int bm, bn; float eff; };
-    const double flops = 2.0 * a.M * (double)a.Cout * a.kchunks * (16 / (int)sizeof(T));
-    const double obytes = (double)a.M * a.Cout * sizeof(T) * (a.res ? 2.0 : 1.0);
-    const double obi = obytes / flops;
-    // candidate 4 = 256x128 pixels x channels, 8 waves, 3-deep DMA ring (one block per CU): MFMA-bound layers
-    // candidate 5 = gemm256.hip: 256x256, 8 waves, 4-deep ring of 64-byte K steps (pure GEMM rows only)
-    // candidate 6 = gemm256.hip's 256x128 variant: 4 waves, 3-deep ring, two workgroups per CU
-    // candidate 7 = gemm_pp.hip: 256x256, 8 waves in two antiphase groups, 128-byte K tiles
-    // candidate 8 = gemm_stream.hip: candidate 7 as a persistent kernel (one K-tile stream per CU)
-    // candidate 9 = gemm_pp.hip on 128 x 256 tiles (3x3 convs whose 256 x 256 tiles would fill under half the CUs)
-    // candidate 10 = gemm_pp.hip on 256 x 128 tiles (3x3 convs with 128 output channels)
-    // candidate 11 = gemm_w4.hip: 256 x 256 persistent, four waves with 128 x 128 wave tiles (pure GEMM rows)
-    constexpr int NC = 12;
-    Cand cands[NC] = {{128, 128, 1.00f}, {64, 128, 0.85f}, {128, 64, 0.85f}, {64, 64, 0.70f}, {256, 128, 0.90f},
-                      {256, 256, 1.12f}, {256, 128, 1.20f}, {256, 256, kEffPP256}, {256, 256, 1.50f}, {128, 256, kEffPP128},
-                      {256, 128, 1.25f}, {256, 256, 0.f}};
-    const bool gemm128_ok = a.nchunk == 1 && a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && a.sh == 1 && a.sw == 1 && !a.strided_n &&
-                            a.vec_io && a.Cout % 8 == 0 && a.y_bytes != 0 && a.Cout >= 128 && a.ktiles >= 2 &&
-                            (!a.res || (long long)a.M * a.res_ld * (long long)sizeof(T) < (1ll << 31));
-    const bool gemm256_ok = gemm128_ok && a.Cout >= 256;
+    return h;
+}
+// The parts of dispatch<T>.  try_* / split_* return true when they took the call (*rc = its status).
+// Thin inputs (<= 128 bytes per pixel), stride 1, few output channels: the gather of every tap through LDS is
+// the bound; conv_halo.hip loads the input rows once and keeps the filters in registers.
+static bool try_halo(const ConvArgs& a, bool pool, hipStream_t st, int* rc) {
+    const int PB = a.C * 2;
+    const bool geom = a.nchunk == 1 && !a.overhang && a.sh == 1 && a.sw == 1 && a.dh == 1 && a.dw == 1 && !a.strided_n && a.vec_io &&
+                      a.Cout % 8 == 0 && a.Cout <= 128 && a.y_bytes != 0;
+    if (pool) {
+        // the ResNet stem, resnet.py:287-290: conv_halo's POOL variant only
+        const bool ok = geom && conv_halo_pool_ok(a.R, a.S, PB, a.Ho, a.Wo) && conv_halo_pool_act_ok(a.act) && !a.res;
+        if (ok) trace_launched("halo_pool", a.M, a.Cout);
+        *rc = ok ? launch_conv_halo(halo_args(a, true), st, num_cus())
+                 : fail(TLXMI_ERR_UNSUPPORTED, "conv2d: TLXMI_EPI_MAXPOOL_3S2P1 needs the fp16 4x4 / 16-channel stem geometry (Wo = 112, even Ho, no residual)");
+        return true;
+    }
+    const int forced_h = (int)tune_int("TLXMI_HALO", -1);   // tuning flavour: 0 = off (A/B runs)
+    if (!(forced_h != 0 && geom && (a.R > 1 || a.S > 1) && conv_halo_tile_pixels(a.R, a.S, PB) > 0 && conv_halo_act_ok(a.act) &&
+          a.HoWo >= 1024 && (!a.res || (long long)a.M * a.res_ld * 2 < (1ll << 31)))) return false;
+    const HaloArgs h = halo_args(a, false);
+    if ((long)h.nring * h.PWp * PB + 512 > 160 * 1024) return false;
+    trace_launched("halo", a.M, a.Cout);
+    *rc = launch_conv_halo(h, st, num_cus());
+    return true;
+}
+struct Shape {      // what the layer's shape admits
+    bool gemm128_ok, gemm256_ok, pp_conv128_ok, pp_conv_ok;   // plain GEMM rows / gemm_pp.hip's CONV mode, for tiles of 128 / 256 channels
+    bool as_conv, strided1x1;                                 // as_conv: needs the gather of CONV mode
+    int tpk;                                                  // K tiles per tap
+};
+template <typename T> static Shape shape_of(const ConvArgs& a) {
+    Shape s;
+    s.gemm128_ok = a.nchunk == 1 && a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && a.sh == 1 && a.sw == 1 && !a.strided_n &&
+                   a.vec_io && a.Cout % 8 == 0 && a.y_bytes != 0 && a.Cout >= 128 && a.ktiles >= 2 &&
+                   (!a.res || (long long)a.M * a.res_ld * (long long)sizeof(T) < (1ll << 31));
+    s.gemm256_ok = s.gemm128_ok && a.Cout >= 256;
     // 3x3 (R x 3) convs on the antiphase GEMM kernel: a 128-byte K tile must lie inside one filter tap
-    const int tpk = a.cpt / 8;     // K tiles per tap
+    s.tpk = a.cpt / 8;
     // (also the strided 1x1 projection shortcuts, resnet.py:246-261: one "tap", rows gathered at stride 2)
-    const bool strided1x1 = a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && (a.sh > 1 || a.sw > 1);
-    const bool as_conv = !(a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && a.sh == 1 && a.sw == 1);   // needs the gather of CONV mode
+    s.strided1x1 = a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && (a.sh > 1 || a.sw > 1);
+    s.as_conv = !(a.R == 1 && a.S == 1 && a.ph == 0 && a.pw == 0 && a.sh == 1 && a.sw == 1);
     // dilated 3x3 convs (DeepLabV3) take the same path; TLXMI_PP_DIL=0 (tuning flavour, A/B) keeps them on the tiles above
     const bool dilated = a.dh != 1 || a.dw != 1;
     const bool pp_dil_ok = !dilated || (tune_int("TLXMI_PP_DIL", 1) != 0 && pp_conv_offsets_ok(a.W, a.R, a.S, a.ph, a.pw, a.dh, a.dw, a.x_ld, (int)sizeof(T)));
-    const bool pp_conv128_ok = a.nchunk == 1 && !a.overhang && ((a.S == 3 && a.R <= 3) || strided1x1) && pp_dil_ok && !a.strided_n &&
-                               a.vec_io && a.Cout % 8 == 0 && a.Cout >= 128 && a.y_bytes != 0 && a.cpt % 8 == 0 && (tpk & (tpk - 1)) == 0 &&
-                               (!a.res || (long long)a.M * a.res_ld * (long long)sizeof(T) < (1ll << 31));
-    const bool pp_conv_ok = pp_conv128_ok && a.Cout >= 256;
-    // K = 128 (two K tiles) and up to 512 output channels on many rows: HBM-bound; the filter-in-registers kernel reads every
-    // activation row once and writes every output row once (gemm_wreg.hip).  K = 256: only the wide layers (768 / 1024 channels:
-    // qkv / fc1 of Swin-B stage 2, 60 -> 55 and 112 -> 87 us at batch 128; 256 / 512 channels measure equal or slower — 128 filter
-    // registers a wave leave one workgroup of <= 8 waves per CU).  TLXMI_WREG (tuning flavour): 0 the tiled kernels, 2 K = 128 only,
-    // 3 every K = 256 width.
+    s.pp_conv128_ok = a.nchunk == 1 && !a.overhang && ((a.S == 3 && a.R <= 3) || s.strided1x1) && pp_dil_ok && !a.strided_n &&
+                      a.vec_io && a.Cout % 8 == 0 && a.Cout >= 128 && a.y_bytes != 0 && a.cpt % 8 == 0 && (s.tpk & (s.tpk - 1)) == 0 &&
+                      (!a.res || (long long)a.M * a.res_ld * (long long)sizeof(T) < (1ll << 31));
+    s.pp_conv_ok = s.pp_conv128_ok && a.Cout >= 256;
+    return s;
+}
+// Whether TLXMI_TILE / TLXMI_FORCE may put the layer on candidate c (the cost model has its own, narrower rules in choose())
+static bool can_force(int c, const ConvArgs& a, const Shape& s) {
+    if (c < 0 || c >= NC || (kCands[c].bn == 128 && a.Cout <= 64)) return false;
+    switch (c) {
+        case IGEMM4: return a.ktiles >= 4;      // (its 3-deep ring needs the >= 4 K tiles the cost model asks of it)
+        case GEMM256_5: case GEMM256_6: case STREAM8: case W4_11: return s.gemm256_ok;
+        case PP7: case PP9: return s.gemm256_ok || s.pp_conv_ok;
+        case PP10: return s.pp_conv128_ok || s.gemm128_ok;
+        default: return true;
+    }
+}
+// K = 128 (two K tiles) and up to 512 output channels on many rows: HBM-bound; the filter-in-registers kernel reads every
+// activation row once and writes every output row once (gemm_wreg.hip).  K = 256: only the wide layers (768 / 1024 channels:
+// qkv / fc1 of Swin-B stage 2, 60 -> 55 and 112 -> 87 us at batch 128; 256 / 512 channels measure equal or slower — 128 filter
+// registers a wave leave one workgroup of <= 8 waves per CU).  TLXMI_WREG (tuning flavour): 0 the tiled kernels, 2 K = 128 only,
+// 3 every K = 256 width.
+template <typename T> static bool try_wreg(const ConvArgs& a, const Shape& s, hipStream_t st, int* rc) {
     const long wreg = tune_int("TLXMI_WREG", 1);
     const bool wreg_k256 = a.kchunks == 32 && wreg != 2 && a.M >= 32768 && (a.Cout >= 768 || wreg == 3);
-    if (gemm128_ok && sizeof(T) == 2 && (a.kchunks == 16 || wreg_k256) && a.M >= 16384 && a.pp_slices <= 1 && !a.out_f32 && wreg &&
-        tune_int("TLXMI_TILE", -1) < 0) {
-        Gemm256Args g;
-        g.debug = 0; g.conv = 0;
-        g.x = a.x; g.w = a.w; g.y = a.y; g.scale = a.scale; g.shift = a.shift; g.res = a.res;
-        g.M = a.M; g.Cout = a.Cout; g.x_ld = a.x_ld; g.y_ld = a.y_ld; g.res_ld = a.res_ld;
-        g.kchunks = a.kchunks; g.ksteps = a.Kp_bytes / 128; g.Kp_bytes = a.Kp_bytes;
-        g.act = a.act; g.act_param = a.act_param; g.flags = a.flags; g.mtiles = g.ntiles = 0; g.gn = 1;
-        g.x_bytes = a.x_bytes; g.w_bytes = a.w_bytes; g.y_bytes = a.y_bytes;
-        g.res_bytes = a.res ? (unsigned)((long long)a.M * a.res_ld * (long long)sizeof(T)) : 0u;
-        if (gemm_wreg_ok(TLXMI_F16, g)) {
-            trace_launched("wreg", a.M, a.Cout);
-            return launch_gemm_wreg(g, st);
+    if (!(s.gemm128_ok && sizeof(T) == 2 && (a.kchunks == 16 || wreg_k256) && a.M >= 16384 && a.pp_slices <= 1 && !a.out_f32 && wreg &&
+          tune_int("TLXMI_TILE", -1) < 0)) return false;
+    const Gemm256Args g = gemm_args<T>(a);
+    if (!gemm_wreg_ok(TLXMI_F16, g)) return false;
+    trace_launched("wreg", a.M, a.Cout);
+    *rc = launch_gemm_wreg(g, st);
+    return true;
+}
+// One workgroup per CU: the last round of a 256x256 launch runs a whole tile time however few tiles it
+// has.  When it would be at most half full, the rows of the full rounds go to the 256x256 kernel and the
+// remaining rows to a second launch of the same kernel on 128x256 tiles (gemm_pp128): twice the tiles, about
+// 0.6 of the time, still one round (split_rows).
+// mode = TLXMI_TAIL (A/B): 0 no split, 1 small tiles only (4 * left <= CUs), default: 128 x 256 tiles (2 * left <= CUs); rows: the split applies if pp7 is chosen
+struct TailPlan { int mode; bool rows; long t256, full_rounds; };
+static TailPlan tail_plan(const ConvArgs& a, const Shape& s, int cus, bool allow_split) {
+    TailPlan t;
+    t.t256 = (long)((a.M + 255) / 256) * ((a.Cout + 255) / 256);
+    t.full_rounds = t.t256 / cus;
+    // (a shared device, TLXMI_PLAN_SHARED_*: no tail splits — the other stream's launches fill a short last round, the extra
+    //  launches only cost: ResNet-50 batch 256 in two halves 3.70 -> 3.59 ms)
+    const bool shared = (a.flags & (TLXMI_PLAN_SHARED_HALF | TLXMI_PLAN_SHARED_FULL)) != 0;
+    t.mode = (int)tune_int("TLXMI_TAIL", shared ? 0 : 2);
+    t.rows = s.gemm256_ok && allow_split && t.mode != 0 && t.full_rounds >= 1 && (t.t256 % cus) != 0 &&
+             (t.mode == 1 ? 4 : 2) * (t.t256 % cus) <= cus;
+    return t;
+}
+
+// Tile choice = max over the candidates of tile_price: bigger tiles re-use operands better (fewer LDS bytes per MFMA).
+// The shape efficiency depends on the regime (measured on MI355X, tools/conv_micro.py sweep): layers
+// that move many output/residual bytes per FLOP (the 1x1 "expand" convs with a skip connection) are
+// latency/HBM-bound and want many small resident blocks; MFMA-bound layers want the 128x128 tile.
+// Launches nothing.
+template <typename T> static int choose(const ConvArgs& a, const Shape& s, const TailPlan& t, int cus, bool allow_stream, bool allow_split) {
+    int best = 0; float best_score = -1.f;
+    if (a.pp_slices > 1) {          // K slices: only the gemm_pp convolution candidates take them (pp7, pp9: >= 256 channels out; pp10: 128)
+        for (int c : {PP7, PP9, PP10}) {
+            const CandInfo& k = kCands[c];
+            if (c == PP10 ? !s.pp_conv128_ok : !s.pp_conv_ok) continue;
+            const long tiles = (long)((a.M + k.bm - 1) / k.bm) * ((a.Cout + k.bn - 1) / k.bn);
+            const float score = tile_price(tiles * a.pp_slices, cus, 0.f, tile_fill((float)a.M * a.Cout, tiles, k.bm, k.bn), k.eff);
+            if (score > best_score) { best_score = score; best = c; }
         }
+        return best;
     }
-    if (!gemm256_ok) cands[5].eff = cands[6].eff = cands[8].eff = cands[11].eff = 0.f;
-    if (!gemm256_ok && !pp_conv_ok) cands[7].eff = 0.f;
+    const double flops = 2.0 * a.M * (double)a.Cout * a.kchunks * (16 / (int)sizeof(T));
+    const double obytes = (double)a.M * a.Cout * sizeof(T) * (a.res ? 2.0 : 1.0);
+    const double obi = obytes / flops;
+    float eff[NC];
+    for (int c = 0; c < NC; ++c) eff[c] = kCands[c].eff;
+    if (!s.gemm256_ok) eff[GEMM256_5] = eff[GEMM256_6] = eff[STREAM8] = eff[W4_11] = 0.f;
+    if (!s.gemm256_ok && !s.pp_conv_ok) eff[PP7] = 0.f;
     // 128 x 256 tiles for plain GEMM rows too (few row tiles: 7 x 7 stage, 2048 -> 512); TLXMI_PP128=0: convs only (A/B)
     const int pp128_gemm = (int)tune_int("TLXMI_PP128", 1);
-    if (!pp_conv_ok && !(gemm256_ok && pp128_gemm)) cands[9].eff = 0.f;
-    if (!pp_conv128_ok) cands[10].eff = 0.f;      // (1x1 layers: reachable through TLXMI_TILE=10 only)
-    cands[5].eff = 0.f;   // superseded by candidate 7 (same tile, antiphase wave groups); kept for A/B runs (TLXMI_TILE=5)
-    if (obi >= 0.0015 || a.ktiles < 4) cands[4].eff = 0.f;
+    if (!s.pp_conv_ok && !(s.gemm256_ok && pp128_gemm)) eff[PP9] = 0.f;
+    if (!s.pp_conv128_ok) eff[PP10] = 0.f;      // (1x1 layers: reachable through TLXMI_TILE=10 only)
+    eff[GEMM256_5] = 0.f;   // superseded by pp7 (same tile, antiphase wave groups); kept for A/B runs (TLXMI_TILE=5)
+    if (obi >= 0.0015 || a.ktiles < 4) eff[IGEMM4] = 0.f;
     // regimes by output bytes per FLOP (tools/ab_tiles.py sweep over the ResNet-50 / ViT-B / Swin-B layer shapes):
     // the 256-row GEMM kernels win up to ~0.005 (256x256) / ~0.02 (256x128, two workgroups per CU); beyond that
     // the layer is HBM / latency-bound and wants many small resident blocks
-    if (obi >= 0.005) cands[7].eff = cands[8].eff = cands[9].eff = 0.f;
-    if (obi >= 0.020) cands[6].eff = 0.f;
-    if (obi >= 0.020 || (obi >= 0.010 && a.ktiles == 1)) { cands[0].eff = 0.65f; cands[1].eff = 0.80f; cands[2].eff = 0.85f; cands[3].eff = 1.00f; }   // 64 -> 256 (+ skip) at 56x56: one K step
-    else if (obi >= 0.010) { cands[0].eff = 1.00f; cands[1].eff = 0.95f; cands[2].eff = 0.95f; cands[3].eff = 0.85f; }   // 128 -> 512 + skip at 28x28
-    else if (obi >= 0.0015) { cands[0].eff = 0.85f; cands[1].eff = 0.90f; cands[2].eff = 1.00f; cands[3].eff = 0.90f; }
-    if (!allow_stream) cands[7].eff = cands[8].eff = 0.f;
+    if (obi >= 0.005) eff[PP7] = eff[STREAM8] = eff[PP9] = 0.f;
+    if (obi >= 0.020) eff[GEMM256_6] = 0.f;
+    if (obi >= 0.020 || (obi >= 0.010 && a.ktiles == 1)) { eff[IGEMM0] = 0.65f; eff[IGEMM1] = 0.80f; eff[IGEMM2] = 0.85f; eff[IGEMM3] = 1.00f; }   // 64 -> 256 (+ skip) at 56x56: one K step
+    else if (obi >= 0.010) { eff[IGEMM0] = 1.00f; eff[IGEMM1] = 0.95f; eff[IGEMM2] = 0.95f; eff[IGEMM3] = 0.85f; }   // 128 -> 512 + skip at 28x28
+    else if (obi >= 0.0015) { eff[IGEMM0] = 0.85f; eff[IGEMM1] = 0.90f; eff[IGEMM2] = 1.00f; eff[IGEMM3] = 0.90f; }
+    if (!allow_stream) eff[PP7] = eff[STREAM8] = 0.f;
     // the persistent kernel hides the plain epilogue but not the GELU arithmetic (measured: fc1 of ViT-B)
     // (except with few row tiles inside a two-stream forward planned for the whole device — Swin-B stage 3, fc1 12544 x 512 ->
     //  2048 at half batch 64: forward 7.88 -> 7.78 ms with the persistent kernel, tools/tile_search.py; ViT-B/16's fc1: equal)
     const bool gelu_stream_ok = (a.flags & TLXMI_PLAN_SHARED_FULL) && a.M < 16384 && a.ktiles >= 8;
-    if (a.act == TLXMI_ACT_GELU && !gelu_stream_ok && !tune_int("TLXMI_GELU_STREAM", 0)) cands[8].eff = 0.f;
-    // One workgroup per CU: the last round of a 256x256 launch runs a whole tile time however few tiles it
-    // has.  When it would be at most half full, the rows of the full rounds go to the 256x256 kernel and the
-    // remaining rows to a second launch of the same kernel on 128x256 tiles (gemm_pp128): twice the tiles, about
-    // 0.6 of the time, still one round (tail split, below).
-    const long t256 = (long)((a.M + 255) / 256) * ((a.Cout + 255) / 256);
-    // TLXMI_PLAN_SHARED_* in the descriptor's flags (tuning flavour: TLXMI_PLAN_CUS too): the launch will share the device
-    // with another stream's — a property of THIS call, carried by its descriptor; the library keeps no planning state
-    const bool shared = (a.flags & (TLXMI_PLAN_SHARED_HALF | TLXMI_PLAN_SHARED_FULL)) != 0;
-    const int cus = tune_int("TLXMI_PLAN_CUS", 0) > 0 ? (int)tune_int("TLXMI_PLAN_CUS", 0)
-                    : (a.flags & TLXMI_PLAN_SHARED_HALF) ? (num_cus() / 2 > 0 ? num_cus() / 2 : 1) : num_cus();
-    const long full_rounds = t256 / cus;
-    // TLXMI_TAIL (A/B): 0 no split, 1 small tiles only (4 * left <= CUs), default: 128 x 256 tiles (2 * left <= CUs)
-    // (a shared device, TLXMI_PLAN_SHARED_*: no tail splits — the other stream's launches fill a short last round, the extra
-    //  launches only cost: ResNet-50 batch 256 in two halves 3.70 -> 3.59 ms)
-    const int tail_mode = (int)tune_int("TLXMI_TAIL", shared ? 0 : 2);
-    const bool tail_split = gemm256_ok && allow_split && tail_mode != 0 && full_rounds >= 1 && (t256 % cus) != 0 &&
-                            (tail_mode == 1 ? 4 : 2) * (t256 % cus) <= cus;
-    int best = 0;
-    float best_score = -1.f;
-    for (int i = 0; i < NC; ++i) {
-        const int bm = cands[i].bm, bn = cands[i].bn;
-        if (cands[i].eff <= 0.f) continue;
-        if (bn == 128 && a.Cout <= 64) continue;
-        size_t lds = (i == 5 || i >= 7) ? (size_t)((i == 9 || i == 10) ? 144 : 128) * 1024 : i == 6 ? (size_t)72 * 1024 : (size_t)(a.ktiles > 1 ? (i == 4 ? 3 : 2) : 1) * (bm + bn) * 128;
-        if (i < 5 && lds < (size_t)bm * bn * 4) lds = (size_t)bm * bn * 4;   // fp32 epilogue tile (gemm256 stores from registers)
-        lds += 2 * bn * sizeof(float);                                        // scale / shift table
-        int per_cu = (int)((160 * 1024) / lds);
+    if (a.act == TLXMI_ACT_GELU && !gelu_stream_ok && !tune_int("TLXMI_GELU_STREAM", 0)) eff[STREAM8] = 0.f;
+    for (int c = 0; c < NC; ++c) {
+        const CandInfo& k = kCands[c];
+        if (eff[c] <= 0.f || (k.bn == 128 && a.Cout <= 64)) continue;
+        const int per_cu = blocks_per_cu(k, a.ktiles);
         if (per_cu < 1) continue;
-        const int reg_cap = i == 6 ? 2 : i >= 4 ? 1 : (bm == 128 && bn == 128) ? 3 : ((bm == 64 && bn == 64) ? 8 : 5);
-        if (per_cu > reg_cap) per_cu = reg_cap;
-        const long blocks = (long)((a.M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn) * a.nchunk;
+        const long blocks = (long)((a.M + k.bm - 1) / k.bm) * ((a.Cout + k.bn - 1) / k.bn) * a.nchunk;
         const long slots = (long)cus * per_cu;
-        const long rounds = (blocks + slots - 1) / slots;
-        float quant = (float)blocks / (float)(rounds * slots);
-        if (i == 7 && tail_split) quant = (float)blocks / (((float)full_rounds + 0.6f) * slots);   // the tail round: ~0.6 of a tile time
+        float tail = 0.f, min_quant = 0.f;
+        if (c == PP7 && t.rows) tail = 0.6f;   // the tail round: ~0.6 of a tile time
         // the persistent kernel balances its own tail (gemm_stream.hip: a last round at most half full, or fewer tiles than half
         // the CUs, runs as half-height tiles at ~0.7 of a tile time), shared device or not
-        if (i == 8 && blocks % slots != 0 && 2 * (blocks % slots) <= slots) quant = (float)blocks / (((float)(blocks / slots) + 0.7f) * slots);
+        if (c == STREAM8 && blocks % slots != 0 && 2 * (blocks % slots) <= slots) tail = 0.7f;
         // a two-stream forward planned for the whole device: the CUs a persistent launch leaves idle serve the other stream, and
         // on long K loops the K-tile stream beats half-height tiles even when it fills under half a round — Swin-B stage 3 at
         // half batch 64, qkv 12544 x 512 -> 1536 and fc2 2048 -> 512: forward 7.88 -> 7.67 ms (tools/tile_search.py on the graph
         // replay; the 512 -> 512 proj and every other layer shape measured no gain and keep their price)
-        if (i == 8 && (a.flags & TLXMI_PLAN_SHARED_FULL) && a.ktiles >= 8 && (a.Cout >= 1024 || a.ktiles >= 32) && quant < 0.7f) quant = 0.7f;
-        // 3x3 convs on the antiphase kernel: a short last round is cut off along the image axis (below)
-        if ((i == 7 || i == 9 || i == 10) && as_conv && allow_split && tail_mode != 0 && blocks / slots >= 1 &&
-            blocks % slots != 0 && 4 * (blocks % slots) <= slots)
-            quant = (float)blocks / (((float)(blocks / slots) + 0.4f) * slots);
-        // wasted work inside partial tiles
-        const float fill = ((float)a.M * a.Cout * a.nchunk) / ((float)blocks * bm * bn);
-        const float score = quant * fill * cands[i].eff;
-        if (score > best_score) { best_score = score; best = i; }
+        if (c == STREAM8 && (a.flags & TLXMI_PLAN_SHARED_FULL) && a.ktiles >= 8 && (a.Cout >= 1024 || a.ktiles >= 32)) min_quant = 0.7f;
+        // 3x3 convs on the antiphase kernel: a short last round is cut off along the image axis (split_images)
+        if (k.family == F_PP && s.as_conv && allow_split && t.mode != 0 && blocks / slots >= 1 && blocks % slots != 0 && 4 * (blocks % slots) <= slots)
+            tail = 0.4f;
+        const float score = tile_price(blocks, slots, tail, tile_fill((float)a.M * a.Cout * a.nchunk, blocks, k.bm, k.bn), eff[c], min_quant);
+        if (score > best_score) { best_score = score; best = c; }
     }
-    // tuning / test aid: TLXMI_TILE=<candidate> forces a tile shape (read on every call, so one process can
-    // compare candidates: tools/ab_tiles.py, tests/test_gemm_gpu.py)
-    if (a.pp_slices > 1) {          // K slices: only the gemm_pp convolution candidates take them (7, 9: >= 256 channels out; 10: 128)
-        if (!(as_conv && (pp_conv_ok || pp_conv128_ok))) return fail(TLXMI_ERR_UNSUPPORTED, "conv2d_splitk: this layer has no gemm_pp convolution path");
-        best = -1;
-        best_score = -1.f;
-        for (int i : {7, 9, 10}) {
-            if ((i == 10 ? !pp_conv128_ok : !pp_conv_ok)) continue;
-            const long blocks = (long)((a.M + cands[i].bm - 1) / cands[i].bm) * ((a.Cout + cands[i].bn - 1) / cands[i].bn) * a.pp_slices;
-            const long rounds = (blocks + cus - 1) / cus;
-            const float fill = ((float)a.M * a.Cout) / ((float)(blocks / a.pp_slices) * cands[i].bm * cands[i].bn);
-            const float score = (float)blocks / (float)(rounds * cus) * fill * (i == 7 ? 1.40f : 1.25f);
-            if (score > best_score) { best_score = score; best = i; }
+    return best;
+}
+
+template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, bool allow_stream = true, bool allow_split = true);
+// Image-axis tail split: one workgroup per CU, so a last round with few tiles costs a whole tile time.  The
+// images whose rows fill the whole rounds stay on this kernel; the last few images are a convolution of their
+// own on the small tiles (28 x 28 stage of ResNet-50 at batch 256: 784 tiles = 3.06 rounds -> 250 + 6 images).
+template <typename T> static bool split_images(const ConvArgs& a, const CandInfo& k, int cus, hipStream_t st, bool allow_stream, int* rc) {
+    const long ntn = (a.Cout + k.bn - 1) / k.bn, tiles = (long)((a.M + k.bm - 1) / k.bm) * ntn;
+    const long full = tiles / cus, left = tiles % cus;
+    if (!(full >= 1 && left != 0 && 4 * left <= cus)) return false;
+    const int n1 = (int)(((full * cus) / ntn) * k.bm / a.HoWo);
+    if (!(n1 >= 1 && n1 < a.N)) return false;
+    ConvArgs lo = a, hi = a;
+    lo.N = n1; lo.M = n1 * a.HoWo; hi.N = a.N - n1; hi.M = hi.N * a.HoWo;
+    const size_t xoff = (size_t)n1 * a.H * a.W * a.x_ld * sizeof(T), yoff = (size_t)n1 * a.HoWo * a.y_ld * sizeof(T);
+    hi.x = a.x + xoff; hi.y = a.y + yoff;
+    if (a.res) hi.res = a.res + (size_t)n1 * a.HoWo * a.res_ld * sizeof(T);
+    lo.x_bytes = (unsigned)xoff; hi.x_bytes = a.x_bytes - lo.x_bytes;
+    lo.y_bytes = (unsigned)yoff; hi.y_bytes = a.y_bytes - lo.y_bytes;
+    *rc = dispatch<T>(lo, st, allow_stream, false);
+    if (*rc == TLXMI_OK) *rc = dispatch<T>(hi, st, false, false);
+    return true;
+}
+// Row tail split of pp7: rows of the full rounds (whole M tiles) -> this candidate; the rest -> best small-tile candidate
+template <typename T> static bool split_rows(const ConvArgs& a, const TailPlan& t, int cus, hipStream_t st, int* rc) {
+    const int nt = (a.Cout + 255) / 256, m_split = (int)((t.full_rounds * cus) / nt) * 256;
+    if (!(m_split > 0 && m_split < a.M)) return false;
+    ConvArgs lo = a, hi = a;
+    lo.N = 1; lo.H = lo.Ho = 1; lo.W = lo.Wo = m_split; lo.HoWo = lo.M = m_split;
+    hi.N = 1; hi.H = hi.Ho = 1; hi.W = hi.Wo = a.M - m_split; hi.HoWo = hi.M = a.M - m_split;
+    const size_t xoff = (size_t)m_split * a.x_ld * sizeof(T), yoff = (size_t)m_split * a.y_ld * sizeof(T);
+    hi.x = a.x + xoff; hi.y = a.y + yoff;
+    if (a.res) hi.res = a.res + (size_t)m_split * a.res_ld * sizeof(T);
+    lo.x_bytes = (unsigned)xoff; hi.x_bytes = a.x_bytes - lo.x_bytes;
+    lo.y_bytes = (unsigned)yoff; hi.y_bytes = a.y_bytes - lo.y_bytes;
+    lo.y_nstride = hi.y_nstride = 0; lo.res_nstride = hi.res_nstride = 0;
+    *rc = dispatch<T>(lo, st, true);     // t256 % cus == 0 there: no further split
+    if (*rc != TLXMI_OK) return true;
+    // a short tail (one round of 128x128 tiles) runs best on the small-tile kernels (measured: ViT fc1,
+    // Swin stage-3 fc1); a longer one on the 128 x 256 antiphase kernel (ViT proj / fc2: -3 %): the same kernel, twice the tiles,
+    // half the time each, still one round (2 * left <= CUs)
+    const bool small = t.mode == 1 || 4 * (t.t256 % cus) <= cus;
+    if (!small) trace_launched(kCands[PP9].name, hi.M, hi.Cout);
+    *rc = small ? dispatch<T>(hi, st, false) : launch_gemm_pp128(kDtype<T>, gemm_args<T>(hi), st);
+    return true;
+}
+// Launches candidate c, after the fallbacks of the kernels that refuse the operands: w4 -> stream -> pp
+template <typename T> static int launch_candidate(int c, const ConvArgs& a, const Shape& s, int cus, hipStream_t st) {
+    if (kCands[c].family == F_IGEMM) {
+        trace_launched(kCands[c].name, a.M, a.Cout);
+        switch (c) {
+            case IGEMM0: return launch<T, 128, 128, 2, 2>(a, st);
+            case IGEMM1: return launch<T, 64, 128, 2, 2>(a, st);
+            case IGEMM2: return launch<T, 128, 64, 2, 2>(a, st);
+            case IGEMM4: return launch<T, 256, 128, 4, 3>(a, st);
+            default: return launch<T, 64, 64, 2, 2>(a, st);
         }
     }
-    const int forced = a.pp_slices > 1 ? -1 : (int)tune_int("TLXMI_TILE", -1);
-    // (candidate 4's 3-deep ring needs the >= 4 K tiles the cost model asks of it above)
-    if (forced >= 0 && forced < NC && !(cands[forced].bn == 128 && a.Cout <= 64) && (forced != 4 || a.ktiles >= 4) &&
-        (forced < 5 || (forced <= 9 && gemm256_ok) || ((forced == 7 || forced == 9) && pp_conv_ok) ||
-         (forced == 10 && (pp_conv128_ok || gemm128_ok)) || (forced == 11 && gemm256_ok))) best = forced;
+    Gemm256Args g = gemm_args<T>(a);
+    if (s.as_conv) {      // the gemm_pp candidates as a convolution
+        g.conv = 1;
+        g.cH = a.H; g.cW = a.W; g.cWo = a.Wo; g.cHoWo = a.HoWo; g.csh = a.sh; g.csw = a.sw; g.cph = a.ph; g.cpw = a.pw;
+        g.cdh = a.dh; g.cdw = a.dw; g.ctaps = a.R * a.S; g.ctshift = 0;
+        while ((1 << g.ctshift) < s.tpk) ++g.ctshift;
+    }
+#ifdef TLXMI_TUNING      // gemm_w4.hip is part of the tuning flavour only (make tune): the product never dispatches it (eff = 0)
+    if (c == W4_11 && gemm_w4_ok(kDtype<T>, g)) {
+        trace_launched(kCands[c].name, a.M, a.Cout);
+        return launch_gemm_w4(kDtype<T>, g, st, cus);
+    }
+#endif
+    if (c == W4_11) c = STREAM8;
+    if (c == STREAM8 && !gemm_stream_ok(kDtype<T>, g)) c = PP7;
+    trace_launched(kCands[c].name, a.M, a.Cout);
+    if (c == STREAM8) return launch_gemm_stream(kDtype<T>, g, st, cus);
+    if (kCands[c].family == F_GEMM256) {
+        g.ksteps = a.Kp_bytes / 64;
+        return launch_gemm256(kDtype<T>, c - GEMM256_5, g, st);
+    }
+    if (a.pp_slices > 1) {
+        g.kslices = a.pp_slices; g.kt_slice = (g.ksteps + a.pp_slices - 1) / a.pp_slices;
+        g.slice_bytes = (long long)a.M * a.y_ld * 4;
+        g.res = nullptr; g.scale = g.shift = nullptr;
+    }
+    return c == PP7 ? launch_gemm_pp(kDtype<T>, g, st) : c == PP9 ? launch_gemm_pp128(kDtype<T>, g, st) : launch_gemm_pp_n128(kDtype<T>, g, st);
+}
+
+template <typename T> static int dispatch(const ConvArgs& a, hipStream_t st, bool allow_stream, bool allow_split) {
+    int rc;
+    const bool pool = (a.flags & TLXMI_EPI_MAXPOOL_3S2P1) != 0;
+    if (sizeof(T) == 2 && try_halo(a, pool, st, &rc)) return rc;
+    if (pool) return fail(TLXMI_ERR_UNSUPPORTED, "conv2d: TLXMI_EPI_MAXPOOL_3S2P1 is an fp16-only fusion");
+    const Shape s = shape_of<T>(a);
+    if (try_wreg<T>(a, s, st, &rc)) return rc;
+    if (a.pp_slices > 1 && !(s.as_conv && (s.pp_conv_ok || s.pp_conv128_ok))) return fail(TLXMI_ERR_UNSUPPORTED, "conv2d_splitk: this layer has no gemm_pp convolution path");
+    // (tuning flavour: TLXMI_PLAN_CUS overrides the CU count of this function's plan only)
+    const int cus = tune_int("TLXMI_PLAN_CUS", 0) > 0 ? (int)tune_int("TLXMI_PLAN_CUS", 0) : plan_cus(a.flags);
+    const TailPlan t = tail_plan(a, s, cus, allow_split);
+    int best = choose<T>(a, s, t, cus, allow_stream, allow_split);
+    // tuning / test aid: TLXMI_TILE=<candidate> forces a tile shape (read on every call, so one process can
+    // compare candidates: tools/ab_tiles.py, tests/test_gemm_gpu.py)
+    if (const int tile = (int)tune_int("TLXMI_TILE", -1); a.pp_slices <= 1 && can_force(tile, a, s)) best = tile;
 #ifdef TLXMI_TUNING
     // TLXMI_FORCE="M:K:N:R:s=cand,...": force a candidate for one layer shape (tools/tile_search.py)
     if (const char* fs = getenv("TLXMI_FORCE")) {
         char key[96];
         snprintf(key, sizeof key, "%d:%d:%d:%d:%d=", a.M, a.C * a.R * a.S, a.Cout, a.R, a.sh);
         const char* hit = strstr(fs, key);
-        if (hit && (hit == fs || hit[-1] == ',')) {
-            const int f = atoi(hit + strlen(key));
-            if (f >= 0 && f < NC && !(cands[f].bn == 128 && a.Cout <= 64) && (f != 4 || a.ktiles >= 4) &&
-                (f < 5 || (f <= 9 && gemm256_ok) || ((f == 7 || f == 9) && pp_conv_ok) || (f == 10 && (pp_conv128_ok || gemm128_ok)) || (f == 11 && gemm256_ok))) best = f;
-        }
+        if (hit && (hit == fs || hit[-1] == ',') && can_force(atoi(hit + strlen(key)), a, s)) best = atoi(hit + strlen(key));
     }
     if (tune_int("TLXMI_TRACE_TILES", 0))
         fprintf(stderr, "tile M=%d K=%d N=%d R=%d s=%d res=%d plan_cus=%d -> cand %d (%dx%d)\n", a.M, a.C * a.R * a.S, a.Cout, a.R, a.sh, a.res ? 1 : 0, cus, best,
-                cands[best].bm, cands[best].bn);
+                kCands[best].bm, kCands[best].bn);
 #endif
-    if ((best == 7 || best == 9 || best == 10) && as_conv && allow_split && tail_mode != 0 && a.pp_slices <= 1) {
-        // Image-axis tail split: one workgroup per CU, so a last round with few tiles costs a whole tile time.  The
-        // images whose rows fill the whole rounds stay on this kernel; the last few images are a convolution of their
-        // own on the small tiles (28 x 28 stage of ResNet-50 at batch 256: 784 tiles = 3.06 rounds -> 250 + 6 images).
-        const int bm = cands[best].bm, bn = cands[best].bn;
-        const long ntn = (a.Cout + bn - 1) / bn;
-        const long tiles = (long)((a.M + bm - 1) / bm) * ntn;
-        const long full = tiles / cus, left = tiles % cus;
-        if (full >= 1 && left != 0 && 4 * left <= cus) {
-            const int n1 = (int)(((full * cus) / ntn) * bm / a.HoWo);
-            if (n1 >= 1 && n1 < a.N) {
-                ConvArgs lo = a, hi = a;
-                lo.N = n1; lo.M = n1 * a.HoWo;
-                hi.N = a.N - n1; hi.M = hi.N * a.HoWo;
-                const size_t xoff = (size_t)n1 * a.H * a.W * a.x_ld * sizeof(T), yoff = (size_t)n1 * a.HoWo * a.y_ld * sizeof(T);
-                hi.x = a.x + xoff;
-                hi.y = a.y + yoff;
-                if (a.res) hi.res = a.res + (size_t)n1 * a.HoWo * a.res_ld * sizeof(T);
-                lo.x_bytes = (unsigned)xoff; hi.x_bytes = a.x_bytes - lo.x_bytes;
-                lo.y_bytes = (unsigned)yoff; hi.y_bytes = a.y_bytes - lo.y_bytes;
-                const int rc = dispatch<T>(lo, st, allow_stream, false);
-                if (rc != TLXMI_OK) return rc;
-                return dispatch<T>(hi, st, false, false);
-            }
-        }
-    }
-    if (best == 7 && tail_split) {
-        // rows of the full rounds (whole M tiles) -> this candidate; the rest -> best small-tile candidate
-        const int nt = (a.Cout + 255) / 256;
-        const int m_split = (int)((full_rounds * cus) / nt) * 256;
-        if (m_split > 0 && m_split < a.M) {
-            ConvArgs lo = a, hi = a;
-            lo.N = 1; lo.H = lo.Ho = 1; lo.W = lo.Wo = m_split; lo.HoWo = lo.M = m_split;
-            hi.N = 1; hi.H = hi.Ho = 1; hi.W = hi.Wo = a.M - m_split; hi.HoWo = hi.M = a.M - m_split;
-            hi.x = a.x + (size_t)m_split * a.x_ld * sizeof(T);
-            hi.y = a.y + (size_t)m_split * a.y_ld * sizeof(T);
-            if (a.res) hi.res = a.res + (size_t)m_split * a.res_ld * sizeof(T);
-            lo.x_bytes = (unsigned)((size_t)m_split * a.x_ld * sizeof(T));
-            hi.x_bytes = a.x_bytes - lo.x_bytes;
-            lo.y_bytes = (unsigned)((size_t)m_split * a.y_ld * sizeof(T));
-            hi.y_bytes = a.y_bytes - lo.y_bytes;
-            lo.y_nstride = hi.y_nstride = 0; lo.res_nstride = hi.res_nstride = 0;
-            const int rc = dispatch<T>(lo, st, true);     // t256 % cus == 0 there: no further split
-            if (rc != TLXMI_OK) return rc;
-            // a short tail (one round of 128x128 tiles) runs best on the small-tile kernels (measured: ViT fc1,
-            // Swin stage-3 fc1); a longer one on the 128 x 256 antiphase kernel (ViT proj / fc2: -3 %)
-            if (tail_mode == 1 || 4 * (t256 % cus) <= cus) return dispatch<T>(hi, st, false);
-            // the rows left over: the same antiphase kernel on 128 x 256 tiles — twice the tiles, half the time each,
-            // still one round (2 * left <= CUs)
-            Gemm256Args g;
-            g.debug = 0;
-            g.conv = 0;
-            g.x = hi.x; g.w = hi.w; g.y = hi.y; g.scale = hi.scale; g.shift = hi.shift; g.res = hi.res;
-            g.M = hi.M; g.Cout = hi.Cout; g.x_ld = hi.x_ld; g.y_ld = hi.y_ld; g.res_ld = hi.res_ld;
-            g.kchunks = hi.kchunks; g.ksteps = hi.Kp_bytes / 128; g.Kp_bytes = hi.Kp_bytes;
-            g.act = hi.act; g.act_param = hi.act_param; g.flags = hi.flags; g.mtiles = g.ntiles = 0; g.gn = 1;
-            g.x_bytes = hi.x_bytes; g.w_bytes = hi.w_bytes; g.y_bytes = hi.y_bytes;
-            g.res_bytes = hi.res ? (unsigned)((long long)hi.M * hi.res_ld * (long long)sizeof(T)) : 0u;
-            trace_launched("pp9", hi.M, hi.Cout);
-            return launch_gemm_pp128(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g, st);
-        }
-    }
-    if (best >= 5) {
-        Gemm256Args g;
-        g.debug = 0;
-        g.conv = 0;
-        if (as_conv) {      // candidates 7 / 9 / 10 as a convolution
-            g.conv = 1;
-            g.cH = a.H; g.cW = a.W; g.cWo = a.Wo; g.cHoWo = a.HoWo; g.csh = a.sh; g.csw = a.sw; g.cph = a.ph; g.cpw = a.pw;
-            g.cdh = a.dh; g.cdw = a.dw;
-            g.ctaps = a.R * a.S;
-            g.ctshift = 0;
-            while ((1 << g.ctshift) < tpk) ++g.ctshift;
-        }
-        g.x = a.x; g.w = a.w; g.y = a.y; g.scale = a.scale; g.shift = a.shift; g.res = a.res;
-        g.M = a.M; g.Cout = a.Cout; g.x_ld = a.x_ld; g.y_ld = a.y_ld; g.res_ld = a.res_ld;
-        g.kchunks = a.kchunks; g.ksteps = a.Kp_bytes / 64; g.Kp_bytes = a.Kp_bytes;
-        g.act = a.act; g.act_param = a.act_param; g.flags = a.flags; g.mtiles = g.ntiles = 0;
-        g.x_bytes = a.x_bytes; g.w_bytes = a.w_bytes; g.y_bytes = a.y_bytes;
-        g.res_bytes = a.res ? (unsigned)((long long)a.M * a.res_ld * (long long)sizeof(T)) : 0u;
-        if (best == 11) {      // gemm_w4.hip is part of the tuning flavour only (make tune): the product never dispatches it (eff = 0)
-#ifdef TLXMI_TUNING
-            g.ksteps = a.Kp_bytes / 128;
-            if (gemm_w4_ok(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g)) {
-                trace_launched("w4_11", a.M, a.Cout);
-                return launch_gemm_w4(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g, st, cus);
-            }
-#endif
-            best = 8;
-        }
-        if (best == 8) {
-            g.ksteps = a.Kp_bytes / 128;
-            if (gemm_stream_ok(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g)) {
-                trace_launched("stream8", a.M, a.Cout);
-                return launch_gemm_stream(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, g, st, cus);
-            }
-            best = 7;
-        }
-        if (best == 7 || best == 9 || best == 10) {
-            g.ksteps = a.Kp_bytes / 128;
-            if (a.pp_slices > 1) {
-                g.kslices = a.pp_slices;
-                g.kt_slice = (g.ksteps + a.pp_slices - 1) / a.pp_slices;
-                g.slice_bytes = (long long)a.M * a.y_ld * 4;
-                g.res = nullptr; g.scale = g.shift = nullptr;
-            }
-            const int dt = sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32;
-            trace_launched(best == 7 ? "pp7" : best == 9 ? "pp9" : "pp10", a.M, a.Cout);
-            return best == 7 ? launch_gemm_pp(dt, g, st) : best == 9 ? launch_gemm_pp128(dt, g, st) : launch_gemm_pp_n128(dt, g, st);
-        }
-        trace_launched(best == 5 ? "gemm256_5" : "gemm256_6", a.M, a.Cout);
-        return launch_gemm256(sizeof(T) == 2 ? TLXMI_F16 : TLXMI_F32, best - 5, g, st);
-    }
-    static const char* const igemm_names[5] = {"igemm0", "igemm1", "igemm2", "igemm3", "igemm4"};
-    trace_launched(igemm_names[best >= 0 && best <= 4 && best != 3 ? best : 3], a.M, a.Cout);
-    switch (best) {
-        case 0: return launch<T, 128, 128, 2, 2>(a, st);
-        case 1: return launch<T, 64, 128, 2, 2>(a, st);
-        case 2: return launch<T, 128, 64, 2, 2>(a, st);
-        case 4: return launch<T, 256, 128, 4, 3>(a, st);
-        default: return launch<T, 64, 64, 2, 2>(a, st);
-    }
+    if (kCands[best].family == F_PP && s.as_conv && allow_split && t.mode != 0 && a.pp_slices <= 1 && split_images<T>(a, kCands[best], cus, st, allow_stream, &rc)) return rc;
+    if (best == PP7 && t.rows && split_rows<T>(a, t, cus, st, &rc)) return rc;
+    return launch_candidate<T>(best, a, s, cus, st);
 }
 
 }  // namespace tlxmi
@@ -1220,18 +1236,8 @@ static int fill_ln_gemm(Gemm256Args& g, const char* who, int dtype, int64_t rows
     const int kchunks = K * 2 / 16, ktiles = (kchunks + 7) / 8;
     if (!(Cout % 32 == 0 && Cout >= 256 && ktiles >= 2 && xb < (1ll << 31) && yb < (1ll << 31) && rows < (1ll << 27)))
         return fail(TLXMI_ERR_UNSUPPORTED, "%s: shape %lld x %d -> %d is outside the persistent 256 x 256 GEMM kernel", who, (long long)rows, K, Cout);
-    g.debug = 0;
-    g.conv = 0;
-    g.x = (const char*)x; g.w = (const char*)w_packed; g.y = (char*)y; g.scale = nullptr; g.shift = nullptr; g.res = nullptr;
-    g.M = (int)rows; g.Cout = Cout; g.x_ld = x_ld; g.y_ld = y_ld; g.res_ld = 0;
-    g.kchunks = kchunks; g.Kp_bytes = ktiles * 128; g.ksteps = ktiles;
-    g.act = TLXMI_ACT_NONE; g.act_param = 0.f; g.flags = 0; g.mtiles = g.ntiles = 0; g.gn = 1;
-    g.x_bytes = (unsigned)xb; g.y_bytes = (unsigned)yb; g.res_bytes = 0;
-    g.w_bytes = (unsigned)(((size_t)(Cout + 127) / 128 * 128) * (size_t)g.Kp_bytes);
+    g = gemm_args(x, w_packed, y, (int)rows, Cout, x_ld, y_ld, kchunks, ktiles, (unsigned)xb, (unsigned)yb);
     return TLXMI_OK;
-}
-static int ln_plan_cus(unsigned flags) {
-    return (flags & TLXMI_PLAN_SHARED_HALF) ? (num_cus() / 2 > 0 ? num_cus() / 2 : 1) : num_cus();
 }
 // Whether a folded GEMM the persistent kernel could take goes to the one-tile kernel's half-height tiles instead: fewer 256 x 256 tiles
 // than half the CUs (Swin-B stage 3 fc2: 49 x 2; stage 4 proj / fc2: 13 x 4; ViT-B/16 at batch 64: 25 x 3).  Measured on the graph replay:
@@ -1284,7 +1290,7 @@ extern "C" int tlxmi_linear_stats(int dtype, int64_t rows, int K, int Cout, int 
     g.flags = flags & (TLXMI_PLAN_SHARED_HALF | TLXMI_PLAN_SHARED_FULL);
     // the persistent kernel where it applies; a residual with a short K (its residual steps need 11 K tiles: Swin-B stage 3 proj,
     // K = 512) and launches of few tiles (ln_small_on_pp) on the one-tile-per-workgroup form of the same K loop
-    if (int rc = (gemm_stream_ok(dtype, g) && !ln_small_on_pp(g)) ? launch_gemm_stream(dtype, g, as_stream(stream), ln_plan_cus(flags)) : launch_ln_pp(dtype, g, as_stream(stream))) return rc;
+    if (int rc = (gemm_stream_ok(dtype, g) && !ln_small_on_pp(g)) ? launch_gemm_stream(dtype, g, as_stream(stream), plan_cus(flags)) : launch_ln_pp(dtype, g, as_stream(stream))) return rc;
     return check_launch("linear_stats");
 }
 
@@ -1308,7 +1314,7 @@ extern "C" int tlxmi_linear_ln(int dtype, int64_t rows, int K, int Cout, int x_l
     g.flags = flags & (TLXMI_PLAN_SHARED_HALF | TLXMI_PLAN_SHARED_FULL);
     // TLXMI_LN_GELU_PP (tuning flavour): 1 = GELU layers on the one-tile-per-workgroup kernel (its epilogue is not squeezed between MFMAs)
     const bool on_pp = !gemm_stream_ok(dtype, g) || ln_small_on_pp(g) || (act == TLXMI_ACT_GELU && tune_int("TLXMI_LN_GELU_PP", 0));
-    if (int rc = on_pp ? launch_ln_pp(dtype, g, as_stream(stream)) : launch_gemm_stream(dtype, g, as_stream(stream), ln_plan_cus(flags))) return rc;
+    if (int rc = on_pp ? launch_ln_pp(dtype, g, as_stream(stream)) : launch_gemm_stream(dtype, g, as_stream(stream), plan_cus(flags))) return rc;
     return check_launch("linear_ln");
 }
 
@@ -1392,32 +1398,25 @@ extern "C" int tlxmi_conv1x1_proj(const tlxmi_proj_desc* d, const void* x, const
     const char* why;
     if (const int rc = proj_check(d, x, x2, w_packed, y, &why)) return fail(rc, "conv1x1_proj: %s", why);
     const long long rows = (long long)d->N * d->Ho * d->Wo;
-    Gemm256Args g;
-    g.debug = 0; g.conv = 0;
-    g.x = (const char*)x; g.w = (const char*)w_packed; g.y = (char*)y; g.scale = nullptr; g.shift = shift; g.res = nullptr;
-    g.M = (int)rows; g.Cout = d->Cout; g.x_ld = d->x_ld; g.y_ld = d->y_ld; g.res_ld = 0;
-    g.k1_tiles = d->K1 / 64; g.k2_tiles = d->K2 / 64;
-    g.ksteps = g.k1_tiles + g.k2_tiles; g.kchunks = g.ksteps * 8; g.Kp_bytes = g.ksteps * 128;
+    const int k1_tiles = d->K1 / 64, k2_tiles = d->K2 / 64;
+    Gemm256Args g = gemm_args(x, w_packed, y, (int)rows, d->Cout, d->x_ld, d->y_ld, (k1_tiles + k2_tiles) * 8, k1_tiles + k2_tiles,
+                              (unsigned)(rows * d->x_ld * 2), (unsigned)(((rows - 1) * d->y_ld + d->Cout) * 2));
+    g.shift = shift; g.k1_tiles = k1_tiles; g.k2_tiles = k2_tiles;
     g.act = d->act; g.act_param = d->act_param; g.flags = d->flags & (TLXMI_PLAN_SHARED_HALF | TLXMI_PLAN_SHARED_FULL);
-    g.mtiles = g.ntiles = 0; g.gn = 1;
-    g.x_bytes = (unsigned)(rows * d->x_ld * 2);
-    g.y_bytes = (unsigned)(((rows - 1) * d->y_ld + d->Cout) * 2);
-    g.res_bytes = 0;
-    g.w_bytes = (unsigned)(((size_t)(d->Cout + 127) / 128 * 128) * (size_t)g.Kp_bytes);
     g.x2 = (const char*)x2; g.x2_ld = d->x2_ld;
     g.x2_bytes = (unsigned)((long long)d->N * d->H2 * d->W2 * d->x2_ld * 2);
     g.dH2 = d->H2; g.dW2 = d->W2; g.dWo = d->Wo; g.dHoWo = d->Ho * d->Wo; g.ds = d->stride;
-    // Tile height by the dispatcher's price (dispatch<T>, candidates 7 and 9): rounds of one workgroup per CU on the CUs this launch is
-    // planned for, times the fill of the last row tile, times the shape efficiency (kEffPP256 / kEffPP128, the dispatcher's own)
-    const int cus = (d->flags & TLXMI_PLAN_SHARED_HALF) ? (num_cus() / 2 > 0 ? num_cus() / 2 : 1) : num_cus();
+    // Tile height by the dispatcher's price (tile_price with the efficiencies of pp7 and pp9): rounds of one workgroup per CU on the CUs
+    // this launch is planned for, times the fill of the last row tile (the column fill is the same for both heights)
+    const int cus = plan_cus(d->flags);
     const long nt = (d->Cout + 255) / 256;
-    auto price = [&](int bm, float eff) {
-        const long mt = (long)((rows + bm - 1) / bm), blocks = mt * nt, rounds = (blocks + cus - 1) / cus;
-        return (float)blocks / (float)(rounds * cus) * ((float)rows / (float)(mt * bm)) * eff;
+    auto price = [&](const CandInfo& k) {
+        const long mt = (long)((rows + k.bm - 1) / k.bm);
+        return tile_price(mt * nt, cus, 0.f, tile_fill((float)rows, mt, k.bm, 1), k.eff);
     };
     // TLXMI_PROJ_TILE (tuning flavour): 1 = 256 x 256 tiles, 2 = 128 x 256 (the tests run either form at sizes the price would not pick it)
-    const long forced = tune_int("TLXMI_PROJ_TILE", 0);
-    const bool half_height = forced == 1 ? false : forced == 2 ? true : price(128, kEffPP128) > price(256, kEffPP256);
+    const long knob = tune_int("TLXMI_PROJ_TILE", 0);
+    const bool half_height = knob == 1 ? false : knob == 2 ? true : price(kCands[PP9]) > price(kCands[PP7]);
     trace_launched(half_height ? "pp_dual128" : "pp_dual256", g.M, g.Cout);
     if (int rc = launch_gemm_pp_dual(g, half_height, as_stream(stream))) return rc;
     return check_launch("conv1x1_proj");
