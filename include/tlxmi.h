@@ -713,6 +713,45 @@ int tlxmi_cswin_attention_plain(const tlxmi_cswin_attention_desc* d, const void*
                                 const float* b_lepe, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LeViT's attention (classification/levit.py:156-224 `Attention`, :243-323 `AttentionSubsample`): q and k are `kd` wide, v and a head's
+ * output `d` wide, the queries an Rq x Rq grid and the keys an Rk x Rk grid (token (y, x) of an R x R grid = row y*R + x), query (y, x)
+ * sitting at key-grid position (y*stride, x*stride); every head adds a learned bias indexed by the distance on the key grid:
+ *   out[b][i][h*d + :] = act( sum_j softmax_j( scale * q_i . k_j + bias[h][|y_i*stride - y_j|][|x_i*stride - x_j|] ) v_j )
+ * bias is fp32 [heads][Rk][Rk] ([h][dy][dx]); the KERNEL computes the index from the token coordinates, no [heads][Lq][Lk] table exists.
+ * Head h of a q / k / v row starts at column h * {q,k,v}_head_stride, of an out row at column h*d: a stage passes three pointers into the
+ * packed `qkv` rows [heads][kd | kd | d] (offsets 0, kd, 2kd; head stride 2kd + d; row stride heads*(2kd + d)), a subsample layer q from
+ * its own [B][Rq*Rq][heads*kd] matrix and k, v from the packed `kv` rows (head stride kd + d).  act (NONE or HARDSWISH, the activation
+ * in front of `proj`) is applied in fp32 before the one rounding.  One writer per output element, a fixed summation order, no atomics.
+ * Rows behind Rq*Rq / Rk*Rk and columns outside a head's q / k / v columns are never read; nothing outside the heads*d output columns is
+ * written.
+ *   tlxmi_levit_attention            fp16: K, V and the bias table of an (image, head) staged once per workgroup in LDS, waves walk
+ *                                    16-query tiles, both products on MFMA (kd 16 = one 16x16x16, kd 32 = one 16x16x32 per key tile), the
+ *                                    scores + bias + softmax one pass in registers (<= 256 keys), the probabilities rounded once to fp16,
+ *                                    the fp32 sum divides the second product.
+ *   tlxmi_levit_attention_supported  pure host code; 1 exactly for: fp16; kd 16 or 32; d 32, 64 or 128; 1 <= Rk <= 16; Rq >= 1,
+ *                                    stride >= 1, (Rq-1)*stride <= Rk-1; B, heads >= 1; act NONE or HARDSWISH; every stride a
+ *                                    non-negative multiple of 8 elements; each tensor's byte extent below 2^31; output rows that do not
+ *                                    overlap.  1 means the call is taken, given 16-byte aligned pointers; everything else returns
+ *                                    TLXMI_ERR_UNSUPPORTED.
+ *   tlxmi_levit_attention_plain      same arguments; fp16 or fp32, kd and d <= 128, any Rk, any non-negative strides, fp32 arithmetic,
+ *                                    no MFMA: the fp32 parity path and the arm of what the hot path does not take.  Not tuned.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_levit_attention_desc {
+    int32_t dtype;
+    int32_t B, heads, kd, d;     /* width of q and k; width of v and of a head's output */
+    int32_t Rq, Rk, stride;      /* queries: an Rq x Rq grid; keys: an Rk x Rk grid; query (y, x) sits at key-grid position (y*stride, x*stride) */
+    float   scale;
+    int32_t act;                 /* TLXMI_ACT_NONE or TLXMI_ACT_HARDSWISH, applied to the output */
+    int64_t q_batch_stride, q_row_stride, q_head_stride, k_batch_stride, k_row_stride, k_head_stride,
+            v_batch_stride, v_row_stride, v_head_stride, out_batch_stride, out_row_stride;   /* elements; a head's output at column h*d */
+} tlxmi_levit_attention_desc;
+int tlxmi_levit_attention_supported(const tlxmi_levit_attention_desc* d);
+int tlxmi_levit_attention(const tlxmi_levit_attention_desc* d, const void* q, const void* k, const void* v, const float* bias, void* out,
+                          void* stream);
+int tlxmi_levit_attention_plain(const tlxmi_levit_attention_desc* d, const void* q, const void* k, const void* v, const float* bias,
+                                void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Swin window plumbing folded into index math (swin_transformer.py:85-116, 317-333):
  *   partition: x[B][H][W][C] --roll(-shift)--> windows [B*nW][ws*ws][C]
  *   reverse:   windows --> x (+roll(+shift)), optionally y = res + reverse(windows)

@@ -71,6 +71,12 @@ class CswinAttnDesc(C.Structure):
             "out_batch_stride", "out_row_stride")]
 
 
+class LevitAttnDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "B", "heads", "kd", "d", "Rq", "Rk", "stride")] + [("scale", C.c_float), ("act", C.c_int32)] + [
+        (n, C.c_int64) for n in ("q_batch_stride", "q_row_stride", "q_head_stride", "k_batch_stride", "k_row_stride", "k_head_stride",
+                                 "v_batch_stride", "v_row_stride", "v_head_stride", "out_batch_stride", "out_row_stride")]
+
+
 class SeamDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in (
         "K1", "N1", "N2", "t2_ld", "skip_ld", "y_ld", "t1_ld", "act")]
@@ -136,6 +142,8 @@ PROTOTYPES = {
     "tlxmi_sr_attention": [C.POINTER(MhaDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_cswin_attention": [C.POINTER(CswinAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_cswin_attention_plain": [C.POINTER(CswinAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_levit_attention": [C.POINTER(LevitAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_levit_attention_plain": [C.POINTER(LevitAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_window_partition": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_window_reverse": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_patch_merge_gather": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -173,6 +181,7 @@ _SPECIAL = {
     "tlxmi_preact_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i], C.c_int),
     "tlxmi_sr_attention_supported": ([C.POINTER(MhaDesc)], C.c_int),
     "tlxmi_cswin_attention_supported": ([C.POINTER(CswinAttnDesc)], C.c_int),
+    "tlxmi_levit_attention_supported": ([C.POINTER(LevitAttnDesc)], C.c_int),
     "tlxmi_lka_dw_supported": ([C.POINTER(LkaDwDesc)], C.c_int),
     "tlxmi_lka_gate_supported": ([C.POINTER(LkaGateDesc)], C.c_int),
 }

@@ -65,6 +65,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # tlxmi_cswin_attention: K / V of a (stripe, head) staged once in LDS, both products on MFMA, the scores in
                                   # registers, LePE from the V tile in the epilogue; off = tlxmi_cswin_attention_plain (the A/B and the tests'
                                   # other arm)
+            "levit_attn": True,   # LeViT's attention (fp16, keys 16 / 32 wide, values 32 / 64 / 128 wide, key grids up to 16 x 16, a bias per head
+                                  # indexed by the distance on the key grid) on tlxmi_levit_attention: K / V / the bias table of an (image, head)
+                                  # staged once in LDS, both products on MFMA, scores + bias + softmax in registers, Hardswish in the epilogue;
+                                  # off = tlxmi_levit_attention_plain (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1751,6 +1755,95 @@ def cswin_attention(qkv, B, H, W, heads, splits, w_lepe, b_lepe, scale, fused=No
         keys = sum(hs * ws for hs, ws in stripes) / nb                  # keys a query meets, averaged over the branches
         _probe.append((e0, e1, 4 * B * H * W * Cc * es + w_lepe.numel() * es, int(4 * B * H * W * keys * Cc) + 18 * B * H * W * Cc,
                        (B, H, W, heads, hd, tuple(stripes), "cswin_attn" if fused else "cswin_plain")))
+    return out
+
+
+def levit_bias_grid(attention_biases, Rq, Rk, stride):
+    """LeViT's `attention_biases` parameter (heads, n_offsets) -> the fp32 [heads][Rk][Rk] grid tlxmi_levit_attention indexes by
+    (|dy|, |dx|) on the key grid.  Column n of the parameter is the n-th DISTINCT offset in the order the reference's dictionary loop
+    meets them (levit.py:172-181 for a stage, :270-283 for a subsample layer: queries row-major outside, keys row-major inside, offset
+    (|y_q*stride - y_k|, |x_q*stride - x_k|)); offsets that never occur stay zero."""
+    if attention_biases.dim() != 2:
+        raise RuntimeError(f"levit_bias_grid: a (heads, n_offsets) parameter is expected, got {tuple(attention_biases.shape)}")
+    Rq, Rk, stride = int(Rq), int(Rk), int(stride)
+    if Rq < 1 or Rk < 1 or stride < 1 or (Rq - 1) * stride > Rk - 1:
+        raise RuntimeError(f"levit_bias_grid: a {Rq} x {Rq} query grid at stride {stride} does not sit on a {Rk} x {Rk} key grid")
+    order = {}
+    for qy in range(Rq):
+        for qx in range(Rq):
+            for ky in range(Rk):
+                for kx in range(Rk):
+                    off = (abs(qy * stride - ky), abs(qx * stride - kx))
+                    if off not in order:
+                        order[off] = len(order)
+    if attention_biases.shape[1] != len(order):
+        raise RuntimeError(f"levit_bias_grid: {attention_biases.shape[1]} offsets in the parameter, the grids have {len(order)}")
+    dy = torch.tensor([o[0] for o in order], dtype=torch.long, device=attention_biases.device)
+    dx = torch.tensor([o[1] for o in order], dtype=torch.long, device=attention_biases.device)
+    grid = torch.zeros((attention_biases.shape[0], Rk, Rk), dtype=torch.float32, device=attention_biases.device)
+    grid[:, dy, dx] = attention_biases.detach().float()
+    return grid.contiguous()
+
+
+def _levit_desc(dtype, B, heads, kd, d, Rq, Rk, stride, scale, act, q, k, v, out, q_hs, k_hs, v_hs):
+    return _lib.LevitAttnDesc(dtype=dt_code(dtype), B=B, heads=heads, kd=kd, d=d, Rq=Rq, Rk=Rk, stride=stride, scale=float(scale), act=int(act),
+                              q_batch_stride=q.stride(0), q_row_stride=q.stride(1), q_head_stride=q_hs,
+                              k_batch_stride=k.stride(0), k_row_stride=k.stride(1), k_head_stride=k_hs,
+                              v_batch_stride=v.stride(0), v_row_stride=v.stride(1), v_head_stride=v_hs,
+                              out_batch_stride=out.stride(0), out_row_stride=out.stride(1))
+
+
+def levit_attention(kv, bias_grid, heads, kd, d, Rk, scale, q=None, Rq=None, stride=1, act=ACT_HARDSWISH, fused=None):
+    """LeViT's attention (levit.py:199-224, :301-323) -> (B, Rq*Rq, heads*d), `act` (ACT_NONE or ACT_HARDSWISH, the activation in front
+    of `proj`) applied.  Token (y, x) of an R x R grid is row y*R + x.
+      a stage (q=None):   kv is the packed `qkv` rows (B, Rk*Rk, heads*(2kd + d)), [heads][kd | kd | d] per row; Rq = Rk, stride 1;
+      a subsample layer:  q (B, Rq*Rq, heads*kd) and kv the packed `kv` rows (B, Rk*Rk, heads*(kd + d)), [heads][kd | d] per row; query
+                          (y, x) sits at key-grid position (y*stride, x*stride).
+    q, k, v are pointers into those rows, read in place.  bias_grid: fp32 [heads][Rk][Rk] (levit_bias_grid).
+    tlxmi_levit_attention (MFMA, the scores in registers) when the "levit_attn" option is on, the precision is fp16, the library takes the
+    shape (kd 16 / 32, d 32 / 64 / 128, Rk <= 16) and the pointers are 16-byte aligned; otherwise tlxmi_levit_attention_plain (fp32
+    arithmetic: the parity reference).  fused=True / False forces one form (tests, tools/); a forced unsupported call raises."""
+    need_gpu(kv, "kv")
+    heads, kd, d, Rk, stride = int(heads), int(kd), int(d), int(Rk), int(stride)
+    per = (kd + d) if q is not None else (2 * kd + d)
+    if kv.dim() != 3 or kv.shape[1] != Rk * Rk or kv.shape[2] != heads * per or kv.stride(-1) != 1:
+        raise RuntimeError(f"levit_attention: packed rows (B, {Rk * Rk}, {heads * per}) with a dense feature axis are expected, got "
+                           f"{tuple(kv.shape)}")
+    B = kv.shape[0]
+    if q is None:
+        Rq, stride = Rk, 1
+        qv, kview, vview, q_hs = kv, kv[..., kd:], kv[..., 2 * kd:], per
+    else:
+        need_gpu(q, "q")
+        Rq = int(Rq)
+        if q.dim() != 3 or tuple(q.shape) != (B, Rq * Rq, heads * kd) or q.stride(-1) != 1 or q.dtype != kv.dtype:
+            raise RuntimeError(f"levit_attention: q ({B}, {Rq * Rq}, {heads * kd}) of kv's dtype with a dense feature axis is expected, got "
+                               f"{tuple(q.shape)} {q.dtype}")
+        qv, kview, vview, q_hs = q, kv, kv[..., kd:], kd
+    if (Rq - 1) * stride > Rk - 1 or Rq < 1 or stride < 1:
+        raise RuntimeError(f"levit_attention: a {Rq} x {Rq} query grid at stride {stride} does not sit on a {Rk} x {Rk} key grid")
+    if tuple(bias_grid.shape) != (heads, Rk, Rk) or bias_grid.dtype != torch.float32 or not bias_grid.is_contiguous() or not bias_grid.is_cuda:
+        raise RuntimeError(f"levit_attention: a dense fp32 [{heads}][{Rk}][{Rk}] bias grid on the device is expected, got "
+                           f"{tuple(bias_grid.shape)} {bias_grid.dtype}")
+    if act not in (ACT_NONE, ACT_HARDSWISH):
+        raise RuntimeError("levit_attention: act is ACT_NONE or ACT_HARDSWISH")
+    out = torch.empty((B, Rq * Rq, heads * d), dtype=kv.dtype, device=kv.device)
+    es = kv.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(out.numel() * es, kv.numel() * es)
+    dsc = _levit_desc(kv.dtype, B, heads, kd, d, Rq, Rk, stride, scale, act, qv, kview, vview, out, q_hs, per, per)
+    if fused is None:
+        fused = bool(_options["levit_attn"] and kv.dtype == torch.float16 and _lib.load().tlxmi_levit_attention_supported(C.byref(dsc))
+                     and all(t.data_ptr() % 16 == 0 for t in (qv, kview, vview, out, bias_grid)))
+    if _probe is not None:
+        e0, e1 = _probe_pair()
+    _lib.call("tlxmi_levit_attention" if fused else "tlxmi_levit_attention_plain", C.byref(dsc), _p(qv), _p(kview), _p(vview), _p(bias_grid),
+              _p(out), _stream())
+    if _probe is not None:
+        e1.record()
+        Lq, Lk = Rq * Rq, Rk * Rk
+        _probe.append((e0, e1, B * heads * (Lq * kd + Lk * (kd + d) + Lq * d) * es + heads * Lk * 4, 2 * B * heads * Lq * Lk * (kd + d),
+                       (B, Rq, Rk, stride, heads, kd, d, "levit_attn" if fused else "levit_plain")))
     return out
 
 

@@ -26,3 +26,6 @@ from .van import VAN, VAN_B0, van  # noqa: F401
 # (the CSWin file's Mlp stays in its module)
 from .cswin_transformer import (CSwinTransformer, CSwintransformer_thiny, PatchEmbedding, LePEAttention, CSwinBlock, MergeBlock,  # noqa: F401
                                 CSwinStage)
+# (the LeViT file's Attention / Residual / Subsample stay in their module: PVTv2's and VAN's own those names in theirs)
+from .levit import (LeViT, levit_128s, levit_128, levit_192, levit_256, levit_384, AttentionSubsample, Conv2d_BN, Linear_BN,  # noqa: F401
+                    BN_Linear, b16)

@@ -52,6 +52,7 @@ def fill(shapes, seed):
       *_weight (attention projections, out x in)   N(0, sqrt(1/fan_in));   *_bias   N(0, 0.02)
       *.weight (1-D) / *.bias    the channels-first LayerNorm of ConvNeXt: as gamma / beta
       layer_scale_*              U(0.05, 0.15)                                   (VAN: van.py:139-143)
+      attention_biases           N(0, 0.5)    LeViT's per-head bias by offset (levit.py:182): large enough that a wrong index moves logits
     """
     rng = np.random.default_rng(seed)
     out = {}
@@ -85,6 +86,8 @@ def fill(shapes, seed):
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(0.05)
         elif leaf.startswith("layer_scale_"):                   # VAN's [dim, 1, 1] layer scales (van.py:139-143): large enough to matter, small enough that 13 gated blocks stay far inside fp16
             a = rng.uniform(0.05, 0.15, shape).astype(np.float32)
+        elif leaf == "attention_biases":                        # LeViT (levit.py:182-183, :284-285)
+            a = rng.standard_normal(shape, dtype=np.float32) * np.float32(0.5)
         else:
             raise KeyError(f"seeded.fill: no rule for parameter {name!r}")
         out[name] = np.ascontiguousarray(a, dtype=np.float32)

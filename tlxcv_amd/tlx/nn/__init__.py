@@ -24,7 +24,7 @@ from . import initializers  # noqa: F401  (re-exported as nn.initializers)
 from .initializers import Constant, TruncatedNormal, xavier_uniform, he_normal, str_to_init  # noqa: F401
 
 __all__ = [
-    "Module", "Sequential", "ModuleList", "Parameter", "GroupConv2d", "Conv2d", "BatchNorm2d", "BatchNorm",
+    "Module", "Sequential", "ModuleList", "Parameter", "GroupConv2d", "Conv2d", "BatchNorm2d", "BatchNorm", "BatchNorm1d",
     "LayerNorm", "Linear", "MaxPool2d", "AdaptiveAvgPool2d", "AdaptiveAvgPool1d", "Dropout", "ReLU", "ReLU6",
     "LeakyReLU", "Hardswish", "HardSigmoid", "Sigmoid", "Softmax", "GELU", "Flatten", "UpSampling2d", "Identity",
     "MultiheadAttention",
@@ -304,6 +304,14 @@ class Sequential(Module):
 
     def append(self, layer):
         self.add_module(str(len(self._modules)), layer)
+
+    def add_sublayer(self, name, sublayer):      # the Paddle spelling the converted files keep (levit.py:50,60)
+        self.add_module(str(name), sublayer)
+        return sublayer
+
+    @property
+    def _sub_layers(self):                       # levit.py:63: `l, bn = self._sub_layers.values()`
+        return self._modules
 
     def forward(self, x):
         for l in self._modules.values():
@@ -618,6 +626,22 @@ class BatchNorm2d(Module):
 
 
 BatchNorm = BatchNorm2d
+
+
+class BatchNorm1d(BatchNorm2d):
+    """nn.BatchNorm1d(num_features=, data_format='channels_first') over the features of (rows, C) — levit.py:75,100.  The models fold it
+    into the Linear beside it; alone it is one tlxmi_affine_act launch over the last axis."""
+
+    def forward(self, x):
+        self._require_eval()
+        E.need_gpu(x, "input")
+        if x.dim() != 2 or x.shape[1] != self.num_features:
+            raise NotImplementedError(f"BatchNorm1d: (rows, {self.num_features}) is expected, got {tuple(x.shape)}")
+        if x.dtype != E.precision():
+            x = x.to(E.precision())
+        scale, shift = self._cached("fold1d", self.folded)
+        y = E.affine_act(x, scale, shift)
+        return self.act(y) if self.act is not None else y
 
 
 class LayerNorm(Module):
