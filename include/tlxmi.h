@@ -752,6 +752,36 @@ int tlxmi_levit_attention_plain(const tlxmi_levit_attention_desc* d, const void*
                                 void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The inner half of a TNT block (classification/tnt.py:142-149 `Block.forward`) in one launch.  x and y are [patches][pixels][dim] (row r of
+ * patch p = row p*pixels + r, rows {x,y}_row_stride elements apart; y may alias x), y_norm is [patches][pixels*dim] (rows yn_row_stride
+ * apart; a null y_norm skips that store):
+ *   y = x + proj(attn(LN1(x)));   y = y + fc2(gelu(fc1(LN2(y))));   y_norm[p][r*dim + c] = LN3(y)[p][r][c]
+ * attn = softmax(scale q k^T) v over `heads` heads of dim / heads channels; qk and v carry no bias; GELU is the erf form.  LN3 reads the
+ * fp32 y, not its rounded store.  params: fp32, tlxmi_tnt_inner_param_count(dim, hidden) values, weights [in][out]:
+ *   g1 b1 | Wqk [dim][2 dim] ([2][heads][hd] columns) | Wv [dim][dim] | Wproj [dim][dim] bproj | g2 b2 | Wfc1 [dim][hidden] bfc1 |
+ *   Wfc2 [hidden][dim] bfc2 | g3 b3
+ * Bytes between the rows are neither read nor written.  One writer per output element, fixed summation orders, no atomics.
+ *   tlxmi_tnt_inner            fp16: one wave per patch, workgroups grid-strided over the patches, the parameters staged once per workgroup
+ *                              in LDS as fp16 MFMA fragments; all five products on v_mfma_f32_16x16x16_f16 (K zero-padded), LayerNorm,
+ *                              scores, softmax, GELU and both residuals in fp32 registers.
+ *   tlxmi_tnt_inner_supported  pure host code; 1 exactly for: fp16, pixels 16, dim 24, heads 4, hidden 96, patches >= 1, scale > 0,
+ *                              eps >= 0, row strides >= the row and multiples of 4 elements.  1 means the call is taken, given 16-byte
+ *                              aligned pointers; everything else returns TLXMI_ERR_UNSUPPORTED.
+ *   tlxmi_tnt_inner_plain      same arguments; fp16 or fp32 tensors, pixels <= 64, dim <= 64, heads dividing dim, hidden <= 4096, fp32
+ *                              arithmetic, no MFMA: the fp32 parity path and the arm of what the hot path does not take.  Not tuned.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_tnt_inner_desc {
+    int32_t dtype;
+    int32_t patches, pixels, dim, heads, hidden;
+    float   scale, eps1, eps2, eps3;             /* hd^-0.5; epsilon of norm_in, norm_mlp_in, norm1_proj */
+    int64_t x_row_stride, y_row_stride, yn_row_stride;   /* elements */
+} tlxmi_tnt_inner_desc;
+int tlxmi_tnt_inner_supported(const tlxmi_tnt_inner_desc* d);
+size_t tlxmi_tnt_inner_param_count(int dim, int hidden);
+int tlxmi_tnt_inner(const tlxmi_tnt_inner_desc* d, const void* x, const void* params, void* y, void* y_norm, void* stream);
+int tlxmi_tnt_inner_plain(const tlxmi_tnt_inner_desc* d, const void* x, const void* params, void* y, void* y_norm, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Swin window plumbing folded into index math (swin_transformer.py:85-116, 317-333):
  *   partition: x[B][H][W][C] --roll(-shift)--> windows [B*nW][ws*ws][C]
  *   reverse:   windows --> x (+roll(+shift)), optionally y = res + reverse(windows)

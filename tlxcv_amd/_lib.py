@@ -77,6 +77,11 @@ class LevitAttnDesc(C.Structure):
                                  "v_batch_stride", "v_row_stride", "v_head_stride", "out_batch_stride", "out_row_stride")]
 
 
+class TntInnerDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "patches", "pixels", "dim", "heads", "hidden")] + [
+        (n, C.c_float) for n in ("scale", "eps1", "eps2", "eps3")] + [(n, C.c_int64) for n in ("x_row_stride", "y_row_stride", "yn_row_stride")]
+
+
 class SeamDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in (
         "K1", "N1", "N2", "t2_ld", "skip_ld", "y_ld", "t1_ld", "act")]
@@ -144,6 +149,8 @@ PROTOTYPES = {
     "tlxmi_cswin_attention_plain": [C.POINTER(CswinAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_levit_attention": [C.POINTER(LevitAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_levit_attention_plain": [C.POINTER(LevitAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_tnt_inner": [C.POINTER(TntInnerDesc), _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_tnt_inner_plain": [C.POINTER(TntInnerDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_window_partition": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_window_reverse": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_patch_merge_gather": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -182,6 +189,8 @@ _SPECIAL = {
     "tlxmi_sr_attention_supported": ([C.POINTER(MhaDesc)], C.c_int),
     "tlxmi_cswin_attention_supported": ([C.POINTER(CswinAttnDesc)], C.c_int),
     "tlxmi_levit_attention_supported": ([C.POINTER(LevitAttnDesc)], C.c_int),
+    "tlxmi_tnt_inner_supported": ([C.POINTER(TntInnerDesc)], C.c_int),
+    "tlxmi_tnt_inner_param_count": ([_i, _i], C.c_size_t),
     "tlxmi_lka_dw_supported": ([C.POINTER(LkaDwDesc)], C.c_int),
     "tlxmi_lka_gate_supported": ([C.POINTER(LkaGateDesc)], C.c_int),
 }

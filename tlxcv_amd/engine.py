@@ -69,6 +69,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # indexed by the distance on the key grid) on tlxmi_levit_attention: K / V / the bias table of an (image, head)
                                   # staged once in LDS, both products on MFMA, scores + bias + softmax in registers, Hardswish in the epilogue;
                                   # off = tlxmi_levit_attention_plain (the A/B and the tests' other arm)
+            "tnt_inner": True,    # TNT's inner transformer block (fp16, 16 pixels x 24 channels a patch, 4 heads, hidden 96) on tlxmi_tnt_inner: three
+                                  # LayerNorms, attention at head width 6 and the MLP in ONE launch, a wave per patch, the parameters staged once
+                                  # per workgroup in LDS, every product on MFMA, the pixel map read once and written once; off =
+                                  # tlxmi_tnt_inner_plain (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1460,8 +1464,9 @@ def global_avgpool(x):
     return y
 
 
-def affine_act(x, scale=None, shift=None, res=None, act=ACT_NONE, act_param=0.0, res_after_act=False, out=None):
-    """y = act(x*scale[c] + shift[c] (+res)) over the last axis."""
+def affine_act(x, scale=None, shift=None, res=None, act=ACT_NONE, act_param=0.0, res_after_act=False, out=None, out_ld=None):
+    """y = act(x*scale[c] + shift[c] (+res)) over the last axis.  out_ld: the rows of `out` sit this many elements apart (a wider or
+    pre-offset buffer)."""
     need_gpu(x, "input")
     if not x.is_contiguous():
         x = x.contiguous()
@@ -1471,8 +1476,8 @@ def affine_act(x, scale=None, shift=None, res=None, act=ACT_NONE, act_param=0.0,
     if res is not None and not res.is_contiguous():
         res = res.contiguous()
     _lib.call("tlxmi_affine_act", _p(x), _p(scale), _p(shift), _p(res), _p(y), dt_code(x.dtype), rows, Cc, Cc,
-              Cc if res is not None else 0, Cc, act, float(act_param), EPI_RES_AFTER_ACT if res_after_act else 0,
-              _stream())
+              Cc if res is not None else 0, Cc if out_ld is None else int(out_ld), act, float(act_param),
+              EPI_RES_AFTER_ACT if res_after_act else 0, _stream())
     return y
 
 
@@ -1845,6 +1850,81 @@ def levit_attention(kv, bias_grid, heads, kd, d, Rk, scale, q=None, Rq=None, str
         _probe.append((e0, e1, B * heads * (Lq * kd + Lk * (kd + d) + Lq * d) * es + heads * Lk * 4, 2 * B * heads * Lq * Lk * (kd + d),
                        (B, Rq, Rk, stride, heads, kd, d, "levit_attn" if fused else "levit_plain")))
     return out
+
+
+TNT_INNER_NAMES = ("norm_in.gamma", "norm_in.beta", "attn_in.qk.weights", "attn_in.v.weights", "attn_in.proj.weights", "attn_in.proj.biases",
+                   "norm_mlp_in.gamma", "norm_mlp_in.beta", "mlp_in.fc1.weights", "mlp_in.fc1.biases", "mlp_in.fc2.weights", "mlp_in.fc2.biases",
+                   "norm1_proj.gamma", "norm1_proj.beta")
+
+
+def tnt_inner_params(block_params):
+    """The inner half of a TNT block's parameters (a mapping from the names in TNT_INNER_NAMES, relative to the block, to tensors; weights
+    (in, out) as nn.Linear keeps them) -> ONE fp32 device buffer in the order tlxmi_tnt_inner reads (include/tlxmi.h):
+    g1 b1 | Wqk | Wv | Wproj bproj | g2 b2 | Wfc1 bfc1 | Wfc2 bfc2 | g3 b3.  `qk` and `v` carry no bias (tnt.py:83-87)."""
+    missing = [n for n in TNT_INNER_NAMES if n not in block_params]
+    if missing:
+        raise RuntimeError(f"tnt_inner_params: missing {missing}")
+    t = {n: block_params[n].detach() for n in TNT_INNER_NAMES}
+    D = t["norm_in.gamma"].numel()
+    hid = t["mlp_in.fc1.biases"].numel()
+    want = {"attn_in.qk.weights": (D, 2 * D), "attn_in.v.weights": (D, D), "attn_in.proj.weights": (D, D), "attn_in.proj.biases": (D,),
+            "mlp_in.fc1.weights": (D, hid), "mlp_in.fc2.weights": (hid, D), "mlp_in.fc2.biases": (D,)}
+    want.update({n: (D,) for n in TNT_INNER_NAMES if n.endswith((".gamma", ".beta"))})
+    for n, shp in want.items():
+        if tuple(t[n].shape) != shp:
+            raise RuntimeError(f"tnt_inner_params: {n} is {tuple(t[n].shape)}, expected {shp}")
+    buf = torch.cat([t[n].float().reshape(-1) for n in TNT_INNER_NAMES]).contiguous()
+    if buf.numel() != _lib.load().tlxmi_tnt_inner_param_count(D, hid):
+        raise RuntimeError("tnt_inner_params: the packed size disagrees with the library's")
+    return buf
+
+
+def _tnt_desc(dtype, patches, pixels, dim, heads, hidden, eps, x_ld, y_ld, yn_ld):
+    return _lib.TntInnerDesc(dtype=dt_code(dtype), patches=patches, pixels=pixels, dim=dim, heads=heads, hidden=hidden,
+                             scale=float((dim // heads) ** -0.5), eps1=float(eps[0]), eps2=float(eps[1]), eps3=float(eps[2]),
+                             x_row_stride=x_ld, y_row_stride=y_ld, yn_row_stride=yn_ld)
+
+
+def tnt_inner(x, packed, heads, eps_in=1e-5, eps_mlp=1e-5, eps_proj=1e-5, y_norm=True, fused=None, out=None):
+    """The inner half of a TNT block (tnt.py:142-149) on x (patches, pixels, dim) -> (y, y_norm): y = x + proj(attn(LN(x))), then
+    y + fc2(gelu(fc1(LN(y)))); y_norm (patches, pixels*dim) = the third LayerNorm of y, flattened pixel-major (None when y_norm is False).
+    packed: tnt_inner_params(...).  out: the tensor y is written to (x itself updates the map in place).
+    tlxmi_tnt_inner (one launch, every product on MFMA) when the "tnt_inner" option is on, the precision is fp16 and the library takes the
+    shape (16 pixels, dim 24, 4 heads, hidden 96); otherwise tlxmi_tnt_inner_plain (fp32 arithmetic: the parity reference).
+    fused=True / False forces one form (tests, tools/); a forced unsupported call raises."""
+    need_gpu(x, "x")
+    heads = int(heads)
+    if x.dim() != 3 or x.stride(-1) != 1 or x.stride(0) != x.shape[1] * x.stride(1):
+        raise RuntimeError(f"tnt_inner: (patches, pixels, dim) rows with a dense channel axis and evenly spaced rows are expected, got "
+                           f"{tuple(x.shape)} strides {tuple(x.stride())}")
+    patches, pixels, D = x.shape
+    if heads < 1 or D % heads:
+        raise RuntimeError(f"tnt_inner: {heads} heads do not divide dim {D}")
+    rest = packed.numel() - 4 * D * D - 8 * D
+    if packed.dtype != torch.float32 or not packed.is_cuda or not packed.is_contiguous() or rest <= 0 or rest % (2 * D + 1):
+        raise RuntimeError(f"tnt_inner: a dense fp32 device buffer from tnt_inner_params for dim {D} is expected, got {tuple(packed.shape)} {packed.dtype}")
+    hidden = rest // (2 * D + 1)
+    y = out if out is not None else torch.empty((patches, pixels, D), dtype=x.dtype, device=x.device)
+    if (tuple(y.shape) != tuple(x.shape) or y.dtype != x.dtype or y.stride(-1) != 1 or y.stride(0) != pixels * y.stride(1)):
+        raise RuntimeError("tnt_inner: out must have x's shape and dtype, a dense channel axis and evenly spaced rows")
+    yn = torch.empty((patches, pixels * D), dtype=x.dtype, device=x.device) if y_norm else None
+    es = x.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * es)
+    dsc = _tnt_desc(x.dtype, patches, pixels, D, heads, hidden, (eps_in, eps_mlp, eps_proj), x.stride(1), y.stride(1), pixels * D)
+    if fused is None:
+        fused = bool(_options["tnt_inner"] and x.dtype == torch.float16 and _lib.load().tlxmi_tnt_inner_supported(C.byref(dsc))
+                     and all(t_.data_ptr() % 16 == 0 for t_ in (x, y, packed) + ((yn,) if yn is not None else ())))
+    if _probe is not None:
+        e0, e1 = _probe_pair()
+    _lib.call("tlxmi_tnt_inner" if fused else "tlxmi_tnt_inner_plain", C.byref(dsc), _p(x), _p(packed), _p(y), _p(yn), _stream())
+    if _probe is not None:
+        e1.record()
+        hd = D // heads
+        flops = 2 * patches * pixels * (4 * D * D + 2 * D * hidden + 2 * heads * pixels * hd)
+        _probe.append((e0, e1, patches * pixels * D * es * (3 if y_norm else 2) + packed.numel() * 4, flops,
+                       (patches, pixels, D, heads, "tnt_inner" if fused else "tnt_plain")))
+    return y, yn
 
 
 def yolo_box(heads_nhwc, anchors, num_classes, img_size, conf_thresh=0.005, downsample_ratio=32, clip_bbox=True, scale_x_y=1.0):

@@ -29,3 +29,5 @@ from .cswin_transformer import (CSwinTransformer, CSwintransformer_thiny, PatchE
 # (the LeViT file's Attention / Residual / Subsample stay in their module: PVTv2's and VAN's own those names in theirs)
 from .levit import (LeViT, levit_128s, levit_128, levit_192, levit_256, levit_384, AttentionSubsample, Conv2d_BN, Linear_BN,  # noqa: F401
                     BN_Linear, b16)
+# (the TNT file's Block / Attention / Mlp stay in their module: ConvNeXt's Block owns that name here, and the other two follow PVTv2's rule)
+from .tnt import TNT, PixelEmbed, tnt_small  # noqa: F401

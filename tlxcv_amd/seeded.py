@@ -53,6 +53,9 @@ def fill(shapes, seed):
       *.weight (1-D) / *.bias    the channels-first LayerNorm of ConvNeXt: as gamma / beta
       layer_scale_*              U(0.05, 0.15)                                   (VAN: van.py:139-143)
       attention_biases           N(0, 0.5)    LeViT's per-head bias by offset (levit.py:182): large enough that a wrong index moves logits
+      patch_pos                  as pos_embed;  pixel_pos  N(0, 0.5): a wrong (c, ky, kx) order moves logits               (TNT: tnt.py:211-216)
+      *attn_in.* / *mlp_in.* weights   N(0, fan_in^-1/2), x 1.5 for attn_in.qk: TNT's inner transformer (24 channels) would otherwise add
+                                 O(0.01) a block and its softmax would be uniform, so a wrong inner kernel would move no logit
     """
     rng = np.random.default_rng(seed)
     out = {}
@@ -63,6 +66,9 @@ def fill(shapes, seed):
         if leaf == "filters":
             fan_in = int(np.prod(shape[1:]))
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(np.sqrt(2.0 / fan_in))
+        elif leaf == "weights" and ("attn_in." in owner + "." or "mlp_in." in owner + "."):      # TNT's inner transformer (tnt.py:125-129)
+            gain = 1.5 if (owner + ".").endswith("attn_in.qk.") else 1.0
+            a = rng.standard_normal(shape, dtype=np.float32) * np.float32(gain / np.sqrt(shape[0]))
         elif leaf == "weights":
             a = np.clip(rng.standard_normal(shape, dtype=np.float32), -2, 2) * np.float32(0.02)
         elif leaf == "biases":
@@ -74,7 +80,9 @@ def fill(shapes, seed):
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(0.05)
         elif leaf == "moving_var":
             a = rng.uniform(0.8, 1.2, shape).astype(np.float32)
-        elif leaf in ("pos_embed", "cls_token", "relative_position_bias_table", "absolute_pos_embed"):
+        elif leaf == "pixel_pos":                               # TNT (tnt.py:214-216): (1, in_dim, 4, 4)
+            a = rng.standard_normal(shape, dtype=np.float32) * np.float32(0.5)
+        elif leaf in ("pos_embed", "cls_token", "relative_position_bias_table", "absolute_pos_embed", "patch_pos"):
             a = np.clip(rng.standard_normal(shape, dtype=np.float32), -2, 2) * np.float32(0.02)
         elif leaf.endswith("_weight") and len(shape) == 2:      # attention projections stored (out, in): detr.py:975-995
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(np.sqrt(1.0 / shape[1]))
