@@ -782,6 +782,43 @@ int tlxmi_tnt_inner(const tlxmi_tnt_inner_desc* d, const void* x, const void* pa
 int tlxmi_tnt_inner_plain(const tlxmi_tnt_inner_desc* d, const void* x, const void* params, void* y, void* y_norm, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The attention half of a Twins GSA block (classification/gvt.py:105-127 `Attention.forward` under :148 `Block.forward`) in one launch:
+ * x and y are [B][Lq][C] token rows (strided like tlxmi_mha's q / out), k and v the two halves of the packed `kv` matrix
+ * [B][Lk][2][heads][hd] read in place (k = kv, v = kv + C, both with row stride 2 C: tlxmi_sr_attention's convention).  For row i of image b
+ *   n = LayerNorm(x_i; gamma, beta, eps)                       (biased variance, two passes, fp32)
+ *   q = n Wq + bq
+ *   a[h*hd + :] = sum_j softmax_j( scale * q[h] . k_j[h] ) v_j[h]        j < Lk, hd = C / heads
+ *   y_i = x_i + a Wp + bp
+ * fp16 storage, fp32 accumulation; all four products on v_mfma_f32_16x16x32_f16; the statistics and the one-pass softmax (no running
+ * maximum: Lk <= 64) in fp32 registers; n, q, the probabilities and a are rounded to fp16 where they become MFMA operands (where the
+ * layer-by-layer fp16 path stores them).  The residual stream is read once and written once.
+ * params: ONE 16-byte aligned block of tlxmi_gsa_block_param_count(C) = 8 C + 2 C^2 16-bit elements:
+ *   gamma[C] beta[C] bq[C] bp[C]     fp32 (two elements each)
+ *   Wq fragments, Wp fragments       fp16, C*C each, weights [in][out]: fragment f = ot * (C/32) + s (ot < C/16 output tiles of 16
+ *                                    channels, s < C/32 contraction steps), lane l < 64, element e < 8 at f*512 + l*8 + e holds
+ *                                    W[perm(s, l >> 4, e)][16 ot + (l & 15)],  perm(s, g, e) = 32 s + 4 g + e for e < 4 and
+ *                                    32 s + 16 + 4 g + (e - 4) for e >= 4 (the order the accumulator tiles of the previous product
+ *                                    leave their rows in)
+ * Key rows >= Lk and query rows >= Lq are never read; output rows >= Lq and the gaps of strided rows are never written; one writer per
+ * output element and a fixed summation order (two launches give the same bits).  y may alias x exactly (same pointer and strides): a
+ * tile's rows are read only by the wave that writes them, and before it writes.
+ * tlxmi_gsa_block_supported() is pure host code and answers 1 exactly for: fp16; C 64, 96 or 128; heads dividing C with hd 32 or 64;
+ * 1 <= Lk <= 64; B, Lq >= 1; every stride a non-negative multiple of 8 elements; each tensor's byte extent ((B-1)*batch stride +
+ * (L-1)*row stride + C) * 2 below 2^31; output rows that do not overlap (batch-major or sequence-major).  1 means the call is taken,
+ * given 16-byte aligned pointers; everything else returns TLXMI_ERR_UNSUPPORTED (run LayerNorm, Linear, tlxmi_sr_attention, Linear).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_gsa_block_desc {
+    int32_t dtype;
+    int32_t B, Lq, Lk, C, heads;
+    float   scale, eps;                          /* hd^-0.5 (or qk_scale); epsilon of norm1 */
+    int64_t x_batch_stride, x_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride,
+            y_batch_stride, y_row_stride;        /* in elements */
+} tlxmi_gsa_block_desc;
+int tlxmi_gsa_block_supported(const tlxmi_gsa_block_desc* d);
+size_t tlxmi_gsa_block_param_count(int C);
+int tlxmi_gsa_block(const tlxmi_gsa_block_desc* d, const void* x, const void* k, const void* v, const void* params, void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Swin window plumbing folded into index math (swin_transformer.py:85-116, 317-333):
  *   partition: x[B][H][W][C] --roll(-shift)--> windows [B*nW][ws*ws][C]
  *   reverse:   windows --> x (+roll(+shift)), optionally y = res + reverse(windows)

@@ -82,6 +82,12 @@ class TntInnerDesc(C.Structure):
         (n, C.c_float) for n in ("scale", "eps1", "eps2", "eps3")] + [(n, C.c_int64) for n in ("x_row_stride", "y_row_stride", "yn_row_stride")]
 
 
+class GsaBlockDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "B", "Lq", "Lk", "C", "heads")] + [(n, C.c_float) for n in ("scale", "eps")] + [
+        (n, C.c_int64) for n in ("x_batch_stride", "x_row_stride", "k_batch_stride", "k_row_stride", "v_batch_stride", "v_row_stride",
+                                 "y_batch_stride", "y_row_stride")]
+
+
 class SeamDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in (
         "K1", "N1", "N2", "t2_ld", "skip_ld", "y_ld", "t1_ld", "act")]
@@ -151,6 +157,7 @@ PROTOTYPES = {
     "tlxmi_levit_attention_plain": [C.POINTER(LevitAttnDesc), _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_tnt_inner": [C.POINTER(TntInnerDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_tnt_inner_plain": [C.POINTER(TntInnerDesc), _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_gsa_block": [C.POINTER(GsaBlockDesc), _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_window_partition": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_window_reverse": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "tlxmi_patch_merge_gather": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -191,6 +198,8 @@ _SPECIAL = {
     "tlxmi_levit_attention_supported": ([C.POINTER(LevitAttnDesc)], C.c_int),
     "tlxmi_tnt_inner_supported": ([C.POINTER(TntInnerDesc)], C.c_int),
     "tlxmi_tnt_inner_param_count": ([_i, _i], C.c_size_t),
+    "tlxmi_gsa_block_supported": ([C.POINTER(GsaBlockDesc)], C.c_int),
+    "tlxmi_gsa_block_param_count": ([_i], C.c_size_t),
     "tlxmi_lka_dw_supported": ([C.POINTER(LkaDwDesc)], C.c_int),
     "tlxmi_lka_gate_supported": ([C.POINTER(LkaGateDesc)], C.c_int),
 }

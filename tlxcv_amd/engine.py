@@ -73,6 +73,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # LayerNorms, attention at head width 6 and the MLP in ONE launch, a wave per patch, the parameters staged once
                                   # per workgroup in LDS, every product on MFMA, the pixel map read once and written once; off =
                                   # tlxmi_tnt_inner_plain (the A/B and the tests' other arm)
+            "gsa_block": True,    # Twins' GSA blocks of the wide stages (fp16, C 64 / 96 / 128, head dim 32 / 64, at most 64 reduced keys): norm1 ->
+                                  # q Linear -> attention -> proj + residual on tlxmi_gsa_block: ONE launch, K / V of an image and both weights
+                                  # staged in LDS, four chained MFMA products, the residual stream read once and written once; elsewhere and
+                                  # off = tlxmi_layernorm -> tlxmi_conv2d -> tlxmi_sr_attention -> tlxmi_conv2d (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1696,6 +1700,138 @@ def sr_attention(q, kv, heads, scale, fused=None):
         e1.record()
         _probe.append((e0, e1, (2 * B * Lq * Cc + 2 * B * Lk * Cc) * es, 4 * B * Lq * Lk * Cc,
                        (B, Lq, Lk, heads, Cc // heads, "sr_attn" if fused else "mha")))
+    return out
+
+
+def gsa_perm(Cc):
+    """The contraction order of tlxmi_gsa_block (include/tlxmi.h): a (C / 32, 4, 8) int64 table, perm[s, g, e] = the input channel in slot
+    8 g + e of 32-deep step s = 32 s + 4 g + e for e < 4, 32 s + 16 + 4 g + (e - 4) for e >= 4."""
+    s = torch.arange(Cc // 32).view(-1, 1, 1)
+    g = torch.arange(4).view(1, -1, 1)
+    e = torch.arange(8).view(1, 1, -1)
+    return 32 * s + 4 * g + (e % 4) + 16 * (e // 4)
+
+
+def gsa_fragments(w):
+    """A Linear weight (in = C, out = C) -> its C * C values in the fragment order of tlxmi_gsa_block: fragment f = ot * (C / 32) + s, lane
+    l, element e at f * 512 + l * 8 + e = w[perm(s, l >> 4, e)][16 ot + (l & 15)]."""
+    Cc = w.shape[0]
+    lane = torch.arange(64)
+    rows = gsa_perm(Cc)[:, lane >> 4, :]                                            # (S, 64, 8)
+    cols = 16 * torch.arange(Cc // 16).view(-1, 1) + (lane & 15).view(1, -1)        # (CT, 64)
+    return w[rows.to(w.device)[None], cols.to(w.device)[:, None, :, None]].reshape(-1)
+
+
+class GsaBlockParams:
+    """The parameters of the attention half of a GSA block (norm1, attn.q, attn.proj), built once per layer by gsa_block_params():
+      .block    ONE fp16-element buffer in tlxmi_gsa_block's order (include/tlxmi.h): gamma, beta, bq, bp as fp32 (two elements each), then
+                the fragments of Wq and of Wp in fp16; None where the library has no kernel for this width
+      .linears  the same layers as engine.layernorm / engine.linear take them (built on first use, per precision): the composition"""
+
+    def __init__(self, gamma, beta, wq, bq, wp, bp):
+        Cc = gamma.numel()
+        if tuple(wq.shape) != (Cc, Cc) or tuple(wp.shape) != (Cc, Cc) or beta.numel() != Cc or bp.numel() != Cc or (bq is not None and bq.numel() != Cc):
+            raise RuntimeError(f"gsa_block_params: norm over {Cc} channels, q {tuple(wq.shape)} and proj {tuple(wp.shape)} (in, out) of that width "
+                               "with biases to match are expected")
+        f32 = lambda t: t.detach().to(torch.float32).contiguous().view(-1)
+        self.C = Cc
+        self.gamma, self.beta, self.bp = f32(gamma), f32(beta), f32(bp)
+        self.bq = f32(bq) if bq is not None else torch.zeros_like(self.gamma)
+        self.wq, self.wp = wq.detach(), wp.detach()
+        self.block = None
+        if _lib.load().tlxmi_gsa_block_param_count(Cc):
+            vecs = torch.cat((self.gamma, self.beta, self.bq, self.bp)).view(torch.float16)
+            self.block = torch.cat((vecs, gsa_fragments(self.wq).to(torch.float16), gsa_fragments(self.wp).to(torch.float16))).contiguous()
+            if self.block.numel() != _lib.load().tlxmi_gsa_block_param_count(Cc):
+                raise RuntimeError("gsa_block_params: the packed size disagrees with the library's")
+        self._linears = {}
+
+    def linears(self, dtype):
+        hit = self._linears.get(dtype)
+        if hit is None:
+            hit = (PackedFilter(self.wq.t().contiguous(), dtype), PackedFilter(self.wp.t().contiguous(), dtype))
+            self._linears[dtype] = hit
+        return hit
+
+
+def gsa_block_params(norm, q, proj):
+    """norm (an nn.LayerNorm: .gamma, .beta), q and proj (nn.Linear: .weights (in, out), .biases or None) -> GsaBlockParams, on the
+    device the parameters live on."""
+    return GsaBlockParams(norm.gamma, norm.beta, q.weights, q.biases, proj.weights, proj.biases)
+
+
+def _gsa_desc(x, kv, y, heads, scale, eps):
+    Cc = x.shape[2]
+    return _lib.GsaBlockDesc(dtype=dt_code(x.dtype), B=x.shape[0], Lq=x.shape[1], Lk=kv.shape[1], C=Cc, heads=heads, scale=float(scale),
+                             eps=float(eps), x_batch_stride=x.stride(0), x_row_stride=x.stride(1), k_batch_stride=kv.stride(0),
+                             k_row_stride=kv.stride(1), v_batch_stride=kv.stride(0), v_row_stride=kv.stride(1),
+                             y_batch_stride=y.stride(0), y_row_stride=y.stride(1))
+
+
+def _gsa_takes(d, x, kv, y, packed):
+    Cc = x.shape[2]
+    return bool(_options["gsa_block"] and x.dtype == torch.float16 and kv.dtype == torch.float16 and packed.block is not None
+                and packed.block.device == x.device and _lib.load().tlxmi_gsa_block_supported(C.byref(d))
+                and all(p_ % 16 == 0 for p_ in (x.data_ptr(), kv.data_ptr(), kv.data_ptr() + 2 * Cc, y.data_ptr(), packed.block.data_ptr())))
+
+
+def gsa_block_takes(x, packed, kv, heads, out=None):
+    """True where gsa_block(x, packed, kv, heads, ..., out=out) runs as the one fused launch: the "gsa_block" option is on, the tensors are
+    fp16 and the library takes the shape.  A model asks before it builds the operands of the composition (the normalised map, q)."""
+    y = out if out is not None else x
+    return _gsa_takes(_gsa_desc(x, kv, y, int(heads), 1.0, 0.0), x, kv, y, packed)
+
+
+def gsa_block(x, packed, kv, heads, scale, eps, fused=None, out=None):
+    """The attention half of a Twins GSA block (gvt.py:105-127, :148): x (B, Lq, C) the residual stream, kv (B, Lk, 2C) packed
+    [2][heads][hd] as the `kv` Linear leaves it (k = kv[..., :C], v = kv[..., C:], read in place), packed = gsa_block_params(norm1, q, proj)
+    -> y (B, Lq, C) = x + proj(softmax(scale q k^T) v) with q = q(LayerNorm(x)).  out: the tensor y is written to (x itself updates the
+    stream in place).  tlxmi_gsa_block (ONE launch, four MFMA products, x read once and y written once) when the "gsa_block" option is on,
+    the tensors are fp16 and the library takes the shape (C 64 / 96 / 128, hd 32 / 64, Lk <= 64); otherwise the composition
+    engine.layernorm -> engine.linear -> engine.sr_attention -> engine.linear with the residual (fp32: the parity reference).
+    fused=True / False forces one form (tests, tools/); a forced unsupported call raises."""
+    need_gpu(x, "x")
+    need_gpu(kv, "kv")
+    heads = int(heads)
+    if (x.dim() != 3 or kv.dim() != 3 or x.dtype != kv.dtype or kv.shape[0] != x.shape[0] or kv.shape[2] != 2 * x.shape[2] or x.shape[2] % heads
+            or x.shape[2] != packed.C):
+        raise RuntimeError(f"gsa_block: x (B, Lq, C) and kv (B, Lk, 2C) of one dtype with C = {packed.C} a multiple of heads = {heads} are "
+                           f"expected, got {tuple(x.shape)} {x.dtype} / {tuple(kv.shape)} {kv.dtype}")
+    if x.stride(-1) != 1 or kv.stride(-1) != 1:
+        raise RuntimeError("gsa_block: the feature axis must be dense")
+    B, Lq, Cc = x.shape
+    Lk = kv.shape[1]
+    y = out if out is not None else torch.empty((B, Lq, Cc), dtype=x.dtype, device=x.device)
+    if tuple(y.shape) != tuple(x.shape) or y.dtype != x.dtype or y.stride(-1) != 1:
+        raise RuntimeError("gsa_block: out must have x's shape and dtype and a dense feature axis")
+    es = x.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(B * Lq * Cc * es, kv.numel() * es)
+    k, v = kv[..., :Cc], kv[..., Cc:]
+    d = _gsa_desc(x, kv, y, heads, scale, eps)
+    if fused is None:
+        fused = _gsa_takes(d, x, kv, y, packed)
+    if fused:
+        if packed.block is None or packed.block.device != x.device:
+            raise RuntimeError(f"gsa_block: no packed parameter block for C = {Cc} on {x.device}")
+        if _probe is not None:
+            e0, e1 = _probe_pair()
+        _lib.call("tlxmi_gsa_block", C.byref(d), _p(x), _p(k), _p(v), _p(packed.block), _p(y), _stream())
+        if _probe is not None:
+            e1.record()
+            _probe.append((e0, e1, (2 * B * Lq * Cc + 2 * B * Lk * Cc) * es + packed.block.numel() * 2,
+                           4 * B * Lq * Cc * Cc + 4 * B * Lq * Lk * Cc, (B, Lq, Lk, heads, Cc // heads, "gsa_block")))
+        return y
+    pkq, pkp = packed.linears(x.dtype)
+    xc = x if x.is_contiguous() else x.contiguous()
+    q = linear(layernorm(xc, packed.gamma, packed.beta, eps), pkq, packed.bq)
+    o = sr_attention(q, kv, heads, scale)
+    if out is None:
+        return linear(o, pkp, packed.bp, res=xc)
+    if out.is_contiguous():
+        linear(o, pkp, packed.bp, res=xc, out=out)
+    else:
+        out.copy_(linear(o, pkp, packed.bp, res=xc))
     return out
 
 

@@ -9,7 +9,12 @@ The recipes are chosen so that activations keep O(1) magnitude through deep resi
 fp16 throughput mode never saturates) while every BatchNorm statistic, bias and affine parameter
 is non-trivial (so a parity test would catch a dropped or mis-ordered term).
 """
+import re
+
 import numpy as np
+
+# Twins (gvt.py): blocks.<stage>.<index>.attn.{q, kv, qkv, proj} — the only tree whose blocks carry two indices
+_TWINS_ATTN = re.compile(r"^blocks\.\d+\.\d+\.attn\.(q|kv|qkv|proj)$")
 
 
 def image_batch(n, seed=0, hw=224, c=3):
@@ -56,6 +61,13 @@ def fill(shapes, seed):
       patch_pos                  as pos_embed;  pixel_pos  N(0, 0.5): a wrong (c, ky, kx) order moves logits               (TNT: tnt.py:211-216)
       *attn_in.* / *mlp_in.* weights   N(0, fan_in^-1/2), x 1.5 for attn_in.qk: TNT's inner transformer (24 channels) would otherwise add
                                  O(0.01) a block and its softmax would be uniform, so a wrong inner kernel would move no logit
+      blocks.<i>.<j>.attn.{q, kv, qkv, proj}.weights   Twins (gvt.py:52-56, :93-96): N(0, fan_in^-1/2), x 1.5 for q — for the same reason: at
+                                 N(0, 0.02) the scores of both attentions would be O(0.01), every softmax uniform, and the attention half of
+                                 a block would add O(0.01) to a stream of O(1); with these, 16 - 30 blocks add O(1) each and the stream
+                                 stays far inside fp16.  `attn.sr.filters` takes the conv rule (fan_in = sr^2 C; a LayerNorm follows it)
+      pos_block.<i>.proj.0.filters   Twins' PEG, a depthwise 3x3 added to its own input (gvt.py:311-325): N(0, fan_in^-1/2) = N(0, 1/3), so one
+                                 PEG multiplies the stream's variance by 2, not by 3, and the four of them keep it far inside fp16
+      pos_embeds.<i>             as pos_embed (gvt.py:240; PyramidVisionTransformer only: CPVTV2 deletes them)
     """
     rng = np.random.default_rng(seed)
     out = {}
@@ -63,7 +75,14 @@ def fill(shapes, seed):
         shape = tuple(shape)
         leaf = name.rsplit(".", 1)[-1]
         owner = name.rsplit(".", 1)[0] if "." in name else ""
-        if leaf == "filters":
+        if leaf == "filters" and owner.startswith("pos_block."):
+            a = rng.standard_normal(shape, dtype=np.float32) * np.float32(1.0 / np.sqrt(np.prod(shape[1:])))
+        elif leaf == "weights" and _TWINS_ATTN.match(owner):
+            gain = 1.5 if owner.endswith(".q") else 1.0
+            a = rng.standard_normal(shape, dtype=np.float32) * np.float32(gain / np.sqrt(shape[0]))
+        elif owner == "pos_embeds":
+            a = np.clip(rng.standard_normal(shape, dtype=np.float32), -2, 2) * np.float32(0.02)
+        elif leaf == "filters":
             fan_in = int(np.prod(shape[1:]))
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(np.sqrt(2.0 / fan_in))
         elif leaf == "weights" and ("attn_in." in owner + "." or "mlp_in." in owner + "."):      # TNT's inner transformer (tnt.py:125-129)
