@@ -490,9 +490,9 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
         const char* const wb = wbuf + (c & 1) * NP * PANEL;
         const bool more = c + 1 < nch;
         u32x4 st[NP][IPT], skn[PW];
-        if (more) {
-            stage_load(c + 1, st);
-            skip_load(c + 1, skn);
+        if (more) {       // (the ablation bits of seam_kernel, plus 32: no exchange — tuning flavour only, results are garbage)
+            if (!TLXMI_DBG(a, 8)) stage_load(c + 1, st);
+            if (!TLXMI_DBG(a, 2)) skip_load(c + 1, skn);
         }
         // ---- GEMM1: this wave's 32 of the step's 64 expand channels, both pixel blocks
         f32x4 acc1[2][PW];
@@ -500,6 +500,7 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
         for (int e = 0; e < 2; ++e) {
 #pragma unroll
             for (int pw = 0; pw < PW; ++pw) acc1[e][pw] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (TLXMI_DBG(a, 16)) continue;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const u32x4 af = *reinterpret_cast<const u32x4*>(wb + (ks >> 1) * PANEL + (a1off[e] ^ ((ks & 1) << 6)));
@@ -520,20 +521,21 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
                 const u32x2 o0 = bs_bn_skip_relu4(acc1[0][pw], s0, h0, half4v{rv[0], rv[1], rv[2], rv[3]});
                 const u32x2 o1 = bs_bn_skip_relu4(acc1[1][pw], s1, h1, half4v{rv[4], rv[5], rv[6], rv[7]});
                 const u32x4 o = u32x4{o0[0], o0[1], o1[0], o1[1]};
-                buf_store16(ysrd, o, pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * hh) * 2 : BUF_OOB);
-                *reinterpret_cast<u32x4*>(ymine + pw * 1024) = o;
+                if (!TLXMI_DBG(a, 1)) buf_store16(ysrd, o, pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * hh) * 2 : BUF_OOB);
+                if (!TLXMI_DBG(a, 32)) *reinterpret_cast<u32x4*>(ymine + pw * 1024) = o;
                 if (hh == 0) yf[pw][0] = o; else yf[pw][1] = o;
             }
         }
         __syncthreads();          // both halves of the step's y chunk are in LDS
 #pragma unroll
         for (int pw = 0; pw < PW; ++pw) {
-            const u32x4 o = *reinterpret_cast<const u32x4*>(ypart + pw * 1024);
+            const u32x4 o = TLXMI_DBG(a, 32) ? (hh == 0 ? yf[pw][0] : yf[pw][1]) : *reinterpret_cast<const u32x4*>(ypart + pw * 1024);
             if (hh == 0) yf[pw][1] = o; else yf[pw][0] = o;
         }
         // ---- GEMM2: row tiles 8 hh .. of the reduce conv, both k-steps of the step's 64 channels
 #pragma unroll
         for (int tt = 0; tt < T2H; ++tt) {
+            if (TLXMI_DBG(a, 16)) continue;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const u32x4 af = *reinterpret_cast<const u32x4*>(wb + (CB + hh * (Q2 / 2) + (tt >> 2)) * PANEL + (a2off[tt & 3] ^ (s << 4)));
@@ -568,11 +570,296 @@ __global__ __launch_bounds__(64 * NW, 1) void seam_pair_kernel(const SeamArgs a)
     }
 }
 
-template <int K1, int N2, int NW> static int launch_seam_pair_t(const SeamArgs& a, hipStream_t st) {
+// The wave-pair seam as TWO WAVE GROUPS IN ANTIPHASE.  In the form above all 8 waves pass each step's two barriers
+// together: while they wait for fragments, skip rows, the exchange or the next filters, the MFMA pipes of the CU idle, and the parts
+// of a step add up.  Here the pairs 0-1 (waves 0-3, group A) and 2-3 (waves 4-7, group B) — one wave of each group on every SIMD —
+// run half a step apart.  A step of a wave is cut into
+//     M(c):  the partner's half of y(c-1) from LDS;  GEMM1(c) -> acc1;  GEMM2(c-1): acc2 += W1'[:, chunk c-1] . y(c-1)
+//     N(c):  epilogue 1 of acc1 -> this wave's half of y(c): to the exchange slot, to HBM;  the skip rows of step c+1
+// one barrier after each.  With t the number of barriers passed, A runs M(c) at t = 2c and N(c) at t = 2c + 1, B one later: whenever
+// one group issues its 64 MFMAs (at raised priority) the other does its arithmetic, stores and loads.  Nothing changes in
+// any accumulator's MFMA sequence (GEMM1: k-steps ascending; GEMM2: steps, then k-steps, ascending) or in the one rounding of y.
+// Filters: set F(c) = { W3 rows of step c, W1' columns of step c-1 } is what M(c) reads, by A at t = 2c and by B at t = 2c + 1, from
+// buffer c & 1; the other buffer, last read at t = 2c - 1, is refilled by LDS-DMA sent at t = 2c — by A, at the start of its M(c), the W1'
+// half of F(c+1); by B, at the start of its N(c-1), the W3 half — 32 KB by 256 threads each, and each group waits for its own transfers
+// (vmcnt, counted by hand) before the barrier that ends t = 2c + 1.  Two buffers of K1/64 + N2/64 panels, the tables and the exchange
+// slots: the LDS footprint of the form above.
+// The exchange slot a wave writes in N(c) is read by its partner in M(c+1), one barrier later, and rewritten two barriers later.
+// Barriers are raw s_barrier after lgkmcnt(0) (__syncthreads would drain a transfer in flight): the y stores and the loads of later
+// phases stay in flight across them.
+template <int K1, int N2>
+__global__ __launch_bounds__(512, 1) void seam_pair_ap_kernel(const SeamArgs a) {
+    static_assert(N2 % 128 == 0, "pairs of waves split N2 in halves of whole 64-channel blocks");
+    constexpr int NW = 8, GT = 256;      // waves; threads of a group
+    constexpr int PW = 2;
+    constexpr int KS = K1 / 32;
+    constexpr int CB = K1 / 64;
+    constexpr int Q2 = N2 / 64;
+    constexpr int NP = CB + Q2;
+    constexpr int SP = CB > Q2 ? CB : Q2;      // panels of the larger filter half
+    constexpr int T2H = N2 / 32;
+    constexpr int PANEL = 64 * 128;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* const wbuf = smem;
+    float* const tab3 = reinterpret_cast<float*>(smem + 2 * NP * PANEL);
+    float* const tab1 = tab3 + 2 * a.N1;
+    char* const ybuf = reinterpret_cast<char*>(tab1 + 2 * N2);                  // [wave][pw][64 lanes][16 bytes]
+
+    const int t = threadIdx.x, lane = t & 63, tg = t & (GT - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int hh = wid & 1, pp = wid >> 1, grp = wid >> 2;
+    const int fr = lane & 15, g = lane >> 4;
+    const int nch = a.N1 >> 6;
+
+    const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), w3srd = buf_srd(a.w3, a.w3_bytes);
+    const __amdgpu_buffer_rsrc_t rsrd = buf_srd(a.res, a.res_bytes), ysrd = buf_srd(a.y, a.y_bytes), zsrd = buf_srd(a.z, a.z_bytes);
+
+    // Filter staging is LDS-DMA: one wave instruction moves 64 x 16 bytes from per-lane buffer offsets to the 1 KiB at a wave-uniform
+    // LDS address, so the image is lane-linear — chunk k*GT + tg of a panel at byte (k*GT + tg) * 16 — and the swizzle sits in the
+    // source offset: the chunk at (row, physical slot) = index >> 3, index & 7 is the logical chunk slot ^ f(row).  No staging
+    // registers, no ds_write pass (13 cycles a wave for 16 bytes a lane); the waits are counted by hand (below).
+    // The half a group stages step after step — descriptor, offsets at step 0, stride per step and per panel, chosen once:
+    //   A: the W1' columns of step c       -> panels CB .. of buffer (c + 1) & 1
+    //   B: the W3 rows of step c + 2       -> panels 0 ..  of buffer c & 1
+    static_assert(CB == Q2, "both filter halves of a step are the same number of panels");
+    const int wq = wid & 3;      // this wave in its group
+    const __amdgpu_buffer_rsrc_t ssrd = buf_srd(grp == 0 ? a.w1 : a.w3, grp == 0 ? a.w1_bytes : a.w3_bytes);
+    const int sstep = grp == 0 ? 128 : 64 * K1 * 2, spanel = grp == 0 ? 64 * a.N1 * 2 : 128;
+    int soff[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int idx = k * GT + tg, srow = idx >> 3, sslot = idx & 7;
+        soff[k] = grp == 0 ? (srow * a.N1 + 8 * (sslot ^ bs_f2(srow))) * 2 : ((128 + srow) * K1 + 8 * (sslot ^ bs_f1(srow))) * 2;
+    }
+    // (dead: 0, or BUF_OOB for a transfer that fetches nothing — it fills its piece with zeros)
+    auto stage_dma = [&](int c, int dead) __attribute__((always_inline)) {
+        char* const dst = wbuf + (grp == 0 ? (((c + 1) & 1) * NP + CB) : ((c & 1) * NP)) * PANEL + wq * 1024;
+#pragma unroll
+        for (int j = 0; j < SP; ++j)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) buf_dma16(ssrd, dst + j * PANEL + k * (GT * 16), (soff[k] + j * spanel + c * sstep) | dead);
+    };
+    // LDS writes of this wave are done, then the workgroup barrier; vector memory operations stay in flight
+    auto phase_barrier = [&]() {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    const int m0 = ((int)blockIdx.x * (NW / 2) + pp) * (16 * PW);
+    int pix[PW];
+    bool pok[PW];
+#pragma unroll
+    for (int pw = 0; pw < PW; ++pw) {
+        pix[pw] = m0 + 16 * pw + fr;
+        pok[pw] = pix[pw] < a.M;
+    }
+    u32x4 xf[KS][PW];
+#pragma unroll
+    for (int pw = 0; pw < PW; ++pw)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            xf[ks][pw] = buf_load16(xsrd, pok[pw] ? (pix[pw] * a.x_ld + 32 * ks + 8 * g) * 2 : BUF_OOB);
+    auto skip_load = [&](int c, u32x4 (&sk)[PW], int dead) {
+#pragma unroll
+        for (int pw = 0; pw < PW; ++pw) sk[pw] = buf_load16(rsrd, pok[pw] ? ((pix[pw] * a.res_ld + 64 * c + 16 * g + 8 * hh) * 2) | dead : BUF_OOB);
+    };
+    u32x4 sk[PW];
+    skip_load(0, sk, 0);
+    // prologue: group A stages the W3 rows of step 0 into buffer 0, group B those of step 1 into buffer 1
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int idx = k * GT + tg, srow = idx >> 3, sl1 = (idx & 7) ^ bs_f1(srow);
+#pragma unroll
+        for (int j = 0; j < CB; ++j)
+            buf_dma16(w3srd, wbuf + (grp * NP + j) * PANEL + k * (GT * 16) + wq * 1024, ((64 * grp + srow) * K1 + 64 * j + 8 * sl1) * 2);
+    }
+    for (int i = t; i < a.N1; i += 64 * NW) {
+        tab3[i] = a.scale3 ? a.scale3[i] : 1.f;
+        tab3[a.N1 + i] = a.shift3 ? a.shift3[i] : 0.f;
+    }
+    for (int i = t; i < N2; i += 64 * NW) {
+        tab1[i] = a.scale1 ? a.scale1[i] : 1.f;
+        tab1[N2 + i] = a.shift1 ? a.shift1[i] : 0.f;
+    }
+    wait_vmcnt<0>();      // the transfers have landed
+    __syncthreads();
+
+    const int arow = 16 * (fr >> 2) + (fr & 3);
+    int a1off[2], a2off[4];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int r = arow + 4 * (2 * hh + e);
+        a1off[e] = r * 128 + ((g ^ bs_f1(r)) << 4);
+    }
+#pragma unroll
+    for (int ci = 0; ci < 4; ++ci) {
+        const int r = arow + 4 * ci;
+        a2off[ci] = r * 128 + (((2 * g) ^ bs_f2(r)) << 4);
+    }
+    char* const ymine = ybuf + (wid * PW * 64 + lane) * 16;
+    const char* const ypart = ybuf + ((wid ^ 1) * PW * 64 + lane) * 16;
+
+    f32x4 acc2[T2H][PW];
+#pragma unroll
+    for (int tt = 0; tt < T2H; ++tt)
+#pragma unroll
+        for (int pw = 0; pw < PW; ++pw) acc2[tt][pw] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc1[2][PW];
+    u32x4 yown[PW], ypar[PW];      // this wave's half of the step's y chunk (k-step hh of GEMM2) and its partner's (k-step hh ^ 1)
+#pragma unroll
+    for (int pw = 0; pw < PW; ++pw) yown[pw] = ypar[pw] = u32x4{0u, 0u, 0u, 0u};
+
+    // M(c).  FIRST: c = 0, there is no step before it (no GEMM2); LAST: c = nch, there is no step c (GEMM2 only, nothing to stage).
+    // GRP is a compile-time constant: the step loop exists once per group (run, below), each copy straight-line code, so that the
+    // compiler's counted waits (vmcnt) leave exactly the younger loads and stores in flight.  For the same reason the staging and skip
+    // loads of the last steps are not branched around: past the end they fetch nothing, into a buffer half that is dead.
+    auto m_phase = [&](int c, auto grp_t, auto first_t, auto last_t) __attribute__((always_inline)) {
+        constexpr int GRP = decltype(grp_t)::value;
+        constexpr bool FIRST = decltype(first_t)::value, LAST = decltype(last_t)::value;
+        const char* const wb = wbuf + (c & 1) * NP * PANEL;
+        // A: the W1' columns of step c go out now: their half of buffer (c + 1) & 1 was last read one barrier ago, by B
+        if constexpr (GRP == 0 && !LAST) stage_dma(c, (TLXMI_DBG(a, 8) && !FIRST) ? BUF_OOB : 0);
+        if constexpr (!FIRST) {      // the partner's half of y(c-1), written one barrier ago
+            if (!TLXMI_DBG(a, 32)) {
+#pragma unroll
+                for (int pw = 0; pw < PW; ++pw) ypar[pw] = *reinterpret_cast<const u32x4*>(ypart + pw * 1024);
+            }
+        }
+        if constexpr (!LAST) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+#pragma unroll
+                for (int pw = 0; pw < PW; ++pw) acc1[e][pw] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        // The phase's A fragments in the order they are used — GEMM1 of step c: k-step ks, sub-tile e at 2 ks + e (this wave's 32 of the
+        // step's 64 expand channels); then GEMM2 of step c - 1: k-step s, row tile tt at T2H s + tt (row tiles 8 hh .. of the reduce conv) —
+        // each feeding the MFMAs of both pixel blocks.  Only this wave issues MFMAs on its SIMD now, so nobody hides its LDS latency:
+        // the reads run FD fragments ahead of their use, in a ring of registers, and the order is pinned.
+        constexpr int FD = 5;
+        constexpr int NF1 = LAST ? 0 : 2 * KS, NF2 = FIRST ? 0 : 2 * T2H, NF = NF1 + NF2;
+        auto frag = [&](int i) __attribute__((always_inline)) {
+            if (i < NF1) return *reinterpret_cast<const u32x4*>(wb + (i >> 2) * PANEL + (a1off[i & 1] ^ (((i >> 1) & 1) << 6)));
+            const int s = (i - NF1) / T2H, tt = (i - NF1) % T2H;
+            return *reinterpret_cast<const u32x4*>(wb + (CB + hh * (Q2 / 2) + (tt >> 2)) * PANEL + (a2off[tt & 3] ^ (s << 4)));
+        };
+        if (!TLXMI_DBG(a, 16)) {
+            u32x4 ring[FD], yk[2][PW];
+#pragma unroll
+            for (int i = 0; i < FD; ++i) ring[i] = frag(i);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int i = 0; i < NF; ++i) {
+                if constexpr (!FIRST) {
+                    if (i == NF1) {      // GEMM2's B fragments by k-step: this wave's half of y(c-1) is k-step hh
+#pragma unroll
+                        for (int pw = 0; pw < PW; ++pw) {
+                            yk[0][pw] = hh == 0 ? yown[pw] : ypar[pw];
+                            yk[1][pw] = hh == 0 ? ypar[pw] : yown[pw];
+                        }
+                    }
+                }
+                const u32x4 af = ring[i % FD];
+                if (i < NF1) {
+#pragma unroll
+                    for (int pw = 0; pw < PW; ++pw) acc1[i & 1][pw] = Mma<half_t>::run(af, xf[i >> 1][pw], acc1[i & 1][pw]);
+                } else {
+#pragma unroll
+                    for (int pw = 0; pw < PW; ++pw) acc2[(i - NF1) % T2H][pw] = Mma<half_t>::run(af, yk[(i - NF1) / T2H][pw], acc2[(i - NF1) % T2H][pw]);
+                }
+                if (i + FD < NF) ring[i % FD] = frag(i + FD);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_s_setprio(0);
+        }
+        // B: the transfers of its last N phase (8, then 2 skip loads and 2 y stores, which stay in flight) have landed
+        if constexpr (GRP == 1 && !FIRST) wait_vmcnt<4>();
+        phase_barrier();      // this group is done with buffer c & 1 and with its partner's slots
+    };
+    // N(c)
+    auto n_phase = [&](int c, auto grp_t) __attribute__((always_inline)) {
+        constexpr int GRP = decltype(grp_t)::value;
+        // B: the W3 rows of step c + 2 go out now, into the half of buffer c & 1 that B itself read until the barrier just passed
+        // (past the last step: zeros into a half nobody reads again)
+        if constexpr (GRP == 1) {
+            stage_dma(c, (c + 2 < nch && !TLXMI_DBG(a, 8)) ? 0 : BUF_OOB);
+            __builtin_amdgcn_sched_barrier(0);      // the count of the wait in M(c+1) has them issued before this phase's loads and stores
+        }
+        {      // ---- epilogue 1 of the half: BN, + skip, ReLU; handed to the partner wave and stored to y
+            const float* sc = tab3 + 64 * c + 16 * g + 8 * hh;
+            const float* sh = sc + a.N1;
+            const f32x4 s0 = *reinterpret_cast<const f32x4*>(sc), s1 = *reinterpret_cast<const f32x4*>(sc + 4);
+            const f32x4 h0 = *reinterpret_cast<const f32x4*>(sh), h1 = *reinterpret_cast<const f32x4*>(sh + 4);
+            u32x4 o[PW];
+#pragma unroll
+            for (int pw = 0; pw < PW; ++pw) {
+                const half8v rv = __builtin_bit_cast(half8v, sk[pw]);
+                const u32x2 o0 = bs_bn_skip_relu4(acc1[0][pw], s0, h0, half4v{rv[0], rv[1], rv[2], rv[3]});
+                const u32x2 o1 = bs_bn_skip_relu4(acc1[1][pw], s1, h1, half4v{rv[4], rv[5], rv[6], rv[7]});
+                o[pw] = u32x4{o0[0], o0[1], o1[0], o1[1]};
+                if (!TLXMI_DBG(a, 32)) *reinterpret_cast<u32x4*>(ymine + pw * 1024) = o[pw];
+                yown[pw] = o[pw];
+            }
+            // the skip rows of the next step go out before the y stores and are used two barriers on
+            skip_load(c + 1, sk, (c + 1 < nch && !TLXMI_DBG(a, 2)) ? 0 : BUF_OOB);
+            if (!TLXMI_DBG(a, 1)) {
+#pragma unroll
+                for (int pw = 0; pw < PW; ++pw) buf_store16(ysrd, o[pw], pok[pw] ? (pix[pw] * a.y_ld + 64 * c + 16 * g + 8 * hh) * 2 : BUF_OOB);
+            }
+        }
+        // A: the transfers of this step's M phase (8, then the 2 skip loads and 2 y stores above, which stay in flight) have landed
+        if constexpr (GRP == 0) wait_vmcnt<4>();
+        phase_barrier();      // the exchange slots and this group's half of the next filter set are written
+    };
+    // One copy of the step loop per group: each is straight-line code whose loads and stores the compiler counts exactly
+    auto run = [&](auto grp_t) __attribute__((always_inline)) {
+        if constexpr (decltype(grp_t)::value == 1) phase_barrier();      // group B runs one barrier behind
+        m_phase(0, grp_t, std::true_type{}, std::false_type{});
+        n_phase(0, grp_t);
+#pragma unroll 1
+        for (int c = 1; c < nch; ++c) {
+            m_phase(c, grp_t, std::false_type{}, std::false_type{});
+            n_phase(c, grp_t);
+        }
+        m_phase(nch, grp_t, std::false_type{}, std::true_type{});
+    };
+    if (grp == 0) run(std::integral_constant<int, 0>{});
+    else run(std::integral_constant<int, 1>{});
+
+    // ---- epilogue 2: this wave's half of t1
+#pragma unroll
+    for (int q = 0; q < Q2 / 2; ++q) {
+        const float* sc = tab1 + 64 * (hh * (Q2 / 2) + q) + 16 * g;
+        const float* sh = sc + N2;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const f32x4 s0 = *reinterpret_cast<const f32x4*>(sc + 8 * h), s1 = *reinterpret_cast<const f32x4*>(sc + 8 * h + 4);
+            const f32x4 h0 = *reinterpret_cast<const f32x4*>(sh + 8 * h), h1 = *reinterpret_cast<const f32x4*>(sh + 8 * h + 4);
+#pragma unroll
+            for (int pw = 0; pw < PW; ++pw) {
+                const u32x2 o0 = bs_bn_relu4(acc2[4 * q + 2 * h][pw], s0, h0), o1 = bs_bn_relu4(acc2[4 * q + 2 * h + 1][pw], s1, h1);
+                const u32x4 o = u32x4{o0[0], o0[1], o1[0], o1[1]};
+                buf_store16(zsrd, o, pok[pw] ? (pix[pw] * a.z_ld + 64 * (hh * (Q2 / 2) + q) + 16 * g + 8 * h) * 2 : BUF_OOB);
+            }
+        }
+    }
+    if (grp == 0) phase_barrier();      // barrier counts match again
+}
+
+// The product's form of the wave-pair seam (the tuning flavour reaches the other one through TLXMI_SEAM bit 6: the parity arm and A/B)
+constexpr bool SEAM_PAIR_ANTIPHASE = true;
+
+// AP: the antiphase form; both forms take the same workgroup (8 waves, 128 pixels) and the same LDS
+template <int K1, int N2, int NW, bool AP> static int launch_seam_pair_t(const SeamArgs& a, hipStream_t st) {
+    static_assert(!AP || NW == 8, "the antiphase form is two groups of four waves");
     constexpr int NP = K1 / 64 + N2 / 64;
     const size_t lds = (size_t)2 * NP * 64 * 128 + (size_t)(2 * a.N1 + 2 * N2) * sizeof(float) + (size_t)NW * 2 * 1024;
     if (lds > 160 * 1024) return fail(TLXMI_ERR_UNSUPPORTED, "block_seam: %zu bytes of LDS", lds);
-    const void* fn = reinterpret_cast<const void*>(&seam_pair_kernel<K1, N2, NW>);
+    const void* fn;
+    if constexpr (AP) fn = reinterpret_cast<const void*>(&seam_pair_ap_kernel<K1, N2>);
+    else fn = reinterpret_cast<const void*>(&seam_pair_kernel<K1, N2, NW>);
     if (int rc = raise_lds_limit(fn, 160 * 1024, "block_seam")) return rc;
     const long grid = ((long)a.M + NW * 16 - 1) / (NW * 16);
     if (grid >= (1l << 31)) return fail(TLXMI_ERR_UNSUPPORTED, "block_seam: too many rows");
@@ -627,7 +914,7 @@ int launch_mlp_seam(const SeamArgs& a0, int K1, int N2, hipStream_t st) {
 }
 
 int launch_block_seam(const SeamArgs& a0, int K1, int N2, hipStream_t st) {
-    const int vv = (int)tune_int("TLXMI_SEAM", 0);     // tuning flavour: bit 0 = the other workgroup shape, bit 1 / 2 = flip the t1 / y store policy (A/B)
+    const int vv = (int)tune_int("TLXMI_SEAM", 0);     // tuning flavour: bit 0 = the other workgroup shape, bit 1 / 2 = flip the t1 / y store policy (A/B), bit 4 / 5 / 6 below
     const int v = vv & 1;
     SeamArgs b = a0;
     b.z_nt = (vv & 2) ? 1 : 0;        // t1 is small and read back at once by the next conv: a plain store keeps it in the Infinity Cache (-124 us per ResNet-50 forward vs nt)
@@ -652,7 +939,10 @@ int launch_block_seam(const SeamArgs& a0, int K1, int N2, hipStream_t st) {
     if (K1 == 128 && N2 == 128) return v ? launch_seam_t<128, 128, 2, 4>(a, st) : launch_seam_t<128, 128, 2, 8>(a, st);
     if (K1 == 128 && N2 == 256) return v ? launch_seam_t<128, 256, 1, 4>(a, st) : launch_seam_t<128, 256, 1, 8>(a, st);
     if (K1 == 256 && N2 == 256) {
-        if (!(vv & 32)) return launch_seam_pair_t<256, 256, 8>(a, st);      // TLXMI_SEAM bit 5 (A/B): the one-wave-per-16-pixels form
+#ifdef TLXMI_TUNING
+        if (vv & 64) return launch_seam_pair_t<256, 256, 8, !SEAM_PAIR_ANTIPHASE>(a, st);      // TLXMI_SEAM bit 6 (A/B, parity arm): the other wave-pair form
+#endif
+        if (!(vv & 32)) return launch_seam_pair_t<256, 256, 8, SEAM_PAIR_ANTIPHASE>(a, st);      // TLXMI_SEAM bit 5 (A/B): the one-wave-per-16-pixels form
         return v ? launch_seam_t<256, 256, 1, 4>(a, st) : launch_seam_t<256, 256, 1, 8>(a, st);
     }
     return fail(TLXMI_ERR_UNSUPPORTED, "block_seam: no instantiation for %d -> N1 -> %d channels", K1, N2);

@@ -20,6 +20,12 @@ __all__ = ['resnet18', 'resnet34', 'resnet50', 'resnet101', 'resnet152', 'wide_r
 
 _HE = nn.initializers.HeNormal()
 
+# images per launch between which the 14 x 14 seams (256 -> 1024 -> 256) run as one fused launch (BottleneckBlock.seam_with; a module
+# constant so that tools/seam14_gate.py can open the gate and measure both sides of each bound).  With the antiphase kernel
+# (profiles/seam_antiphase/batch_table.txt, fused against two launches on the same graph replay): 32 a launch -1.9 %, 64 on one stream
+# -0.4 %, 48 / 64 inside a two-stream forward +4.5 / +2.9 %, 96 / 128 / 192 +2.9 / +1.4 / +4.0 %, 256 +2.3 %; more than 256 not measured
+SEAM14_IMAGES = (48, 256)
+
 
 def _conv(cin, cout, k, stride=1, padding=0, dilation=1, groups=1, data_format='channels_first'):
     return nn.GroupConv2d(in_channels=cin, out_channels=cout, kernel_size=k, stride=stride, padding=padding,
@@ -185,13 +191,15 @@ class BottleneckBlock(nn.Module):
         # Where the fused launch pays (tools/small_batch.py, graph replay, one box): a seam runs its 64-channel steps one after
         # the other, so with few pixels it is a chain of latencies — batch 1 0.91 ms with all seams, 0.78 without the 14 x 14
         # ones, 0.74 without any; from 16 images the 56 x 56 / 28 x 28 seams win (batch 32: 1.09 vs 1.14 ms), the 14 x 14 ones
-        # (1 MB of filters per 128 pixels) only from ~96 images a launch.
+        # (1 MB of filters per 128 pixels) only from more images a launch: SEAM14_IMAGES.
         n_img = out.shape[0]
         # (round 5, tools/batch_table.py: at 512 images = 2 x 256 per launch the 14 x 14 seams LOSE 2.3 % to two persistent GEMM launches —
         #  their 1 MB of filters per 128 pixels is re-streamed 196 times per CU; at 2 x 128 they win 1.7 %: fused up to 192 images a launch)
         #  end of round 5, same table: inside a two-stream forward of 96 / 128 images (48 / 64 a launch) they lose 1.1 / 1.9 % as well — 96 ... 192 images
         #  a launch whatever the stream arrangement)
-        if n_img < 12 or (c3.in_channels >= 256 and (n_img < 96 or n_img > 192)):
+        # (both bounds moved with the antiphase form of the 14 x 14 kernel, which no longer loses at 48 ... 64 and at 256 images a launch:
+        #  SEAM14_IMAGES above)
+        if n_img < 12 or (c3.in_channels >= 256 and not SEAM14_IMAGES[0] <= n_img <= SEAM14_IMAGES[1]):
             return None
         pk3 = c3._cached("pk", lambda: E.PackedFilter(c3.filters, dt))
         pk1 = c1._cached("pk", lambda: E.PackedFilter(c1.filters, dt))

@@ -1,6 +1,6 @@
 """Throughput against batch: ResNet-50 / ViT-B/16 / Swin-B at batch 1, 8, 32, 64, 96, 128, 256, 512 on the hipGraph replay, with the
 dispatch switch points of each batch marked AND measured: every host-side switch that changes at some batch is toggled on the same graph
-replay — two_streams (forwards of >= 96 / 32 / 32 images), the bottleneck seams (>= 12 images per launch; the 14 x 14 ones from 96 to 192 images
+replay — two_streams (forwards of >= 96 / 32 / 32 images), the bottleneck seams (>= 12 images per launch; the 14 x 14 ones from 48 to 256 images
 per launch), split-K (classifier head <= 512 rows, 7 x 7 convs with few tiles), the folded LayerNorm (>= 2048 token rows per launch).
 Output -> profiles/<round>/batch_table.txt.   usage: batch_table.py [models] [batches]"""
 import os

@@ -1,5 +1,7 @@
 """What binds the bottleneck seam: the launch with parts switched off (tuning flavour, TLXMI_SEAM_DBG bits: 1 no y store,
-2 no skip loads, 4 no t1 store, 8 no filter staging after the first step, 16 no MFMAs).  Timing only — results are garbage."""
+2 no skip loads, 4 no t1 store, 8 no filter staging after the first step, 16 no MFMAs, 32 no exchange between the waves of a pair
+— the wave-pair forms of 256 -> N1 -> 256 know 1, 2, 8, 16, 32).  Timing only — results are garbage.
+usage: seam_ablate.py [cases, comma separated] [batch] [TLXMI_SEAM variant] [K1: only the shapes with this many input channels]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -10,9 +12,13 @@ from tlxcv_amd import engine as E
 
 dev = torch.device("cuda:0")
 tlxcv_amd.set_precision("fp16")
-B = 256
+B = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+os.environ["TLXMI_SEAM"] = sys.argv[3] if len(sys.argv) > 3 else "0"
+ONLY = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 CASES = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else "0,1,2,4,8,16,3,7,19,23,31".split(","))]
 for K1, N1, N2, hw in ((64, 256, 64, 56), (128, 512, 128, 28), (128, 512, 256, 28), (256, 1024, 256, 14)):
+    if ONLY and K1 != ONLY:
+        continue
     g = torch.Generator().manual_seed(1)
     t2 = torch.randn((B, hw, hw, K1), generator=g).half().to(dev)
     skip = torch.randn((B, hw, hw, N1), generator=g).half().to(dev)

@@ -1,5 +1,6 @@
 """Interleaved A/B per ResNet-50 stage, batch 256: the bottleneck seam as one launch (per TLXMI_SEAM variant) vs conv3 + skip and
-conv1 as two.  usage: seam_micro.py [batch] [variants, comma separated: 0,8]"""
+conv1 as two.  usage: seam_micro.py [batch] [variants, comma separated: 0,8] [K1: only the shapes with this many input channels]
+(variant 64: the other form of the wave-pair seam 256 -> N1 -> 256 — lock step where the product runs two wave groups in antiphase)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,6 +16,8 @@ tlxcv_amd.set_precision("fp16")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 VARS = ["0"] if PRODUCT else [v for v in (sys.argv[2].split(",") if len(sys.argv) > 2 else ["0"])]
 for K1, N1, N2, hw in ((64, 256, 64, 56), (64, 256, 128, 56), (128, 512, 128, 28), (128, 512, 256, 28), (256, 1024, 256, 14)):
+    if len(sys.argv) > 3 and K1 != int(sys.argv[3]):
+        continue
     g = torch.Generator().manual_seed(1)
     t2 = torch.randn((B, hw, hw, K1), generator=g).half().to(dev)
     skip = torch.randn((B, hw, hw, N1), generator=g).half().to(dev)
