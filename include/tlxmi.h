@@ -495,6 +495,42 @@ int tlxmi_lka_gate(const tlxmi_lka_gate_desc* d, const void* a1, const void* t, 
                    const float* res_scale, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ShuffleNetV2's units (classification/shufflenetv2.py:43-107).
+ *
+ * tlxmi_shuffle_unit: the stride-1 InvertedResidual (:54-76) in one launch.  x: N*H*W pixels of pitch x_ld, C = 2 h channels used:
+ *     hid1 = fp16( act( pw1(x[..., h:C]) * s1 + t1 ) )                  1 x 1, h -> h
+ *     hid2 = fp16( dw3x3(hid1, zero padding 1) * s2 + t2 )              no activation
+ *     f    = act( pw2(hid2) * s3 + t3 )                                 1 x 1, h -> h
+ *     y[..., 2 i] = x[..., i]  (bit copy),   y[..., 2 i + 1] = fp16(f[i]),   i < h
+ * fp32 accumulation; the two roundings shown are where three separate launches store fp16.  hid1 at a position OUTSIDE the image is
+ * zero (the depthwise's padding), not act(t1).  Only the C channels of a pixel are read, and nothing is computed from the passthrough
+ * half: whatever the columns behind C or that half hold (Inf, NaN) reaches no other output.  y has pitch y_ld; the columns
+ * [C, min(y_ld, roundup(C, 8))) are written as zeros (later convs read a padded map through zero filter columns), the columns behind
+ * them are left untouched.  y aliases no input.  One writer per element, fixed summation order, no atomics.
+ * params: tlxmi_shuffle_unit_param_bytes(h) bytes, Kp = h rounded up to 32, everything beyond h zero:
+ *     fp16 w1[Kp][Kp] (row = output channel), fp16 w2[Kp][Kp], fp16 wdw[9][Kp] (tap r * 3 + s), fp32 s1, t1, s2, t2, s3, t3 [Kp] each.
+ * tlxmi_shuffle_unit_supported() is pure host code and answers 1 exactly for: fp16; N, H, W >= 1; C even, 2 <= C <= 256 (h <= 128:
+ * wider units run as tlxmi_conv2d, tlxmi_dwconv2d, tlxmi_conv2d, tlxmi_shuffle_concat); x_ld >= C; y_ld >= C and even; act ReLU or SiLU;
+ * (pixels * x_ld + 256) * 2 and (pixels * y_ld + 512) * 2 below 2^31 (32-bit byte offsets).  1 means the call is taken, given x, params
+ * and y 16-byte aligned (TLXMI_ERR_ALIGNMENT otherwise); anything else returns TLXMI_ERR_UNSUPPORTED.
+ *
+ * tlxmi_shuffle_concat: concat + channel_shuffle(2) of two maps (:75-76, :106-107), fp16 or fp32: y[r][2 i] = a[r][i],
+ * y[r][2 i + 1] = b[r][i], i < h; pitches a_ld, b_ld >= h and y_ld >= 2 h; the same zero-pad rule for [2 h, min(y_ld, roundup(2 h, 8))).
+ * 64-bit offsets.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_shuffle_unit_desc {
+    int32_t dtype;
+    int32_t N, H, W, C;
+    int32_t x_ld, y_ld;
+    int32_t act;
+} tlxmi_shuffle_unit_desc;
+int tlxmi_shuffle_unit_supported(const tlxmi_shuffle_unit_desc* d);
+size_t tlxmi_shuffle_unit_param_bytes(int h);
+int tlxmi_shuffle_unit(const tlxmi_shuffle_unit_desc* d, const void* x, const void* params, void* y, void* stream);
+int tlxmi_shuffle_concat(const void* a, const void* b, void* y, int dtype, int64_t rows, int h, int a_ld, int b_ld, int y_ld,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

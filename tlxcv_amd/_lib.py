@@ -48,6 +48,10 @@ class LkaDwDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "C", "x_ld", "y_ld")]
 
 
+class ShuffleUnitDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "C", "x_ld", "y_ld", "act")]
+
+
 class LkaGateDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in ("C", "a1_ld", "t_ld", "res_ld", "y_ld")]
 
@@ -172,6 +176,8 @@ PROTOTYPES = {
     "tlxmi_lka_dw": [C.POINTER(LkaDwDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_lka_gate": [C.POINTER(LkaGateDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "tlxmi_mul": [_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp],
+    "tlxmi_shuffle_unit": [C.POINTER(ShuffleUnitDesc), _vp, _vp, _vp, _vp],
+    "tlxmi_shuffle_concat": [_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -202,6 +208,8 @@ _SPECIAL = {
     "tlxmi_gsa_block_param_count": ([_i], C.c_size_t),
     "tlxmi_lka_dw_supported": ([C.POINTER(LkaDwDesc)], C.c_int),
     "tlxmi_lka_gate_supported": ([C.POINTER(LkaGateDesc)], C.c_int),
+    "tlxmi_shuffle_unit_supported": ([C.POINTER(ShuffleUnitDesc)], C.c_int),
+    "tlxmi_shuffle_unit_param_bytes": ([_i], C.c_size_t),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 
@@ -243,7 +251,7 @@ def load():
 class tuning:
     """`with _lib.tuning(TLXMI_TILE="7"): ...` — run the enclosed calls on the TUNING flavour of the library
     (libtlxmi_tune.so: the same sources built with -DTLXMI_TUNING), which reads the A/B knobs (TLXMI_TILE, TLXMI_HALO,
-    TLXMI_TAIL, TLXMI_PP128, TLXMI_STORE, TLXMI_DWSTRIP, TLXMI_PANEL_KB, TLXMI_DEBUG) from the environment on every call.
+    TLXMI_TAIL, TLXMI_PP128, TLXMI_STORE, TLXMI_DWSTRIP, TLXMI_PANEL_KB, TLXMI_SU_THREADS, TLXMI_DEBUG) from the environment on every call.
     The product library never does: outside this context no environment variable changes a kernel choice or a result.
     Used by tools/ab_*.py and by the tests that force a tile candidate the dispatcher would not pick at test sizes."""
 

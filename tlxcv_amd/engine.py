@@ -77,6 +77,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # q Linear -> attention -> proj + residual on tlxmi_gsa_block: ONE launch, K / V of an image and both weights
                                   # staged in LDS, four chained MFMA products, the residual stream read once and written once; elsewhere and
                                   # off = tlxmi_layernorm -> tlxmi_conv2d -> tlxmi_sr_attention -> tlxmi_conv2d (the A/B and the tests' other arm)
+            "shuffle_unit": True, # ShuffleNetV2's stride-1 units (fp16, half width h <= 128): split -> 1x1 + BN + act -> depthwise 3x3 + BN -> 1x1 + BN + act
+                                  # -> concat -> channel_shuffle on tlxmi_shuffle_unit: ONE launch, both hidden maps in LDS, both products on MFMA,
+                                  # the pixel read once and written once with the shuffle in the store; elsewhere and off = tlxmi_conv2d ->
+                                  # tlxmi_dwconv2d -> tlxmi_conv2d -> tlxmi_shuffle_concat (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -611,12 +615,17 @@ def _pair(v):
 
 def conv2d(x, pk, stride=1, padding=0, dilation=1, scale=None, shift=None, res=None, act=ACT_NONE,
            act_param=0.0, res_after_act=False, out=None, out_ld=None, y_nstride=0, res_nstride=0,
-           res_bcast=False, res_ld=None, out_hw=None, overhang=False, maxpool3s2=False):
+           res_bcast=False, res_ld=None, out_hw=None, overhang=False, maxpool3s2=False, x_ld=None):
     """x (N,H,W,C>=Cin_pad...) NHWC -> y (N,Ho,Wo,Cout).  `out` may be a wider/pre-offset buffer.
     maxpool3s2: fold nn.MaxPool2d(3, 2, 1) into the conv's epilogue (TLXMI_EPI_MAXPOOL_3S2P1) -> (N,Ho/2,Wo/2,Cout);
-    returns None — nothing launched — when the library has no fused kernel for this geometry."""
+    returns None — nothing launched — when the library has no fused kernel for this geometry.
+    x_ld: the pixel pitch when x is a 16-byte aligned column slice of a wider map (a view: its last axis is the slice's width)."""
     need_gpu(x, "input")
     N, H, W, ld = x.shape
+    if x_ld is not None:
+        if x_ld < ld or pk.Cin_pad > ld:
+            raise RuntimeError(f"conv2d: a column slice of {ld} channels at pitch {x_ld} cannot feed a filter of {pk.Cin_pad}")
+        ld = int(x_ld)
     if x.dtype != pk.dtype:
         raise RuntimeError(f"conv2d: input dtype {x.dtype} != packed filter dtype {pk.dtype}")
     if ld < pk.Cin_pad:
@@ -1399,6 +1408,166 @@ def lka_gate(a1, t, pk1, scale1, shift1, pk2, scale2, shift2, res, res_scale, fu
         _probe = probe
     probe.append((e0, e1, (4 * rows * Cc + 2 * Cc * Cc) * es, 4 * rows * Cc * Cc, (rows, 1, 1, Cc, Cc, "lka_gate" if fused else "conv-mul-affine-conv")))
     return y
+
+
+# ---------------------------------------------------------------------------------------------
+# ShuffleNetV2 units
+# ---------------------------------------------------------------------------------------------
+SHUFFLE_PAD = 8       # a shuffled map of c channels is kept at pitch roundup(c, 8), the columns behind c zero (both dtypes)
+
+
+def shuffle_pitch(c):
+    return (int(c) + SHUFFLE_PAD - 1) // SHUFFLE_PAD * SHUFFLE_PAD
+
+
+def shuffle_unit_pack(w1, s1, t1, wdw, s2, t2, w2, s3, t3):
+    """The parameter image tlxmi_shuffle_unit reads (include/tlxmi.h), as one uint8 tensor on the operands' device: with Kp = h rounded
+    up to 32, fp16 w1[Kp][Kp], fp16 w2[Kp][Kp], fp16 wdw[9][Kp] (tap r * 3 + s), fp32 s1, t1, s2, t2, s3, t3 [Kp] each, everything
+    beyond h zero.  w1, w2: (h, h, 1, 1) or (h, h) filters (out, in); wdw: (h, 1, 3, 3); the scales / shifts: fp32 [h] (folded BatchNorms)."""
+    h = int(w1.shape[0])
+    kp = (h + 31) // 32 * 32
+    dev = w1.device
+    img = []
+    for w in (w1, w2):
+        m = torch.zeros((kp, kp), dtype=torch.float16, device=dev)
+        m[:h, :h] = w.detach().reshape(h, h).to(torch.float16)
+        img.append(m)
+    d = torch.zeros((9, kp), dtype=torch.float16, device=dev)
+    d[:, :h] = wdw.detach().reshape(h, 9).t().to(torch.float16)
+    img.append(d)
+    aff = torch.zeros((6, kp), dtype=torch.float32, device=dev)
+    for i, v in enumerate((s1, t1, s2, t2, s3, t3)):
+        aff[i, :h] = v.detach().to(torch.float32)
+    img.append(aff)
+    return torch.cat([m.contiguous().view(torch.uint8).reshape(-1) for m in img])
+
+
+class ShuffleUnitParams:
+    """One stride-1 InvertedResidual's weights in the forms both arms of shuffle_unit() read: the packed 1x1 filters and the [3][3][hp]
+    depthwise filter of the layer-by-layer arm (hp = h rounded up to the dtype's 16-byte chunk, zero filled, as its folded BatchNorm),
+    and — fp16, h within the fused kernel — the one-buffer image of tlxmi_shuffle_unit (shuffle_unit_pack)."""
+
+    def __init__(self, w1, bn1, wdw, bn2, w2, bn3, dtype):
+        self.h = h = int(w1.shape[0])
+        self.dtype = dtype
+        v = vec(dtype)
+        self.hp = hp = (h + v - 1) // v * v
+        (self.s1, self.t1), (s2, t2), (self.s3, self.t3) = ((_f32(a), _f32(b)) for a, b in (bn1, bn2, bn3))
+        self.pk1, self.pk2 = PackedFilter(w1, dtype), PackedFilter(w2, dtype)
+        dev = self.s1.device
+        self.wdw = torch.zeros((3, 3, hp), dtype=dtype, device=dev)
+        self.wdw[..., :h] = wdw.detach()[:, 0].permute(1, 2, 0).to(dtype)
+        self.s2, self.t2 = torch.zeros(hp, dtype=torch.float32, device=dev), torch.zeros(hp, dtype=torch.float32, device=dev)
+        self.s2[:h], self.t2[:h] = s2, t2
+        self.blob = None
+        if dtype == torch.float16 and _lib.load().tlxmi_shuffle_unit_param_bytes(h):
+            self.blob = shuffle_unit_pack(w1, self.s1, self.t1, wdw, s2, t2, w2, self.s3, self.t3)
+            assert self.blob.numel() == _lib.load().tlxmi_shuffle_unit_param_bytes(h)
+
+
+def _shuffle_unit_desc(x, c, y_ld, act):
+    N, H, W, ld = x.shape
+    return _lib.ShuffleUnitDesc(dtype=dt_code(x.dtype), N=N, H=H, W=W, C=c, x_ld=ld, y_ld=y_ld, act=act)
+
+
+# What the fused launch keeps by default is what the library takes (h <= 128): tools/shufflenet_bench.py times each stage shape of x0_5 / x1_0
+# against the layer-by-layer arm on one MI355X at batch 256 (profiles/shufflenet/shufflenet_bench_b256.txt, DESIGN 4.26), and the fused launch
+# won at all five shapes it takes (0.34 - 0.45 of the four launches): there is no routing constant.
+def shuffle_unit_supported(x, c=None, act=ACT_RELU, y_ld=None):
+    """Whether shuffle_unit() runs tlxmi_shuffle_unit on this NHWC map by default: the "shuffle_unit" option on, fp16 and the
+    library takes the shape (h = c / 2 <= 128)."""
+    c = x.shape[-1] if c is None else int(c)
+    y_ld = shuffle_pitch(c) if y_ld is None else int(y_ld)
+    return bool(_options["shuffle_unit"] and x.dtype == torch.float16 and x.is_contiguous()
+                and _lib.load().tlxmi_shuffle_unit_supported(C.byref(_shuffle_unit_desc(x, c, y_ld, act))))
+
+
+def shuffle_concat(a, b, out=None, out_ld=None, cols=None):
+    """concat + channel_shuffle(2) of two maps (shufflenetv2.py:75-76): y[..., 2i] = a[..., i], y[..., 2i + 1] = b[..., i] for i < cols
+    (default: a's last axis; a and b may be pitched wider) -> y (..., shuffle_pitch(2 cols)) with the columns behind 2 cols zero, or
+    written into `out` (pixel pitch out_ld)."""
+    need_gpu(a, "input")
+    need_gpu(b, "input")
+    h = a.shape[-1] if cols is None else int(cols)
+    rows = a.numel() // a.shape[-1]
+    if a.dtype != b.dtype or not a.is_contiguous() or not b.is_contiguous() or b.numel() // b.shape[-1] != rows or a.shape[-1] < h or b.shape[-1] < h:
+        raise RuntimeError(f"shuffle_concat: two dense maps of one dtype with the same pixels and at least {h} channels are expected, got "
+                           f"{tuple(a.shape)} {a.dtype} / {tuple(b.shape)} {b.dtype}")
+    if out is None:
+        out_ld = shuffle_pitch(2 * h)
+        out = torch.empty(tuple(a.shape[:-1]) + (out_ld,), dtype=a.dtype, device=a.device)
+    elif out_ld is None:
+        out_ld = out.shape[-1]
+    if out.dtype != a.dtype or out_ld < 2 * h:
+        raise RuntimeError("shuffle_concat: out must have the operands' dtype and a pitch of at least twice their channels")
+    es = a.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(a.numel() * es, b.numel() * es, rows * out_ld * es)
+    _lib.call("tlxmi_shuffle_concat", _p(a), _p(b), _p(out), dt_code(a.dtype), rows, h, a.shape[-1], b.shape[-1], out_ld, _stream())
+    return out
+
+
+def shuffle_unit(x, params, act, fused=None, out=None):
+    """ShuffleNetV2's stride-1 InvertedResidual (shufflenetv2.py:69-76) on an NHWC map x (N, H, W, x_ld) whose first c = 2 h channels are
+    the input (h = params.h): the second half runs 1x1 + BN + act -> depthwise 3x3 + BN -> 1x1 + BN + act, the maps between them rounded
+    to the activation dtype, and is interleaved with the untouched first half -> y (N, H, W, shuffle_pitch(c)), the columns behind c zero,
+    or written into `out` (its last axis is the pitch).  params: ShuffleUnitParams.  One launch (tlxmi_shuffle_unit, the hidden maps in
+    LDS) when the "shuffle_unit" option is on, the precision is fp16 and the library takes the shape (h <= 128); otherwise tlxmi_conv2d ->
+    tlxmi_dwconv2d -> tlxmi_conv2d -> tlxmi_shuffle_concat (fp32 always: the parity reference), the branch half copied out first where
+    it does not start on a 16-byte boundary.  fused=True / False forces one form (tests, tools/); True raises where the launch is not
+    supported."""
+    global _probe
+    need_gpu(x, "input")
+    N, H, W, ld = x.shape
+    h = params.h
+    c = 2 * h
+    if x.dtype != params.dtype or ld < c or not x.is_contiguous():
+        raise RuntimeError(f"shuffle_unit: x must be a dense NHWC map of the parameters' dtype with at least {c} channels, got {tuple(x.shape)} {x.dtype}")
+    if out is None:
+        out = torch.empty((N, H, W, shuffle_pitch(c)), dtype=x.dtype, device=x.device)
+    y_ld = out.shape[-1]
+    if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, H, W) or y_ld < c or not out.is_contiguous():
+        raise RuntimeError("shuffle_unit: out must be a dense map of x's dtype and pixels with at least c channels")
+    desc = _shuffle_unit_desc(x, c, y_ld, act)
+    takes = bool(x.dtype == torch.float16 and params.blob is not None and _lib.load().tlxmi_shuffle_unit_supported(C.byref(desc)))
+    if fused is None:
+        fused = takes and _options["shuffle_unit"]
+    elif fused and not takes:
+        raise RuntimeError(f"shuffle_unit: tlxmi_shuffle_unit does not take {tuple(x.shape)} {x.dtype} with h = {h}, act {act}, y_ld {y_ld}")
+    es = x.element_size()
+    M = N * H * W
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * es, M * y_ld * es)
+
+    def launch():
+        if fused:
+            _lib.call("tlxmi_shuffle_unit", C.byref(desc), _p(x), _p(params.blob), _p(out), _stream())
+            return
+        v, hp = vec(x.dtype), params.hp
+        if h % v == 0 and ld % v == 0:
+            t = _conv2d(x[..., h:c], params.pk1, 1, 0, 1, params.s1, params.t1, act=act, x_ld=ld)
+        else:       # the branch half starts inside a 16-byte chunk: a dense copy, zero filled up to the filter's padded width
+            xb = torch.zeros((N, H, W, hp), dtype=x.dtype, device=x.device)
+            xb[..., :h] = x[..., h:c]
+            t = torch.zeros((N, H, W, hp), dtype=x.dtype, device=x.device)      # (its pad columns feed the depthwise: zeros)
+            _conv2d(xb, params.pk1, 1, 0, 1, params.s1, params.t1, act=act, out=t, out_ld=hp)
+        t = dwconv2d(t, params.wdw, 1, 1, 1, params.s2, params.t2)
+        f = torch.empty((N, H, W, hp), dtype=x.dtype, device=x.device)
+        _conv2d(t, params.pk2, 1, 0, 1, params.s3, params.t3, act=act, out=f, out_ld=hp)
+        shuffle_concat(x, f, out, y_ld, cols=h)
+    if _probe is None:
+        launch()
+        return out
+    probe, _probe = _probe, None      # the chain is one entry
+    try:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+    finally:
+        _probe = probe
+    probe.append((e0, e1, (2 * M * c + 2 * h * h + 9 * h) * es, 2 * M * h * (2 * h + 9), (N, H, W, c, c, "shuffle_unit" if fused else "conv-dw-conv-shuffle")))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

@@ -32,5 +32,8 @@ from .levit import (LeViT, levit_128s, levit_128, levit_192, levit_256, levit_38
 # (the TNT file's Block / Attention / Mlp stay in their module: ConvNeXt's Block owns that name here, and the other two follow PVTv2's rule)
 from .tnt import TNT, PixelEmbed, tnt_small  # noqa: F401
 # (the Twins file's Attention / Block / PatchEmbed stay in their module: PVTv2's, ConvNeXt's and ViT's own those names in theirs)
+from .shufflenetv2 import (ShuffleNetV2, InvertedResidual, InvertedResidualDS, create_activation_layer, channel_shuffle,  # noqa: F401
+                           shufflenet_v2_x0_25, shufflenet_v2_x0_33, shufflenet_v2_x0_5, shufflenet_v2_x1_0, shufflenet_v2_x1_5,
+                           shufflenet_v2_x2_0, shufflenet_v2_swish)
 from .gvt import (GroupAttention, SBlock, GroupBlock, PyramidVisionTransformer, PosCNN, CPVTV2, PCPVT, ALTGVT, pcpvt_small,  # noqa: F401
                   pcpvt_base, pcpvt_large, alt_gvt_small, alt_gvt_base, alt_gvt_large)

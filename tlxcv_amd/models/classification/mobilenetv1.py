@@ -9,7 +9,7 @@ from ...tlx.nn import as_nhwc, from_nhwc
 
 __all__ = ["MobileNetV1"]
 
-_ACT_CODE = {nn.ReLU: E.ACT_RELU, nn.ReLU6: E.ACT_RELU6, nn.Hardswish: E.ACT_HARDSWISH, nn.Sigmoid: E.ACT_SIGMOID}
+_ACT_CODE = {nn.ReLU: E.ACT_RELU, nn.ReLU6: E.ACT_RELU6, nn.Hardswish: E.ACT_HARDSWISH, nn.Sigmoid: E.ACT_SIGMOID, nn.Swish: E.ACT_SILU}
 
 
 class ConvNormActivation(nn.Sequential):

@@ -387,6 +387,10 @@ class Sigmoid(_Act):
     ACT = E.ACT_SIGMOID
 
 
+class Swish(_Act):  # shufflenetv2.py:33: x * sigmoid(x)
+    ACT = E.ACT_SILU
+
+
 class GELU(_Act):  # tlx.ops.GeLU, vision_transformer.py:70 — exact erf form [TLX-recalled]
     ACT = E.ACT_GELU
 
