@@ -531,6 +531,37 @@ int tlxmi_shuffle_concat(const void* a, const void* b, void* y, int dtype, int64
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GhostNet's Ghost module (classification/ghostnet.py:74-94) in one launch: primary_conv (1 x 1, Cin -> m, BN, act) ->
+ * cheap_operation (depthwise 3 x 3 on that map, BN, act) -> concat([primary, cheap]), + the bottleneck's shortcut (:140).
+ *     a1 = act( sum_k x[p][k] W1[n][k] * s1[n] + t1[n] )                n < m, fp32 accumulation on MFMA
+ *     p1 = fp16(a1)                                                     what the depthwise reads
+ *     a2 = act( dw3x3(p1)[n] * s2[n] + t2[n] )                          pad 1, stride 1, taps in (r, s) order as tlxmi_dwconv2d, fp32
+ *     y[p][n] = fp16( a1 (+ res[p][n]) ),    y[p][m + n] = fp16( a2 (+ res[p][m + n]) )
+ * Two roundings: p1 (where two launches store fp16) and the output; the shortcut is added to the fp32 value, so with res the first
+ * half is fp16(a1 + res), not fp16(p1 + res).  p1 at a position OUTSIDE the image is zero (the depthwise's padding), not act(t1).
+ * x: N*H*W pixels of pitch x_ld, Cin channels read (whatever the columns behind them hold reaches no output); res: null, or the same
+ * pixels at pitch res_ld, 2 m channels read; it may alias x.  y has pitch y_ld; the columns [2 m, min(y_ld, roundup(2 m, 8))) are
+ * written as zeros (later convs read a padded map through zero filter columns), the columns behind them are left untouched.  y
+ * aliases no input.  One writer per element, fixed summation order, no atomics.
+ * params: tlxmi_ghost_module_param_bytes(Cin, m) bytes, Kp = Cin rounded up to 32, mp = m rounded up to 16, everything beyond Cin / m zero:
+ *     fp16 w1[mp][Kp] (row = output channel), fp16 wdw[9][mp] (tap r * 3 + s), fp32 s1, t1, s2, t2 [mp] each.
+ * tlxmi_ghost_module_supported() is pure host code and answers 1 exactly for: fp16; N, H, W >= 1; 4 <= Cin <= 1248; m even,
+ * 4 <= m <= 624; x_ld >= Cin; y_ld >= 2 m and even; res_ld 0 (no shortcut) or >= 2 m and even; act none or ReLU;
+ * (pixels * ld + 2048) * 2 below 2^31 for the three pitches (32-bit byte offsets).  1 means the call is taken, given x, params, res
+ * and y 16-byte aligned (TLXMI_ERR_ALIGNMENT otherwise) and res given exactly when res_ld != 0 (TLXMI_ERR_BAD_ARG); anything else
+ * returns TLXMI_ERR_UNSUPPORTED (run tlxmi_conv2d, tlxmi_dwconv2d and tlxmi_affine_act instead).  param_bytes is 0 outside the ranges.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_ghost_module_desc {
+    int32_t dtype;
+    int32_t N, H, W, Cin, m;
+    int32_t x_ld, y_ld, res_ld;
+    int32_t act;
+} tlxmi_ghost_module_desc;
+int tlxmi_ghost_module_supported(const tlxmi_ghost_module_desc* d);
+size_t tlxmi_ghost_module_param_bytes(int Cin, int m);
+int tlxmi_ghost_module(const tlxmi_ghost_module_desc* d, const void* x, const void* params, const void* res, void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

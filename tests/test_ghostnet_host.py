@@ -1,0 +1,187 @@
+"""CPU-side tests of GhostNet: the three factories build with the reference's per-block widths (_make_divisible), the parameter tree is the
+fixtures' (and the reference model file's where the reference tree is present), the plain-torch restatement reproduces the fixtures' logits
+from the seeded weights, the parameter image of tlxmi_ghost_module equals a numpy statement of it, the library's predicate answers for the
+shapes the header promises, and clip(v, 0, 1) = hardsigmoid(6 v - 3), the fold the SE block runs on."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, REPO
+
+FIXTURES = [("ghostnet_x1_0_b2.npz", "ghostnet_x1_0", 1.0), ("ghostnet_x0_5_c10_96x160_b1.npz", "ghostnet_x0_5", 0.5),
+            ("ghostnet_x1_3_c10_96x160_b1.npz", "ghostnet_x1_3", 1.3)]
+# (stem, [(in, hidden, out)] of the 16 bottlenecks, conv_last) worked out by hand from ghostnet.py:147-163 and _make_divisible(., 4)
+WIDTHS = {
+    "ghostnet_x0_5": (8, [(8, 8, 8), (8, 24, 12), (12, 36, 12), (12, 36, 20), (20, 60, 20), (20, 120, 40), (40, 100, 40), (40, 92, 40), (40, 92, 40),
+                          (40, 240, 56), (56, 336, 56), (56, 336, 80), (80, 480, 80), (80, 480, 80), (80, 480, 80), (80, 480, 80)], 480),
+    "ghostnet_x1_0": (16, [(16, 16, 16), (16, 48, 24), (24, 72, 24), (24, 72, 40), (40, 120, 40), (40, 240, 80), (80, 200, 80), (80, 184, 80),
+                           (80, 184, 80), (80, 480, 112), (112, 672, 112), (112, 672, 160), (160, 960, 160), (160, 960, 160), (160, 960, 160),
+                           (160, 960, 160)], 960),
+    "ghostnet_x1_3": (20, [(20, 20, 20), (20, 64, 32), (32, 92, 32), (32, 92, 52), (52, 156, 52), (52, 312, 104), (104, 260, 104), (104, 240, 104),
+                           (104, 240, 104), (104, 624, 144), (144, 872, 144), (144, 872, 208), (208, 1248, 208), (208, 1248, 208), (208, 1248, 208),
+                           (208, 1248, 208)], 1248)}
+SCALE = {"ghostnet_x0_5": 0.5, "ghostnet_x1_0": 1.0, "ghostnet_x1_3": 1.3}
+
+
+@pytest.mark.parametrize("name", sorted(WIDTHS))
+def test_factories_and_block_widths(name):
+    import ghostnet_restated as RS
+    from tlxcv_amd import models
+    m = getattr(models, name)(class_num=10)
+    stem, blocks, last = WIDTHS[name]
+    assert isinstance(m, models.GhostNet) and len(m.ghost_bottleneck_list) == 16 and m.scale == SCALE[name]
+    assert RS.widths(SCALE[name]) == (stem, [(i, h, o, k, se, s) for (i, h, o), (k, _, _, se, s) in zip(blocks, RS.CFGS)], last)
+    assert tuple(m.conv1._conv.filters.shape) == (stem, 3, 3, 3) and m.conv1._conv.stride == (2, 2)
+    for idx, ((cin, hid, out), (k, _, _, se, s)) in enumerate(zip(blocks, RS.CFGS)):
+        b = getattr(m, f"_ghostbottleneck_{idx}")
+        assert b is m.ghost_bottleneck_list[idx]
+        g1, g2 = b.ghost_module_1, b.ghost_module_2
+        assert tuple(g1.primary_conv._conv.filters.shape) == (hid // 2, cin, 1, 1) and tuple(g1.cheap_operation._conv.filters.shape) == (hid // 2, 1, 3, 3)
+        assert tuple(g2.primary_conv._conv.filters.shape) == (out // 2, hid, 1, 1) and tuple(g2.cheap_operation._conv.filters.shape) == (out // 2, 1, 3, 3)
+        assert g1.primary_conv.batch_norm.act is not None and g2.primary_conv.batch_norm.act is None and g2.cheap_operation.batch_norm.act is None
+        assert hasattr(b, "depthwise_conv") == (s == 2) and hasattr(b, "se_block") == bool(se)
+        if s == 2:
+            assert tuple(b.depthwise_conv._conv.filters.shape) == (hid, 1, k, k) and b.depthwise_conv._conv.stride == (2, 2)
+        if se:
+            assert tuple(b.se_block.squeeze.weights.shape) == (hid, hid // 4) and tuple(b.se_block.excitation.weights.shape) == (hid // 4, hid)
+        assert hasattr(b, "shortcut_conv") == (s != 1 or cin != out)
+        if hasattr(b, "shortcut_conv"):
+            assert tuple(b.shortcut_depthwise._conv.filters.shape) == (cin, 1, k, k) and tuple(b.shortcut_conv._conv.filters.shape) == (out, cin, 1, 1)
+    assert tuple(m.conv_last._conv.filters.shape) == (last, blocks[-1][2], 1, 1)
+    assert tuple(m.fc_0._conv.filters.shape) == (1280, last, 1, 1) and tuple(m.fc_1.weights.shape) == (1280, 10)
+
+
+def test_constructor_arguments_and_refusals():
+    import tlxcv_amd
+    from tlxcv_amd.models import GhostNet, ghostnet_x1_0
+    tlxcv_amd.install()
+    from tlxcv.models import ghostnet_x1_0 as aliased
+    assert aliased is ghostnet_x1_0
+    m = GhostNet(scale=1.0)
+    assert m.class_num == 1000 and tuple(m.fc_1.weights.shape) == (1280, 1000)
+    with pytest.raises(NotImplementedError, match="pretrained"):
+        ghostnet_x1_0(pretrained=True)
+    with pytest.raises(NotImplementedError, match="set_eval"):
+        m(torch.zeros(1, 3, 32, 32))                               # train mode: refused like the other models
+
+
+@pytest.mark.parametrize("fname,arch,scale", FIXTURES)
+def test_parameter_tree_matches_fixture(fname, arch, scale):
+    from tlxcv_amd import models, seeded
+    g = np.load(os.path.join(GOLDEN, fname))
+    assert str(g["arch"]) == arch
+    m = getattr(models, arch)(class_num=int(g["num_classes"]))
+    shapes = seeded.shapes_of(m)
+    assert list(shapes.keys()) == list(g["param_names"]) and len(shapes) == 435
+    names = list(shapes)
+    assert names[:2] == ["conv1._conv.filters", "conv1.batch_norm.gamma"] and names[-2:] == ["fc_1.weights", "fc_1.biases"]
+    assert "_ghostbottleneck_3.ghost_module_1.primary_conv._conv.filters" in shapes and "_ghostbottleneck_15.se_block.excitation.biases" in shapes
+    assert "conv_last.batch_norm.moving_var" in shapes and "fc_0._conv.filters" in shapes
+    if arch == "ghostnet_x1_0":
+        assert sum(int(np.prod(s)) for s in shapes.values()) == 5207544
+
+
+def test_parameter_tree_matches_reference_model_file():
+    from oracle.gen_golden import REF
+    if not os.path.isfile(os.path.join(REF, "tlxcv", "models", "classification", "ghostnet.py")):
+        pytest.skip("reference tree not present")
+    code = ("import sys; sys.path.insert(0, 'tools'); import gen_ghostnet_golden as G; from tlxcv_amd import seeded; "
+            "ref, _ = G.reference_module(); "
+            "print('\\n'.join(f'{k} {v}' for k, v in seeded.shapes_of(ref.ghostnet_x1_3(class_num=7)).items()))")
+    out = subprocess.check_output([sys.executable, "-c", code], cwd=REPO, text=True)
+    from tlxcv_amd import seeded
+    from tlxcv_amd.models import ghostnet_x1_3
+    mine = [f"{k} {tuple(v)}" for k, v in seeded.shapes_of(ghostnet_x1_3(class_num=7)).items()]
+    assert out.strip().splitlines() == mine
+
+
+@pytest.mark.parametrize("fname,arch,scale", FIXTURES)
+def test_fp32_restatement_reproduces_the_fixture(fname, arch, scale):
+    """float32 restatement on seeded.fill weights against the logits the reference file gave in float64: 1e-4 of the logit range, same
+    argmax; and the margin rule that keeps the GPU test's fp16 argmax check from being vacuous."""
+    import ghostnet_restated as RS
+    from tlxcv_amd import models, seeded
+    g = np.load(os.path.join(GOLDEN, fname))
+    params = seeded.fill(seeded.shapes_of(getattr(models, arch)(class_num=int(g["num_classes"]))), int(g["weight_seed"]))
+    x = torch.from_numpy(RS.ghostnet_input(int(g["batch"]), int(g["input_seed"]), *[int(v) for v in g["hw"]]))
+    with torch.no_grad():
+        y = RS.ghostnet({k: torch.from_numpy(v) for k, v in params.items()}, x, scale).numpy()
+    lg = g["logits"]
+    rng_ = float(lg.max() - lg.min())
+    assert y.shape == lg.shape and np.abs(y - lg).max() <= 1e-4 * rng_ and (y.argmax(-1) == g["argmax"]).all()
+    s = np.sort(lg, axis=1)
+    assert ((s[:, -1] - s[:, -2]) > 2 * 0.003 * rng_).all()
+    assert float(g["restatement_max_abs_diff"]) <= 1e-5
+
+
+def test_parameter_image_matches_numpy():
+    """engine.ghost_module_pack on a seeded module's weights and BatchNorm folds (scale = gamma / sqrt(var + eps), shift = beta - mean scale)
+    against numpy: fp16 w1[mp][Kp], fp16 taps[9][mp], fp32 s1, t1, s2, t2 [mp], Kp = roundup(Cin, 32), mp = roundup(m, 16), zero padded."""
+    from tlxcv_amd import _lib, engine as E, seeded
+    from tlxcv_amd.models.classification.ghostnet import GhostModule
+    cin, m = 40, 46                                                # x0_5's ghost_module_1 of blocks 7 / 8: neither width a multiple of 8
+    u = GhostModule(cin, 2 * m)
+    p = seeded.fill(seeded.shapes_of(u), 9)
+    kp, mp = 64, 48
+
+    def fold(pre):
+        s = p[pre + "gamma"] / np.sqrt(p[pre + "moving_var"].astype(np.float64) + 1e-5)
+        return s, p[pre + "beta"] - p[pre + "moving_mean"] * s
+    (s1, t1), (s2, t2) = fold("primary_conv.batch_norm."), fold("cheap_operation.batch_norm.")
+    f32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32))
+    blob = E.ghost_module_pack(torch.from_numpy(p["primary_conv._conv.filters"]), f32(s1), f32(t1),
+                               torch.from_numpy(p["cheap_operation._conv.filters"]), f32(s2), f32(t2)).numpy()
+    assert blob.nbytes == _lib.load().tlxmi_ghost_module_param_bytes(cin, m) == mp * kp * 2 + 9 * mp * 2 + 4 * mp * 4
+    img = np.zeros((mp, kp), np.float16)
+    img[:m, :cin] = p["primary_conv._conv.filters"].reshape(m, cin).astype(np.float16)
+    o = img.nbytes
+    assert np.array_equal(blob[:o].view(np.float16).reshape(mp, kp), img)
+    taps = np.zeros((9, mp), np.float16)
+    taps[:, :m] = p["cheap_operation._conv.filters"].reshape(m, 9).T.astype(np.float16)
+    assert np.array_equal(blob[o:o + taps.nbytes].view(np.float16).reshape(9, mp), taps)
+    aff = blob[o + taps.nbytes:].view(np.float32).reshape(4, mp)
+    for i, v in enumerate((s1, t1, s2, t2)):
+        assert np.array_equal(aff[i, :m], np.asarray(v, dtype=np.float32)) and not aff[i, m:].any()
+
+
+def test_predicate_answers_what_the_header_promises():
+    from tlxcv_amd import _lib, engine as E
+    lib = _lib.load()
+
+    def ok(**kw):
+        d = dict(dtype=E.dt_code(torch.float16), N=2, H=7, W=9, Cin=40, m=24, x_ld=40, y_ld=48, res_ld=0, act=_lib.ACT_RELU)
+        d.update(kw)
+        return bool(lib.tlxmi_ghost_module_supported(ctypes.byref(_lib.GhostModuleDesc(**d))))
+    assert ok() and ok(act=_lib.ACT_NONE) and ok(res_ld=48) and ok(res_ld=50, y_ld=1000) and ok(N=1, H=1, W=1)
+    for m in (4, 6, 10, 12, 18, 36, 46, 92, 100, 130, 436, 624):   # every even m of the range: the widths of the three variants and the ends
+        assert ok(m=m, y_ld=2 * m) and lib.tlxmi_ghost_module_param_bytes(40, m) > 0
+    for cin in (4, 5, 8, 12, 20, 100, 184, 872, 1248):
+        assert ok(Cin=cin, x_ld=cin) and ok(Cin=cin, x_ld=cin + 3) and lib.tlxmi_ghost_module_param_bytes(cin, 24) > 0
+    assert not ok(m=23) and not ok(m=2) and not ok(m=626, y_ld=1252)                 # odd, below and above the range
+    assert not ok(Cin=3, x_ld=8) and not ok(Cin=1249, x_ld=1256)
+    assert not ok(x_ld=39) and not ok(y_ld=46) and not ok(y_ld=49) and not ok(res_ld=46) and not ok(res_ld=49)
+    assert not ok(dtype=E.dt_code(torch.float32)) and not ok(act=_lib.ACT_SILU) and not ok(act=_lib.ACT_RELU6) and not ok(N=0) and not ok(H=0)
+    assert lib.tlxmi_ghost_module_param_bytes(40, 23) == 0 and lib.tlxmi_ghost_module_param_bytes(1249, 24) == 0
+    # 32-bit byte offsets: (pixels * ld + 2048) * 2 < 2^31 for every pitch
+    assert ok(N=1, H=1024, W=1024, Cin=1000, x_ld=1000, m=4, y_ld=8)                  # 2.0e9 bytes of x
+    assert not ok(N=1, H=1024, W=1024, Cin=1024, x_ld=1024, m=4, y_ld=8)              # 2^31 bytes of x
+    assert not ok(N=1, H=1024, W=1024, Cin=8, x_ld=8, m=512, y_ld=1024)               # 2^31 bytes of y
+    assert not ok(N=1, H=1024, W=1024, Cin=8, x_ld=8, m=4, y_ld=8, res_ld=1024)
+
+
+def test_clip_is_hardsigmoid_of_6v_minus_3():
+    """SEBlock's clip(v, 0, 1) (ghostnet.py:67) runs as ACT_HARDSIGMOID (min(max(u + 3, 0), 6) / 6) of u = 6 v - 3: on a grid that crosses 0
+    and 1, in float64 exactly to rounding and in float32 within a few ulp of 1."""
+    v = torch.arange(-2048, 3073, dtype=torch.float64) / 1024.0     # exact: 0 and 1 are on the grid
+    assert (v < 0).any() and ((v > 0) & (v < 1)).any() and (v > 1).any() and (v == 0).any() and (v == 1).any()
+    hs = lambda u: torch.clamp(u + 3.0, 0.0, 6.0) / 6.0
+    assert (hs(6.0 * v - 3.0) - v.clamp(0, 1)).abs().max().item() <= 4 * 2.0 ** -53
+    v32 = v.float()
+    got = torch.clamp((6.0 * v32 - 3.0) + 3.0, 0.0, 6.0) * (1.0 / 6.0)
+    assert (got.double() - v32.double().clamp(0, 1)).abs().max().item() <= 8 * 2.0 ** -24
+    assert (got[v32 <= 0] == 0).all() and (got[v32 >= 1.0001] >= 1 - 2.0 ** -23).all()

@@ -52,6 +52,10 @@ class ShuffleUnitDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "C", "x_ld", "y_ld", "act")]
 
 
+class GhostModuleDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "Cin", "m", "x_ld", "y_ld", "res_ld", "act")]
+
+
 class LkaGateDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in ("C", "a1_ld", "t_ld", "res_ld", "y_ld")]
 
@@ -178,6 +182,7 @@ PROTOTYPES = {
     "tlxmi_mul": [_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp],
     "tlxmi_shuffle_unit": [C.POINTER(ShuffleUnitDesc), _vp, _vp, _vp, _vp],
     "tlxmi_shuffle_concat": [_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp],
+    "tlxmi_ghost_module": [C.POINTER(GhostModuleDesc), _vp, _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -210,6 +215,8 @@ _SPECIAL = {
     "tlxmi_lka_gate_supported": ([C.POINTER(LkaGateDesc)], C.c_int),
     "tlxmi_shuffle_unit_supported": ([C.POINTER(ShuffleUnitDesc)], C.c_int),
     "tlxmi_shuffle_unit_param_bytes": ([_i], C.c_size_t),
+    "tlxmi_ghost_module_supported": ([C.POINTER(GhostModuleDesc)], C.c_int),
+    "tlxmi_ghost_module_param_bytes": ([_i, _i], C.c_size_t),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

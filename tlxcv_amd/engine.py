@@ -81,6 +81,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # -> concat -> channel_shuffle on tlxmi_shuffle_unit: ONE launch, both hidden maps in LDS, both products on MFMA,
                                   # the pixel read once and written once with the shuffle in the store; elsewhere and off = tlxmi_conv2d ->
                                   # tlxmi_dwconv2d -> tlxmi_conv2d -> tlxmi_shuffle_concat (the A/B and the tests' other arm)
+            "ghost_module": True, # GhostNet's Ghost modules (fp16; the shapes the measured table keeps: maps up to 56 x 56, m <= 100, Cin * m <= 19200): 1x1 + BN + act -> depthwise 3x3 + BN + act -> concat
+                                  # (+ the bottleneck's shortcut) on tlxmi_ghost_module: ONE launch, the primary map of a pixel tile in LDS, the
+                                  # 1x1 on MFMA, both halves stored from the launch; off = tlxmi_conv2d -> tlxmi_dwconv2d (-> tlxmi_affine_act
+                                  # for the shortcut) (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1107,7 +1111,10 @@ def linear_ln(x, prep, part, eps, act=ACT_NONE, out=None):
     return y
 
 
-def dwconv2d(x, w_rsc, stride=1, padding=0, dilation=1, scale=None, shift=None, act=ACT_NONE, act_param=0.0, out_hw=None):
+def dwconv2d(x, w_rsc, stride=1, padding=0, dilation=1, scale=None, shift=None, act=ACT_NONE, act_param=0.0, out_hw=None,
+             x_ld=None, out=None, out_ld=None):
+    """x_ld: the pixel pitch when x is a 16-byte aligned column slice of a wider map (a view: the filter's channels are read);
+    out / out_ld: write into a 16-byte aligned column slice of a wider buffer (pixel pitch out_ld, default out's last axis)."""
     need_gpu(x, "input")
     N, H, W, Cc = x.shape
     R, S, Cw = w_rsc.shape
@@ -1118,9 +1125,10 @@ def dwconv2d(x, w_rsc, stride=1, padding=0, dilation=1, scale=None, shift=None, 
     Wo = (W + 2 * pw - dw * (S - 1) - 1) // sw + 1
     if out_hw is not None:      # one-sided end padding ('SAME' at stride 2): the last windows read zeros past the edge
         Ho, Wo = int(out_hw[0]), int(out_hw[1])
-    y = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
+    y = out if out is not None else torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
+    y_ld = Cc if out is None else int(out_ld if out_ld is not None else out.shape[-1])
     d = _lib.DwConvDesc(dtype=dt_code(x.dtype), N=N, H=H, W=W, C=Cw, R=R, S=S, stride_h=sh, stride_w=sw, pad_h=ph,
-                        pad_w=pw, dil_h=dh, dil_w=dw, Ho=Ho, Wo=Wo, x_ld=Cc, y_ld=Cc, act=act,
+                        pad_w=pw, dil_h=dh, dil_w=dw, Ho=Ho, Wo=Wo, x_ld=Cc if x_ld is None else int(x_ld), y_ld=y_ld, act=act,
                         act_param=float(act_param))
     _lib.call("tlxmi_dwconv2d", C.byref(d), _p(x), _p(w_rsc), _p(scale), _p(shift), _p(y), _stream())
     return y
@@ -1567,6 +1575,164 @@ def shuffle_unit(x, params, act, fused=None, out=None):
     finally:
         _probe = probe
     probe.append((e0, e1, (2 * M * c + 2 * h * h + 9 * h) * es, 2 * M * h * (2 * h + 9), (N, H, W, c, c, "shuffle_unit" if fused else "conv-dw-conv-shuffle")))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# GhostNet's Ghost module
+# ---------------------------------------------------------------------------------------------
+def ghost_module_pack(w1, s1, t1, wdw, s2, t2):
+    """The parameter image tlxmi_ghost_module reads (include/tlxmi.h), as one uint8 tensor on the operands' device: with Kp = Cin
+    rounded up to 32 and mp = m rounded up to 16, fp16 w1[mp][Kp], fp16 wdw[9][mp] (tap r * 3 + s), fp32 s1, t1, s2, t2 [mp] each,
+    everything beyond Cin / m zero.  w1: (m, Cin, 1, 1) or (m, Cin) (out, in); wdw: (m, 1, 3, 3); the scales / shifts: fp32 [m]
+    (folded BatchNorms)."""
+    m, cin = int(w1.shape[0]), int(w1.shape[1])
+    kp, mp = (cin + 31) // 32 * 32, (m + 15) // 16 * 16
+    dev = w1.device
+    f = torch.zeros((mp, kp), dtype=torch.float16, device=dev)
+    f[:m, :cin] = w1.detach().reshape(m, cin).to(torch.float16)
+    d = torch.zeros((9, mp), dtype=torch.float16, device=dev)
+    d[:, :m] = wdw.detach().reshape(m, 9).t().to(torch.float16)
+    aff = torch.zeros((4, mp), dtype=torch.float32, device=dev)
+    for i, v in enumerate((s1, t1, s2, t2)):
+        aff[i, :m] = v.detach().to(torch.float32)
+    return torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in (f, d, aff)])
+
+
+class GhostModuleParams:
+    """One GhostModule's weights in the forms both arms of ghost_module() read: the packed 1x1 filter and the [3][3][mp] depthwise
+    filter of the layer-by-layer arm (mp = m rounded up to the dtype's 16-byte chunk, zero filled, as its folded BatchNorm), and — fp16,
+    widths within the fused kernel — the one-buffer image of tlxmi_ghost_module (ghost_module_pack).  w1: (m, Cin, 1, 1);
+    wdw: (m, 1, 3, 3); bn1, bn2: (scale, shift) of the folded BatchNorms."""
+
+    def __init__(self, w1, bn1, wdw, bn2, dtype):
+        self.m = m = int(w1.shape[0])
+        self.cin = int(w1.shape[1])
+        self.dtype = dtype
+        v = vec(dtype)
+        self.mp = mp = (m + v - 1) // v * v
+        (self.s1, self.t1), (s2, t2) = ((_f32(a), _f32(b)) for a, b in (bn1, bn2))
+        self.pk1 = PackedFilter(w1, dtype)
+        dev = self.s1.device
+        self.wdw = torch.zeros((3, 3, mp), dtype=dtype, device=dev)
+        self.wdw[..., :m] = wdw.detach()[:, 0].permute(1, 2, 0).to(dtype)
+        self.s2, self.t2 = torch.zeros(mp, dtype=torch.float32, device=dev), torch.zeros(mp, dtype=torch.float32, device=dev)
+        self.s2[:m], self.t2[:m] = s2, t2
+        self.blob = None
+        if dtype == torch.float16 and _lib.load().tlxmi_ghost_module_param_bytes(self.cin, m):
+            self.blob = ghost_module_pack(w1, self.s1, self.t1, wdw, s2, t2)
+            assert self.blob.numel() == _lib.load().tlxmi_ghost_module_param_bytes(self.cin, m)
+
+
+def _ghost_module_desc(x, cin, m, y_ld, res_ld, act):
+    N, H, W, ld = x.shape
+    return _lib.GhostModuleDesc(dtype=dt_code(x.dtype), N=N, H=H, W=W, Cin=cin, m=m, x_ld=ld, y_ld=y_ld, res_ld=res_ld, act=act)
+
+
+def ghost_module_takes(x, cin, m, act=ACT_RELU, y_ld=None, res_ld=0):
+    """Whether the library's tlxmi_ghost_module takes this NHWC map (fp16, widths and pitches within the kernel): what fused=True needs."""
+    y_ld = shuffle_pitch(2 * m) if y_ld is None else int(y_ld)
+    return bool(x.dtype == torch.float16 and x.is_contiguous()
+                and _lib.load().tlxmi_ghost_module_supported(C.byref(_ghost_module_desc(x, int(cin), int(m), y_ld, int(res_ld), act))))
+
+
+# Which shapes the fused launch keeps by default.  MEASURED: tools/ghostnet_bench.py times every distinct module shape of ghostnet_x0_5 /
+# ghostnet_x1_0 against the layer-by-layer arm on one MI355X at batch 256 (profiles/ghostnet/ghostnet_bench_b256.txt, DESIGN 4.27).  The
+# fused launch won (0.44 - 0.92 of the layers' time) at every shape with a map of at most 56 x 56, m <= 100 and Cin * m <= 19200, and
+# lost (1.16 - 2.41) at every other one: the 112 x 112 maps (4 - 24 channels on a 16 x 32 MFMA tile), m >= 120 (two or more channel
+# chunks, each recomputing the halo and re-reading x) and Cin >= 480 with m >= 56 (filter rows that leave LDS room for 16 - 48
+# channels a chunk).  The three bounds are the table's, not a model: shapes between its rows (x1_3, other resolutions) are unmeasured.
+GHOST_FUSED_MAX_PIXELS, GHOST_FUSED_MAX_M, GHOST_FUSED_MAX_CIN_M = 56 * 56, 100, 19200
+
+
+def _ghost_module_routed(H, W, cin, m):
+    return H * W <= GHOST_FUSED_MAX_PIXELS and m <= GHOST_FUSED_MAX_M and cin * m <= GHOST_FUSED_MAX_CIN_M
+
+
+def ghost_module_supported(x, cin, m, act=ACT_RELU, y_ld=None, res_ld=0):
+    """Whether ghost_module() runs tlxmi_ghost_module on this NHWC map by default: the "ghost_module" option on, the library takes the
+    shape (ghost_module_takes) and the measured table keeps it (otherwise it runs layer by layer)."""
+    return bool(_options["ghost_module"] and _ghost_module_routed(x.shape[1], x.shape[2], int(cin), int(m))
+                and ghost_module_takes(x, cin, m, act, y_ld, res_ld))
+
+
+def ghost_module(x, params, act, res=None, fused=None, out=None):
+    """GhostNet's GhostModule (ghostnet.py:74-94) on an NHWC map x (N, H, W, x_ld) whose first Cin = params.cin channels are the input:
+    primary = act(1x1 * s1 + t1) (m = params.m channels), cheap = act(dw3x3(primary rounded to the activation dtype) * s2 + t2),
+    y = concat([primary, cheap]) (+ res, the bottleneck's shortcut, ghostnet.py:140; a map of the same pixels with at least 2 m
+    channels, which may be x) -> y (N, H, W, shuffle_pitch(2 m)), the columns behind 2 m zero, or written into `out` (its last axis
+    is the pitch).  params: GhostModuleParams.  One launch (tlxmi_ghost_module, the primary map in LDS) when the "ghost_module"
+    option is on, the precision is fp16, the library takes the shape and the measured table keeps it (ghost_module_supported); otherwise tlxmi_conv2d into out[..., :m] -> tlxmi_dwconv2d
+    from there into out[..., m:] (through a dense copy where m is no whole number of 16-byte chunks) -> tlxmi_affine_act for the
+    shortcut (fp32 always: the parity reference; there the pitches are whole chunks and res has zero pad columns).  fused=True /
+    False forces one form (tests, tools/); True raises where the launch is not supported."""
+    global _probe
+    need_gpu(x, "input")
+    N, H, W, ld = x.shape
+    m, cin = params.m, params.cin
+    c = 2 * m
+    if x.dtype != params.dtype or ld < cin or not x.is_contiguous():
+        raise RuntimeError(f"ghost_module: x must be a dense NHWC map of the parameters' dtype with at least {cin} channels, got {tuple(x.shape)} {x.dtype}")
+    if out is None:
+        out = torch.empty((N, H, W, shuffle_pitch(c)), dtype=x.dtype, device=x.device)
+    y_ld = out.shape[-1]
+    if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, H, W) or y_ld < c or not out.is_contiguous():
+        raise RuntimeError("ghost_module: out must be a dense map of x's dtype and pixels with at least 2 m channels")
+    res_ld = 0
+    if res is not None:
+        res_ld = res.shape[-1]
+        if res.dtype != x.dtype or tuple(res.shape[:3]) != (N, H, W) or res_ld < c or not res.is_contiguous():
+            raise RuntimeError("ghost_module: res must be a dense map of x's dtype and pixels with at least 2 m channels")
+    desc = _ghost_module_desc(x, cin, m, y_ld, res_ld, act)
+    takes = bool(x.dtype == torch.float16 and params.blob is not None and _lib.load().tlxmi_ghost_module_supported(C.byref(desc)))
+    if fused is None:
+        fused = takes and _options["ghost_module"] and _ghost_module_routed(H, W, cin, m)
+    elif fused and not takes:
+        raise RuntimeError(f"ghost_module: tlxmi_ghost_module does not take {tuple(x.shape)} {x.dtype} with Cin = {cin}, m = {m}, act {act}, "
+                           f"y_ld {y_ld}, res_ld {res_ld}")
+    es = x.element_size()
+    M = N * H * W
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * es, M * y_ld * es, M * res_ld * es)
+
+    def launch():
+        if fused:
+            _lib.call("tlxmi_ghost_module", C.byref(desc), _p(x), _p(params.blob), _p(res), _p(out), _stream())
+            return
+        v, mp = vec(x.dtype), params.mp
+        zend = min(y_ld, shuffle_pitch(c))
+        if ld < params.pk1.Cin_pad:
+            raise RuntimeError(f"ghost_module: layer by layer, x needs a pitch of at least {params.pk1.Cin_pad} channels")
+        if m % v == 0 and y_ld % v == 0:
+            _conv2d(x, params.pk1, 1, 0, 1, params.s1, params.t1, act=act, out=out, out_ld=y_ld)
+            dwconv2d(out[..., :m], params.wdw, 1, 1, 1, params.s2, params.t2, act=act, x_ld=y_ld, out=out[..., m:], out_ld=y_ld)
+        else:       # the cheap half starts inside a 16-byte chunk: dense copies, zero filled up to the filter's padded width
+            t = torch.zeros((N, H, W, mp), dtype=x.dtype, device=x.device)
+            _conv2d(x, params.pk1, 1, 0, 1, params.s1, params.t1, act=act, out=t, out_ld=mp)
+            u = dwconv2d(t, params.wdw, 1, 1, 1, params.s2, params.t2, act=act)
+            out[..., :m] = t[..., :m]
+            out[..., m:c] = u[..., :m]
+        if zend > c:
+            out[..., c:zend] = 0
+        if res is not None:
+            cw = (c + v - 1) // v * v
+            if cw > zend or y_ld % v or res_ld % v or res_ld < cw:
+                raise RuntimeError(f"ghost_module: layer by layer, the shortcut needs pitches that are whole 16-byte chunks (y_ld {y_ld}, res_ld {res_ld})")
+            _lib.call("tlxmi_affine_act", _p(out), None, None, _p(res), _p(out), dt_code(x.dtype), M, cw, y_ld, res_ld, y_ld, ACT_NONE, 0.0, 0,
+                      _stream())
+    if _probe is None:
+        launch()
+        return out
+    probe, _probe = _probe, None      # the chain is one entry
+    try:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+    finally:
+        _probe = probe
+    probe.append((e0, e1, (M * (cin + c * (2 if res is not None else 1)) + m * cin + 9 * m) * es, 2 * M * m * (cin + 9),
+                  (N, H, W, cin, c, "ghost_module" if fused else "conv-dw-add")))
     return out
 
 

@@ -35,5 +35,6 @@ from .tnt import TNT, PixelEmbed, tnt_small  # noqa: F401
 from .shufflenetv2 import (ShuffleNetV2, InvertedResidual, InvertedResidualDS, create_activation_layer, channel_shuffle,  # noqa: F401
                            shufflenet_v2_x0_25, shufflenet_v2_x0_33, shufflenet_v2_x0_5, shufflenet_v2_x1_0, shufflenet_v2_x1_5,
                            shufflenet_v2_x2_0, shufflenet_v2_swish)
+from .ghostnet import (GhostNet, GhostBottleneck, GhostModule, SEBlock, ghostnet_x0_5, ghostnet_x1_0, ghostnet_x1_3)  # noqa: F401
 from .gvt import (GroupAttention, SBlock, GroupBlock, PyramidVisionTransformer, PosCNN, CPVTV2, PCPVT, ALTGVT, pcpvt_small,  # noqa: F401
                   pcpvt_base, pcpvt_large, alt_gvt_small, alt_gvt_base, alt_gvt_large)

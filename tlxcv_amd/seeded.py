@@ -15,6 +15,8 @@ import numpy as np
 
 # Twins (gvt.py): blocks.<stage>.<index>.attn.{q, kv, qkv, proj} — the only tree whose blocks carry two indices
 _TWINS_ATTN = re.compile(r"^blocks\.\d+\.\d+\.attn\.(q|kv|qkv|proj)$")
+# GhostNet (ghostnet.py:109-126): the convs of a bottleneck that no ReLU follows
+_GHOST_LINEAR = re.compile(r"^_ghostbottleneck_\d+\.(ghost_module_2\.(primary_conv|cheap_operation)|depthwise_conv|shortcut_depthwise|shortcut_conv)\._conv$")
 
 
 def image_batch(n, seed=0, hw=224, c=3):
@@ -40,6 +42,9 @@ def _is_last_bn_of_block(name):
     # MobileNetV2/V3: the BatchNorm of the linear projection (mobilenetv2.py:30-33, mobilenetv3.py:107-110).
     # ResNeSt: conv3's BatchNorm and the shortcut BatchNorm of a bottleneck (resnest.py:258-309).
     if "_bottleneck_" in name and name.rsplit("_bottleneck_", 1)[1].split(".", 1)[1:] in (["conv3.batch_norm"], ["batch_norm"]):
+        return True
+    # GhostNet: ghost_module_2's primary BatchNorm and the shortcut conv's BatchNorm (ghostnet.py:134-140).
+    if name.endswith(("ghost_module_2.primary_conv.batch_norm", "shortcut_conv.batch_norm")):
         return True
     return name.endswith(("bn3", "downsample.1", "conv2.batch_norm", "linear_conv.1")) or name.endswith(".bn2")
 
@@ -68,6 +73,10 @@ def fill(shapes, seed):
       pos_block.<i>.proj.0.filters   Twins' PEG, a depthwise 3x3 added to its own input (gvt.py:311-325): N(0, fan_in^-1/2) = N(0, 1/3), so one
                                  PEG multiplies the stream's variance by 2, not by 3, and the four of them keep it far inside fp16
       pos_embeds.<i>             as pos_embed (gvt.py:240; PyramidVisionTransformer only: CPVTV2 deletes them)
+      _ghostbottleneck_<i>.{ghost_module_2.*, depthwise_conv, shortcut_*}._conv.filters   GhostNet's convs that NO ReLU follows
+                                 (ghostnet.py:109-126): N(0, fan_in^-1/2), not the ReLU gain sqrt(2) — up to four of them in a row, 16 blocks deep,
+                                 would otherwise double the stream's variance each and leave fp16 (BatchNorm is an affine map in eval mode);
+                                 with them, and the residual-feeding gamma rule on ghost_module_2.primary_conv / shortcut_conv, the stream stays O(10)
     """
     rng = np.random.default_rng(seed)
     out = {}
@@ -82,6 +91,8 @@ def fill(shapes, seed):
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(gain / np.sqrt(shape[0]))
         elif owner == "pos_embeds":
             a = np.clip(rng.standard_normal(shape, dtype=np.float32), -2, 2) * np.float32(0.02)
+        elif leaf == "filters" and _GHOST_LINEAR.match(owner):
+            a = rng.standard_normal(shape, dtype=np.float32) * np.float32(1.0 / np.sqrt(np.prod(shape[1:])))
         elif leaf == "filters":
             fan_in = int(np.prod(shape[1:]))
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(np.sqrt(2.0 / fan_in))

@@ -239,6 +239,11 @@ class Module(torch.nn.Module):
         self._invalidate()
         return r
 
+    def add_sublayer(self, name, sublayer):
+        """Paddle's Layer.add_sublayer, which the converted files keep (ghostnet.py:164): register `sublayer` under `name`, return it."""
+        self.add_module(str(name), sublayer)
+        return sublayer
+
     def _require_eval(self):
         if self.is_train:
             raise NotImplementedError(
