@@ -562,6 +562,49 @@ size_t tlxmi_ghost_module_param_bytes(int Cin, int m);
 int tlxmi_ghost_module(const tlxmi_ghost_module_desc* d, const void* x, const void* params, const void* res, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * MixNet's mixed depthwise convolution (classification/mixnet.py:195-252: split -> one depthwise conv a group, each with its own
+ * window -> concat; BatchNorm + activation of MixConvBlock :308-314) in one launch, with the Squeeze-Excitation pool (:182) of the
+ * result as an optional second output.  The C channels are G consecutive groups of group_channels[g] >= 1 channels; a channel c of
+ * group g has k = kernel[g] (odd, 3 .. 11) and p = (k - 1) / 2; one stride st (1 or 2) for all groups, dilation 1,
+ * Ho = (H - 1) / st + 1, Wo = (W - 1) / st + 1 for every group:
+ *     y[n][ho][wo][c] = T( act( (sum_{r,s<k} x[n][ho st + r - p][wo st + s - p][c] w_c[r][s]) * scale[c] + shift[c] ) )
+ *     pool[n][c]      = T( (sum_{ho,wo} float(y[n][ho][wo][c])) / (Ho Wo) )                   pool may be NULL
+ * T: fp16 or fp32.  A tap outside the image contributes zero.  fp32 accumulation in (r, s) order, scale, shift and act (none, ReLU,
+ * SiLU) in fp32, ONE rounding.  pool sums the ROUNDED y values (what tlxmi_global_avgpool would read back) in fp32 in a fixed order
+ * and rounds once.  x has pitch x_ld >= C and the columns behind C are never read; y has pitch y_ld >= C and nothing behind C is
+ * written; pool has pitch pool_ld >= C.  y aliases no input.  One writer per element, no atomics: two launches give the same bits.
+ * Group boundaries are arbitrary (90 | 90 | 90 | 90): the kernel works on slabs of 8 channels, and a slab that straddles a boundary
+ * runs at the larger window with the smaller filter centred among zero taps — so x must be finite there (0 * Inf is NaN).
+ * params: tlxmi_mixconv_dw_param_bytes(d) bytes, kmax = the largest kernel[g]:
+ *     T w[C / 8][kmax * kmax][8]   slab s = channels 8 s .. 8 s + 7 with K_s = the largest window among them: its FIRST K_s * K_s * 8
+ *                                  entries are [K_s][K_s][8] (tap r * K_s + s, channel fastest); a channel with k < K_s holds its k x k
+ *                                  taps at rows / columns (K_s - k) / 2 .. and zeros around them; the rest of the slab's room is unused;
+ *     fp32 scale[C], shift[C].
+ * tlxmi_mixconv_dw_supported(d, with_pool) is pure host code and answers 1 exactly for: fp16 or fp32; N, H, W >= 1; C % 8 == 0;
+ * 1 <= G <= 5; every group_channels[g] >= 1 and their sum C; every kernel[g] odd in 3 .. 11; stride 1 or 2; act none, ReLU or SiLU;
+ * x_ld, y_ld >= C and multiples of 8 (fp16) / 4 (fp32); (pixels * ld + 64) * sizeof(T) below 2^31 for x and y (32-bit byte offsets);
+ * kmax * (W + kmax - 1) * 8 sizeof(T) + kmax^2 * 8 sizeof(T) <= 160 KiB (one output row's window in LDS: W <= 909 in fp16 at
+ * kmax = 11); and with_pool: pool_ld >= C and the whole padded slab of an image in LDS,
+ *     ((Ho - 1) st + kmax) * (W + kmax - 1) * 8 sizeof(T) + kmax^2 * 8 sizeof(T) <= 160 KiB
+ * (56 x 56 at stride 2 with windows up to 11: 69 KiB in fp16, 138 KiB in fp32; 28 x 28 at stride 1: 25 / 49 KiB).  1 means the call
+ * is taken, given x, params, y and pool 16-byte aligned (TLXMI_ERR_ALIGNMENT otherwise); anything else returns
+ * TLXMI_ERR_UNSUPPORTED (run tlxmi_dwconv2d a group and tlxmi_global_avgpool instead).  param_bytes is 0 where supported(d, 0) is.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_mixconv_dw_desc {
+    int32_t dtype;
+    int32_t N, H, W, C;
+    int32_t G;
+    int32_t group_channels[5];
+    int32_t kernel[5];
+    int32_t stride;
+    int32_t x_ld, y_ld, pool_ld;
+    int32_t act;
+} tlxmi_mixconv_dw_desc;
+int tlxmi_mixconv_dw_supported(const tlxmi_mixconv_dw_desc* d, int with_pool);
+size_t tlxmi_mixconv_dw_param_bytes(const tlxmi_mixconv_dw_desc* d);
+int tlxmi_mixconv_dw(const tlxmi_mixconv_dw_desc* d, const void* x, const void* params, void* y, void* pool, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

@@ -1,0 +1,216 @@
+"""CPU-side tests of MixNet: the three factories build the reference's parameter tree (the fixtures', and the reference model file's where
+the reference tree is present), round_channels / split_channels and the constructor signatures are the reference's, the library's
+predicate and parameter-image size answer as host code, the parameter image equals a numpy statement of it, the plain-torch
+restatement reproduces the fixtures' logits from the seeded weights, and the MixNet rule of seeded.fill touches MixNet's names only."""
+import ctypes
+import inspect
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, REPO
+
+FIXTURES = [("mixnet_s_b2.npz", "mixnet_s", 321), ("mixnet_m_c10_200x224_b1.npz", "mixnet_m", 389), ("mixnet_l_c10_208x200_b1.npz", "mixnet_l", 389)]
+
+
+@pytest.mark.parametrize("fname,arch,count", FIXTURES)
+def test_parameter_tree_matches_fixture(fname, arch, count):
+    from tlxcv_amd import models, seeded
+    g = np.load(os.path.join(GOLDEN, fname))
+    assert str(g["arch"]) == arch
+    m = getattr(models, arch)(class_num=int(g["num_classes"]))
+    assert isinstance(m, models.MixNet)
+    shapes = seeded.shapes_of(m)
+    assert list(shapes.keys()) == list(g["param_names"]) and len(shapes) == count
+    names = list(shapes)
+    assert names[0] == "features.init_block.conv1.conv.filters" and names[-2:] == ["output.weights", "output.biases"]
+    assert "features.stage1.unit1.conv2.bn.gamma" in shapes and "features.stage2.unit1.se.conv1.filters" in shapes
+    assert not any(n.endswith("biases") for n in names[:-1])                      # b_init=() / bias=False: `output` alone has a bias
+    assert tuple(shapes["output.weights"]) == (1536, int(g["num_classes"]))
+    if arch == "mixnet_s":
+        assert tuple(shapes["features.stage1.unit1.exp_conv.conv.0.filters"]) == (48, 8, 1, 1)
+        assert tuple(shapes["features.stage4.unit4.conv1.conv.4.filters"]) == (144, 1, 11, 11)       # 720 channels in five groups
+        assert tuple(shapes["features.stage3.unit1.conv1.conv.2.filters"]) == (80, 1, 7, 7)
+    if arch == "mixnet_m":
+        assert tuple(shapes["features.stage4.unit2.conv1.conv.0.filters"]) == (90, 1, 3, 3)          # 360 channels in four groups of 90
+
+
+def test_parameter_tree_matches_reference_model_file():
+    from oracle.gen_golden import REF
+    if not os.path.isfile(os.path.join(REF, "tlxcv", "models", "classification", "mixnet.py")):
+        pytest.skip("reference tree not present")
+    code = ("import sys; sys.path.insert(0, 'tools'); import gen_mixnet_golden as G; from tlxcv_amd import seeded; "
+            "ref, _ = G.reference_module(); "
+            "print('\\n'.join(f'{k} {v}' for k, v in seeded.shapes_of(ref.mixnet_l(class_num=7)).items()))")
+    out = subprocess.check_output([sys.executable, "-c", code], cwd=REPO, text=True)
+    from tlxcv_amd import seeded
+    from tlxcv_amd.models import mixnet_l
+    mine = [f"{k} {tuple(v)}" for k, v in seeded.shapes_of(mixnet_l(class_num=7)).items()]
+    assert out.strip().splitlines() == mine
+
+
+def test_round_channels_and_split_channels():
+    import mixnet_restated as RS
+    from tlxcv_amd.models import MixConv, round_channels
+    assert MixConv.split_channels(96, 2) == [48, 48] and MixConv.split_channels(360, 4) == [90] * 4 and MixConv.split_channels(720, 5) == [144] * 5
+    assert MixConv.split_channels(100, 3) == [34, 33, 33] and MixConv.split_channels(16, 5) == [4, 3, 3, 3, 3]       # the remainder to the first
+    assert MixConv.split_channels(7, 1) == [7]
+    # worked by hand from mixnet.py:48-52: the widths of mixnet_l (x 1.3) and the two edges of the rule
+    for c, want in ((24 * 1.3, 32), (32 * 1.3, 40), (40 * 1.3, 56), (80 * 1.3, 104), (120 * 1.3, 160), (200 * 1.3, 264), (3, 8), (11.9, 16),
+                    (12, 16), (20, 24), (17, 16), (19, 24)):
+        assert round_channels(c) == want == RS.round_channels(c), c
+    assert round_channels(10, 4) == 12 and round_channels(100, 32) == 96
+    for n in (96, 360, 720, 100, 16):
+        for k in (1, 2, 3, 4, 5):
+            assert RS.split_channels(n, k) == MixConv.split_channels(n, k)
+
+
+def test_constructor_signatures_and_refusals():
+    import tlxcv_amd
+    from tlxcv_amd.models.classification import mixnet as M
+    tlxcv_amd.install()
+    from tlxcv.models import mixnet_s as aliased
+    assert aliased is M.mixnet_s
+    args = lambda f: list(inspect.signature(f).parameters)
+    assert args(M.MixNet.__init__)[1:] == ["channels", "init_block_channels", "final_block_channels", "exp_kernel_counts", "conv1_kernel_counts",
+                                           "conv2_kernel_counts", "exp_factors", "se_factors", "in_channels", "in_size", "class_num"]
+    assert args(M.MixUnit.__init__)[1:] == ["in_channels", "out_channels", "stride", "exp_kernel_count", "conv1_kernel_count",
+                                            "conv2_kernel_count", "exp_factor", "se_factor", "activation"]
+    conv = ["in_channels", "out_channels", "kernel_size", "stride", "padding", "dilation", "groups", "bias"]
+    assert args(M.MixConv.__init__)[1:] == conv + ["axis"]
+    assert args(M.MixConvBlock.__init__)[1:] == conv + ["use_bn", "bn_eps", "activation"] == args(M.ConvBlock.__init__)[1:]
+    assert args(M.SEBlock.__init__)[1:] == ["channels", "reduction", "mid_channels", "round_mid", "use_conv", "mid_activation", "out_activation"]
+    assert args(M.MixInitBlock.__init__)[1:] == ["in_channels", "out_channels"]
+    assert args(M.round_channels) == ["channels", "divisor"] and args(M.mixnet_s) == ["pretrained", "kwargs"]
+    m = M.mixnet_s(class_num=5, in_channels=3, in_size=(200, 208))
+    assert m.class_num == 5 and m.in_size == (200, 208) and tuple(m.output.weights.shape) == (1536, 5)
+    assert m.features.stage2.unit1.conv1.conv.splitted_in_channels == [48, 48, 48] and len(m.units()) == 1 + 2 + 4 + 3 + 6
+    u = M.MixUnit(40, 40, 1, 2, 2, 2, 6, 2, "swish")
+    assert u.residual and u.use_se and tuple(u.se.conv1.filters.shape) == (20, 240, 1, 1) and u.se.conv1.biases is None
+    with pytest.raises(NotImplementedError, match="pretrained"):
+        M.mixnet_m(pretrained=True)
+    with pytest.raises(NotImplementedError, match="set_eval"):
+        m(torch.zeros(1, 3, 224, 224))                              # train mode: refused like the other models
+    with pytest.raises(ValueError, match="Unsupported MixNet version"):
+        M.get_mixnet("x", 1.0)
+
+
+def _desc(**kw):
+    from tlxcv_amd import engine as E
+    d = dict(dtype=torch.float16, N=2, H=28, W=28, groups=[90] * 4, kernels=[3, 5, 7, 9], stride=1, act=E.ACT_SILU, C=None, x_ld=None, y_ld=None)
+    d.update(kw)
+    Cc = sum(d["groups"]) if d["C"] is None else d["C"]
+    return E._mixconv_desc(d["dtype"], d["N"], d["H"], d["W"], Cc, d["groups"], d["kernels"], d["stride"], d["x_ld"] or Cc, d["y_ld"] or Cc, Cc,
+                           d["act"])
+
+
+def test_predicate_and_param_bytes_are_host_code():
+    from tlxcv_amd import _lib, engine as E
+    lib = _lib.load()
+    ok = lambda pool=1, **kw: bool(lib.tlxmi_mixconv_dw_supported(ctypes.byref(_desc(**kw)), pool))
+    nbytes = lambda **kw: lib.tlxmi_mixconv_dw_param_bytes(ctypes.byref(_desc(**kw)))
+    assert ok() and ok(0) and ok(dtype=torch.float32) and ok(act=E.ACT_RELU) and ok(act=E.ACT_NONE) and ok(stride=2)
+    assert nbytes() == 360 * 81 * 2 + 2 * 360 * 4 and nbytes(dtype=torch.float32) == 360 * 81 * 4 + 2 * 360 * 4
+    assert nbytes(groups=[8], kernels=[3]) == 8 * 9 * 2 + 64
+    # the mixed units of the three variants at 224 x 224 (channels, groups, map, stride), SE pooled, either format
+    for Cc, G, hw, st in ((144, 3, 56, 2), (240, 2, 28, 1), (240, 3, 28, 2), (480, 2, 14, 1), (480, 3, 14, 1), (360, 4, 14, 1), (720, 5, 14, 2),
+                          (1200, 4, 7, 1), (192, 4, 56, 2), (312, 4, 56, 2), (960, 4, 14, 2), (1584, 4, 7, 1)):
+        for dt in (torch.float16, torch.float32):
+            n = Cc // G
+            assert ok(dtype=dt, H=hw, W=hw, groups=[Cc - n * (G - 1)] + [n] * (G - 1), kernels=[3 + 2 * i for i in range(G)], stride=st), (Cc, G, hw)
+    assert ok(0, H=112, W=112, groups=[64] * 3, kernels=[3, 5, 7], stride=2)          # stage 1 of mixnet_m: no SE, the rows are tiled
+    for dt in (torch.float16, torch.float32):                                          # the header's worst case: windows up to 11
+        assert ok(dtype=dt, H=56, W=56, groups=[8], kernels=[11], stride=2) and ok(dtype=dt, H=28, W=28, groups=[8], kernels=[11])
+    assert not ok(H=160, W=160, groups=[8], kernels=[11]) and ok(0, H=160, W=160, groups=[8], kernels=[11])      # the pool bound
+    assert not ok(groups=[8], kernels=[4]) and not ok(groups=[8], kernels=[13]) and not ok(groups=[8], kernels=[1]) and not ok(stride=3)
+    assert not ok(C=352) and not ok(groups=[4, 8], kernels=[3, 5]) and not ok(groups=[0, 8], kernels=[3, 5])
+    assert not ok(x_ld=364) and not ok(y_ld=364) and not ok(x_ld=352) and ok(x_ld=368, y_ld=376)
+    assert not ok(dtype=torch.float32, x_ld=362) and ok(dtype=torch.float32, x_ld=364)
+    assert not ok(act=E.ACT_RELU6) and not ok(act=E.ACT_GELU) and not ok(N=0) and not ok(H=0)
+    six = _desc(groups=[8] * 6, kernels=[3, 5, 7, 9, 11, 3])
+    six.G = 6
+    assert not lib.tlxmi_mixconv_dw_supported(ctypes.byref(six), 0) and lib.tlxmi_mixconv_dw_param_bytes(ctypes.byref(six)) == 0
+    # 32-bit byte offsets: (pixels * ld + 64) * sizeof(T) < 2^31 for x and y
+    assert ok(0, N=1, H=1024, W=1000, groups=[1000], kernels=[3]) and not ok(0, N=1, H=1024, W=1024, groups=[1024], kernels=[3])
+    assert not ok(0, dtype=torch.float32, N=1, H=1024, W=512, groups=[1024], kernels=[3])
+
+
+def test_parameter_image_matches_numpy():
+    """engine.mixconv_dw_pack against numpy: slab s of 8 channels at K_s = its largest window, [K_s][K_s][8] at the head of its
+    kmax^2 x 8 room, a smaller window centred among zeros; then scale, shift."""
+    from tlxcv_amd import engine as E
+    groups, kernels = [10, 10, 12], [3, 5, 9]
+    rng = np.random.default_rng(3)
+    filters = [rng.standard_normal((n, 1, k, k)).astype(np.float32) for n, k in zip(groups, kernels)]
+    Cc, kmax = 32, 9
+    scale, shift = rng.standard_normal(Cc).astype(np.float32), rng.standard_normal(Cc).astype(np.float32)
+    for dt, npdt in ((torch.float16, np.float16), (torch.float32, np.float32)):
+        blob = E.mixconv_dw_pack([torch.from_numpy(f) for f in filters], torch.from_numpy(scale), torch.from_numpy(shift), dt).numpy()
+        es = np.dtype(npdt).itemsize
+        assert blob.nbytes == Cc * kmax * kmax * es + 2 * Cc * 4
+        w = blob[:Cc * kmax * kmax * es].view(npdt).reshape(Cc // 8, kmax * kmax, 8)
+        kc = np.repeat(kernels, groups)
+        chan = np.concatenate([f[:, 0] for f in [np.pad(f, ((0, 0), (0, 0), ((kmax - k) // 2,) * 2, ((kmax - k) // 2,) * 2))
+                                                 for f, k in zip(filters, kernels)]])          # (C, 9, 9), every window centred
+        for s in range(Cc // 8):
+            K = int(kc[8 * s:8 * s + 8].max())
+            assert K == (3, 5, 9, 9)[s]
+            o = (kmax - K) // 2
+            want = chan[8 * s:8 * s + 8, o:o + K, o:o + K].transpose(1, 2, 0).reshape(K * K, 8).astype(npdt)
+            assert np.array_equal(w[s, :K * K], want) and not w[s, K * K:].any()
+        aff = blob[Cc * kmax * kmax * es:].view(np.float32).reshape(2, Cc)
+        assert np.array_equal(aff[0], scale) and np.array_equal(aff[1], shift)
+
+
+@pytest.mark.parametrize("fname,arch,count", FIXTURES)
+def test_fp32_restatement_reproduces_the_fixture(fname, arch, count):
+    """float32 restatement on seeded.fill weights against the logits the reference file gave in float64: 1e-4 of the logit range, same
+    argmax; the margin rule that keeps the GPU test's fp16 argmax check from being vacuous; distinct classes on the rows of a batch."""
+    import mixnet_restated as RS
+    from tlxcv_amd import models, seeded
+    g = np.load(os.path.join(GOLDEN, fname))
+    params = seeded.fill(seeded.shapes_of(getattr(models, arch)(class_num=int(g["num_classes"]))), int(g["weight_seed"]))
+    x = torch.from_numpy(RS.mixnet_input(int(g["batch"]), int(g["input_seed"]), *[int(v) for v in g["hw"]]))
+    outs = []
+    with torch.no_grad():
+        y = RS.mixnet({k: torch.from_numpy(v) for k, v in params.items()}, x, arch, outs).numpy()
+    lg = g["logits"]
+    rng_ = float(lg.max() - lg.min())
+    assert y.shape == lg.shape and np.abs(y - lg).max() <= 1e-4 * rng_ and (y.argmax(-1) == g["argmax"]).all()
+    s = np.sort(lg, axis=1)
+    assert ((s[:, -1] - s[:, -2]) > 2 * 0.003 * rng_).all()
+    assert float(g["restatement_max_abs_diff"]) <= 1e-5
+    assert max(float(u.abs().max()) for u in outs) < 1000.0                         # fp16 headroom of the residual stream
+    assert int(g["batch"]) == 1 or len(set(g["argmax"].tolist())) > 1
+
+
+def test_fill_rule_touches_only_mixnet_names():
+    """fill draws from one generator in name order: a rule keyed by a name no other model has cannot move their values.  (1) the values
+    of names that do not match are the same whether or not a matching name follows them; (2) a matching projection filter is drawn at
+    fan_in^-1/2, a non-matching filter of the same shape at sqrt(2 / fan_in), from the same normals."""
+    from tlxcv_amd import models, seeded
+    other = {"conv1._conv.filters": (16, 3, 3, 3), "layer1.0.conv2.filters": (8, 8, 3, 3), "layer1.0.bn2.gamma": (8,),
+             "_ghostbottleneck_3.ghost_module_2.primary_conv._conv.filters": (12, 24, 1, 1), "features.0.conv2.filters": (8, 8, 1, 1),
+             "stage1.unit1.conv2.conv.filters": (8, 8, 1, 1), "features.stage1.unit1.conv1.conv.0.filters": (8, 1, 3, 3),
+             "features.stage1.unit1.conv2.bn.gamma": (24,), "fc.weights": (32, 10), "fc.biases": (10,)}
+    before = seeded.fill(other, 5)
+    after = seeded.fill(dict(other, **{"features.stage1.unit1.conv2.conv.0.filters": (12, 36, 1, 1)}), 5)
+    for k in other:
+        assert np.array_equal(before[k], after[k]), k
+    assert 0.8 <= before["features.stage1.unit1.conv2.bn.gamma"].min() and before["features.stage1.unit1.conv2.bn.gamma"].max() <= 1.2
+    shape = (24, 72, 1, 1)
+    for name in ("features.stage1.unit2.conv2.conv.1.filters", "features.init_block.conv2.conv2.conv.filters", "features.stage4.unit6.conv2.conv.filters"):
+        a = seeded.fill({name: shape}, 9)[name]
+        b = seeded.fill({"features.stage1.unit2.exp_conv.conv.1.filters": shape}, 9)["features.stage1.unit2.exp_conv.conv.1.filters"]
+        assert np.allclose(a * np.sqrt(2.0), b, rtol=1e-6, atol=0) and abs(float(a.std()) - 72 ** -0.5) < 0.01
+    # every other family's fill is what it was: none of their names matches the rule
+    for arch in ("resnet18", "ghostnet_x0_5", "shufflenet_v2_x0_25", "mobilenet_v3_small"):
+        names = list(seeded.shapes_of(getattr(models, arch)()))
+        assert not any(seeded._MIXNET_PROJ.match(n) for n in names), arch
+    names = list(seeded.shapes_of(models.mixnet_s(class_num=10)))
+    hit = [n for n in names if seeded._MIXNET_PROJ.match(n) and n.endswith("filters")]
+    assert len(hit) == 3 * 1 + 13 * 2 and all(".conv2." in n for n in hit)            # 16 projections, 13 of them in two groups

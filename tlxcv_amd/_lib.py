@@ -56,6 +56,11 @@ class GhostModuleDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "Cin", "m", "x_ld", "y_ld", "res_ld", "act")]
 
 
+class MixConvDwDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "C", "G")] + [("group_channels", C.c_int32 * 5), ("kernel", C.c_int32 * 5)] + [
+        (n, C.c_int32) for n in ("stride", "x_ld", "y_ld", "pool_ld", "act")]
+
+
 class LkaGateDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in ("C", "a1_ld", "t_ld", "res_ld", "y_ld")]
 
@@ -183,6 +188,7 @@ PROTOTYPES = {
     "tlxmi_shuffle_unit": [C.POINTER(ShuffleUnitDesc), _vp, _vp, _vp, _vp],
     "tlxmi_shuffle_concat": [_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp],
     "tlxmi_ghost_module": [C.POINTER(GhostModuleDesc), _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_mixconv_dw": [C.POINTER(MixConvDwDesc), _vp, _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -217,6 +223,8 @@ _SPECIAL = {
     "tlxmi_shuffle_unit_param_bytes": ([_i], C.c_size_t),
     "tlxmi_ghost_module_supported": ([C.POINTER(GhostModuleDesc)], C.c_int),
     "tlxmi_ghost_module_param_bytes": ([_i, _i], C.c_size_t),
+    "tlxmi_mixconv_dw_supported": ([C.POINTER(MixConvDwDesc), _i], C.c_int),
+    "tlxmi_mixconv_dw_param_bytes": ([C.POINTER(MixConvDwDesc)], C.c_size_t),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

@@ -85,6 +85,11 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # (+ the bottleneck's shortcut) on tlxmi_ghost_module: ONE launch, the primary map of a pixel tile in LDS, the
                                   # 1x1 on MFMA, both halves stored from the launch; off = tlxmi_conv2d -> tlxmi_dwconv2d (-> tlxmi_affine_act
                                   # for the shortcut) (the A/B and the tests' other arm)
+            "mixconv": True,      # MixNet's mixed depthwise convs (fp16 and fp32; C a multiple of 8, up to five groups, odd windows 3 .. 11, stride 1 / 2):
+                                  # split -> a depthwise conv a group, each with its own window -> concat -> BN + act, and the SE pool of the
+                                  # result, on tlxmi_mixconv_dw: ONE launch, an 8-channel slab of an image (or of a row tile) in LDS, one read and
+                                  # one write of the map; elsewhere and off = one tlxmi_dwconv2d a group (through dense copies where a group does
+                                  # not start and end on 16-byte chunks) -> tlxmi_global_avgpool (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1734,6 +1739,166 @@ def ghost_module(x, params, act, res=None, fused=None, out=None):
     probe.append((e0, e1, (M * (cin + c * (2 if res is not None else 1)) + m * cin + 9 * m) * es, 2 * M * m * (cin + 9),
                   (N, H, W, cin, c, "ghost_module" if fused else "conv-dw-add")))
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# MixNet's mixed depthwise convolution
+# ---------------------------------------------------------------------------------------------
+def mixconv_dw_pack(filters, scale, shift, dtype):
+    """The parameter image tlxmi_mixconv_dw reads (include/tlxmi.h), as one uint8 tensor on the operands' device.  filters: one
+    (n_g, 1, k_g, k_g) tensor a group, in channel order; scale / shift: fp32 [C] (the folded BatchNorm over the concatenated map).
+    With kmax the largest k_g: T w[C / 8][kmax * kmax][8] — slab s (channels 8 s .. 8 s + 7) runs at K_s, the largest window among
+    its channels, and its first K_s * K_s * 8 entries are [K_s][K_s][8]; a channel with a smaller window sits centred among zero
+    taps — then fp32 scale[C], shift[C]."""
+    ks = [int(f.shape[-1]) for f in filters]
+    ns = [int(f.shape[0]) for f in filters]
+    Cc, kmax = sum(ns), max(ks)
+    dev = filters[0].device
+    kc = torch.cat([torch.full((n,), k, dtype=torch.int64) for n, k in zip(ns, ks)])          # window of every channel
+    full = torch.zeros((Cc, kmax, kmax), dtype=torch.float32, device=dev)                     # every channel centred at kmax
+    a = 0
+    for f, n, k in zip(filters, ns, ks):
+        o = (kmax - k) // 2
+        full[a:a + n, o:o + k, o:o + k] = f.detach().reshape(n, k, k).to(torch.float32)
+        a += n
+    w = torch.zeros((Cc // 8, kmax * kmax, 8), dtype=dtype, device=dev)
+    for s in range(Cc // 8):
+        K = int(kc[8 * s:8 * s + 8].max())
+        o = (kmax - K) // 2
+        w[s, :K * K] = full[8 * s:8 * s + 8, o:o + K, o:o + K].reshape(8, K * K).t().to(dtype)
+    aff = torch.stack([scale.detach().to(torch.float32), shift.detach().to(torch.float32)])
+    return torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in (w, aff)])
+
+
+class MixConvParams:
+    """One MixConv's weights in the forms both arms of mixconv_dw() read: a group's [k][k][n_g] depthwise filter and its slice of the
+    folded BatchNorm for tlxmi_dwconv2d (padded with zeros to whole 16-byte chunks where n_g is none), and — C a multiple of 8, at
+    most five groups, odd windows 3 .. 11 — the one-buffer image of tlxmi_mixconv_dw (mixconv_dw_pack).  filters: one (n_g, 1, k_g, k_g)
+    tensor a group; bn: (scale, shift) fp32 [C] over the concatenated channels."""
+
+    def __init__(self, filters, bn, dtype):
+        self.groups = [int(f.shape[0]) for f in filters]
+        self.kernels = [int(f.shape[-1]) for f in filters]
+        self.C = sum(self.groups)
+        self.dtype = dtype
+        self.scale, self.shift = _f32(bn[0]), _f32(bn[1])
+        dev = self.scale.device
+        v = vec(dtype)
+        self.per_group = []
+        a = 0
+        for f, n, k in zip(filters, self.groups, self.kernels):
+            npad = (n + v - 1) // v * v
+            w = torch.zeros((k, k, npad), dtype=dtype, device=dev)
+            w[..., :n] = f.detach()[:, 0].permute(1, 2, 0).to(dtype)
+            s, t = torch.zeros(npad, dtype=torch.float32, device=dev), torch.zeros(npad, dtype=torch.float32, device=dev)
+            s[:n], t[:n] = self.scale[a:a + n], self.shift[a:a + n]
+            self.per_group.append((a, n, npad, w, s, t))
+            a += n
+        self.blob = None
+        in_range = (self.C % 8 == 0 and 1 <= len(filters) <= 5 and all(3 <= k <= 11 and k % 2 for k in self.kernels)
+                    and all(tuple(f.shape[1:]) == (1, k, k) for f, k in zip(filters, self.kernels)))
+        if in_range:
+            self.blob = mixconv_dw_pack([f.to(dev) for f in filters], self.scale, self.shift, dtype)
+            assert self.blob.numel() == _lib.load().tlxmi_mixconv_dw_param_bytes(C.byref(_mixconv_desc(
+                dtype, 1, 1, 1, self.C, self.groups, self.kernels, 1, self.C, self.C, self.C, ACT_NONE)))
+
+
+def _mixconv_desc(dtype, N, H, W, Cc, groups, kernels, stride, x_ld, y_ld, pool_ld, act):
+    d = _lib.MixConvDwDesc(dtype=dt_code(dtype), N=N, H=H, W=W, C=Cc, G=len(groups), stride=stride, x_ld=x_ld, y_ld=y_ld, pool_ld=pool_ld, act=act)
+    for i in range(min(len(groups), 5)):
+        d.group_channels[i], d.kernel[i] = int(groups[i]), int(kernels[i])
+    return d
+
+
+def mixconv_dw_supported(x, groups, kernels, stride=1, act=ACT_NONE, pool=False, y_ld=None):
+    """Whether mixconv_dw() runs tlxmi_mixconv_dw on this NHWC map by default: the "mixconv" option on and the library takes the
+    shape (fp16 or fp32; C = sum(groups) a multiple of 8; at most five groups, odd windows 3 .. 11; stride 1 or 2; pitches in whole
+    16-byte chunks; with pool, the padded 8-channel slab of an image within the LDS — include/tlxmi.h).  More than five groups, a
+    stride pair or an activation code outside the descriptor are simply not taken."""
+    groups, kernels = list(groups), list(kernels)
+    if not _options["mixconv"] or x.dim() != 4 or not x.is_contiguous() or x.dtype not in (torch.float16, torch.float32):
+        return False
+    if len(groups) != len(kernels) or not 1 <= len(groups) <= 5 or not isinstance(stride, int):
+        return False
+    N, H, W, ld = x.shape
+    Cc = sum(groups)
+    y_ld = Cc if y_ld is None else int(y_ld)
+    return bool(_lib.load().tlxmi_mixconv_dw_supported(C.byref(_mixconv_desc(x.dtype, N, H, W, Cc, groups, kernels, stride, ld, y_ld, Cc, act)),
+                                                       1 if pool else 0))
+
+
+def mixconv_dw(x, params, stride, act, pool=False, fused=None, out=None):
+    """MixNet's MixConv + BatchNorm + activation (mixnet.py:244-252, :308-314) on an NHWC map x (N, H, W, x_ld) whose first
+    C = params.C channels are the input: channel c of group g runs a depthwise k_g x k_g conv (pad (k_g - 1) / 2, `stride`), then
+    * scale + shift and act -> y (N, Ho, Wo, C), or written into `out` (its last axis is the pitch; nothing behind C is written).
+    pool=True also returns the Squeeze-Excitation pool of y, (N, C) in x's dtype: -> (y, pool).  One launch (tlxmi_mixconv_dw) when
+    the "mixconv" option is on and the library takes the shape (mixconv_dw_supported); otherwise one tlxmi_dwconv2d a group — on the
+    column slice where it starts and ends on 16-byte chunks, through a dense zero-padded copy of the slice otherwise — and
+    tlxmi_global_avgpool.  fused=True / False forces one form (tests, tools/); True raises where the launch is not supported."""
+    global _probe
+    need_gpu(x, "input")
+    N, H, W, ld = x.shape
+    Cc = params.C
+    if x.dtype != params.dtype or ld < Cc or not x.is_contiguous():
+        raise RuntimeError(f"mixconv_dw: x must be a dense NHWC map of the parameters' dtype with at least {Cc} channels, got {tuple(x.shape)} {x.dtype}")
+    if not isinstance(stride, int) or stride < 1:
+        raise RuntimeError(f"mixconv_dw: one positive stride for both axes, got {stride!r}")
+    extents = {((H + 2 * ((k - 1) // 2) - k) // stride + 1, (W + 2 * ((k - 1) // 2) - k) // stride + 1) for k in params.kernels}
+    if len(extents) != 1 or min(extents.pop()) < 1:
+        raise RuntimeError(f"mixconv_dw: windows {params.kernels} at pad (k - 1) // 2 do not give one output extent on {H} x {W}")
+    k0 = params.kernels[0]
+    Ho, Wo = (H + 2 * ((k0 - 1) // 2) - k0) // stride + 1, (W + 2 * ((k0 - 1) // 2) - k0) // stride + 1
+    if out is None:
+        out = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
+    y_ld = out.shape[-1]
+    if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, Ho, Wo) or y_ld < Cc or not out.is_contiguous():
+        raise RuntimeError(f"mixconv_dw: out must be a dense ({N}, {Ho}, {Wo}, >= {Cc}) map of x's dtype")
+    desc = _mixconv_desc(x.dtype, N, H, W, Cc, params.groups, params.kernels, stride, ld, y_ld, Cc, act)
+    takes = bool(params.blob is not None and _lib.load().tlxmi_mixconv_dw_supported(C.byref(desc), 1 if pool else 0))
+    if fused is None:
+        fused = takes and _options["mixconv"]
+    elif fused and not takes:
+        raise RuntimeError(f"mixconv_dw: tlxmi_mixconv_dw does not take {tuple(x.shape)} {x.dtype} with groups {params.groups}, windows "
+                           f"{params.kernels}, stride {stride}, act {act}, y_ld {y_ld}, pool {pool}")
+    es = x.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * es, out.numel() * es)
+    pooled = torch.empty((N, Cc), dtype=x.dtype, device=x.device) if pool else None
+
+    def launch():
+        if fused:
+            _lib.call("tlxmi_mixconv_dw", C.byref(desc), _p(x), _p(params.blob), _p(out), _p(pooled), _stream())
+            return
+        v = vec(x.dtype)
+        for (a, n, npad, w, s, t), k in zip(params.per_group, params.kernels):
+            if a % v == 0 and n % v == 0 and ld % v == 0 and y_ld % v == 0:
+                dwconv2d(x[..., a:a + n], w, stride, (k - 1) // 2, 1, s, t, act=act, x_ld=ld, out=out[..., a:a + n], out_ld=y_ld)
+            else:       # the slice starts or ends inside a 16-byte chunk: a dense copy, zero filled up to the filter's padded width
+                piece = torch.zeros((N, H, W, npad), dtype=x.dtype, device=x.device)
+                piece[..., :n] = x[..., a:a + n]
+                out[..., a:a + n] = dwconv2d(piece, w, stride, (k - 1) // 2, 1, s, t, act=act)[..., :n]
+        if pool and Cc % v == 0 and y_ld % v == 0:
+            _lib.call("tlxmi_global_avgpool", _p(out), _p(pooled), dt_code(x.dtype), N, Ho * Wo, Cc, y_ld, Cc, _stream())
+        elif pool:      # C or the pitch is no whole number of 16-byte chunks: pool a dense zero-padded copy
+            cp = (Cc + v - 1) // v * v
+            wide = torch.zeros((N, Ho, Wo, cp), dtype=x.dtype, device=x.device)
+            wide[..., :Cc] = out[..., :Cc]
+            pooled.copy_(global_avgpool(wide)[:, :Cc])
+    if _probe is None:
+        launch()
+        return (out, pooled) if pool else out
+    probe, _probe = _probe, None      # the chain is one entry
+    try:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+    finally:
+        _probe = probe
+    taps = sum(n * k * k for n, k in zip(params.groups, params.kernels))
+    probe.append((e0, e1, (N * H * W * Cc + N * Ho * Wo * Cc + taps) * es, 2 * N * Ho * Wo * taps,
+                  (N, H, W, Cc, Cc, "mixconv_dw" if fused else "dw-per-group")))
+    return (out, pooled) if pool else out
 
 
 # ---------------------------------------------------------------------------------------------

@@ -38,3 +38,6 @@ from .shufflenetv2 import (ShuffleNetV2, InvertedResidual, InvertedResidualDS, c
 from .ghostnet import (GhostNet, GhostBottleneck, GhostModule, SEBlock, ghostnet_x0_5, ghostnet_x1_0, ghostnet_x1_3)  # noqa: F401
 from .gvt import (GroupAttention, SBlock, GroupBlock, PyramidVisionTransformer, PosCNN, CPVTV2, PCPVT, ALTGVT, pcpvt_small,  # noqa: F401
                   pcpvt_base, pcpvt_large, alt_gvt_small, alt_gvt_base, alt_gvt_large)
+# (the MixNet file's ConvBlock / SEBlock / get_activation_layer stay in their module: GhostNet's SEBlock owns that name here)
+from .mixnet import (MixNet, MixUnit, MixInitBlock, MixConv, MixConvBlock, mixconv1x1_block, round_channels, mixnet_s, mixnet_m,  # noqa: F401
+                     mixnet_l)

@@ -17,6 +17,8 @@ import numpy as np
 _TWINS_ATTN = re.compile(r"^blocks\.\d+\.\d+\.attn\.(q|kv|qkv|proj)$")
 # GhostNet (ghostnet.py:109-126): the convs of a bottleneck that no ReLU follows
 _GHOST_LINEAR = re.compile(r"^_ghostbottleneck_\d+\.(ghost_module_2\.(primary_conv|cheap_operation)|depthwise_conv|shortcut_depthwise|shortcut_conv)\._conv$")
+# MixNet (mixnet.py:410-417, :449): a unit's projection conv2 — no activation follows it and it feeds the residual add
+_MIXNET_PROJ = re.compile(r"^features\.(init_block\.conv2|stage\d+\.unit\d+)\.conv2\.")
 
 
 def image_batch(n, seed=0, hw=224, c=3):
@@ -77,6 +79,14 @@ def fill(shapes, seed):
                                  (ghostnet.py:109-126): N(0, fan_in^-1/2), not the ReLU gain sqrt(2) — up to four of them in a row, 16 blocks deep,
                                  would otherwise double the stream's variance each and leave fp16 (BatchNorm is an affine map in eval mode);
                                  with them, and the residual-feeding gamma rule on ghost_module_2.primary_conv / shortcut_conv, the stream stays O(10)
+      features.{init_block.conv2, stage<i>.unit<j>}.conv2.*.filters   MixNet's projections (mixnet.py:410-417: a 1x1 conv, plain or in two
+                                 groups, + BatchNorm with NO activation, added to the unit's input): N(0, fan_in^-1/2), not the ReLU gain
+                                 sqrt(2).  Under the general rules the eval-mode stream grows about 1.3 x a unit (its BatchNorm gamma is
+                                 named `conv2.bn`, which the residual-feeding gamma rule does not know) and peaks at 1254 (s), 1829 (m),
+                                 7265 (l) with logits near 1000: outside fp16.  With this rule alone unit outputs stay between 1 and 36.
+                                 The gamma is left at U(0.8, 1.2): a smaller gamma ON TOP of this rule kills the signal (the logits of two
+                                 images then differ by 0.5 % of their range and share one argmax).  Keyed by names only MixNet has: the
+                                 values drawn for every other model are unchanged
     """
     rng = np.random.default_rng(seed)
     out = {}
@@ -92,6 +102,8 @@ def fill(shapes, seed):
         elif owner == "pos_embeds":
             a = np.clip(rng.standard_normal(shape, dtype=np.float32), -2, 2) * np.float32(0.02)
         elif leaf == "filters" and _GHOST_LINEAR.match(owner):
+            a = rng.standard_normal(shape, dtype=np.float32) * np.float32(1.0 / np.sqrt(np.prod(shape[1:])))
+        elif leaf == "filters" and _MIXNET_PROJ.match(name):
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(1.0 / np.sqrt(np.prod(shape[1:])))
         elif leaf == "filters":
             fan_in = int(np.prod(shape[1:]))
