@@ -605,6 +605,45 @@ size_t tlxmi_mixconv_dw_param_bytes(const tlxmi_mixconv_dw_desc* d);
 int tlxmi_mixconv_dw(const tlxmi_mixconv_dw_desc* d, const void* x, const void* params, void* y, void* pool, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Res2Net's hierarchical 3 x 3 chain (classification/res2net.py:76-90, the stride-1 block) in one launch.  The NHWC map is cut
+ * into `scales` slices of w channels; slice s occupies the columns [s wp, s wp + w), wp >= w a multiple of 8 (every slice starts
+ * 16-byte aligned), and nc = scales - 1 convs (3 x 3, pad 1, stride 1, dilation 1, w -> w) follow each other:
+ *     a_0 = x_0,    a_s = fp16( float(x_s) + float(y_{s-1}) )                                  s = 1 .. nc - 1
+ *     y_s = fp16( act( conv3x3(a_s; W_s)[n] * scale_s[n] + shift_s[n] ) )                      s = 0 .. nc - 1, fp32 accumulation on MFMA
+ *     y_{scales-1} = x_{scales-1}                                                              bit-exact
+ * Roundings: y_s as stored and a_s as the MFMA reads it — where the layer-by-layer graph (tlxmi_conv2d, tlxmi_affine_act with res)
+ * rounds — and no others.  a_s at a position OUTSIDE the image is zero (the conv's padding), not x_s + act(shift_{s-1}).
+ * x: N*H*W pixels of pitch x_ld, y: the same pixels at pitch y_ld.  The input pad columns [s wp + w, (s + 1) wp) reach no output
+ * (they may hold NaN); the output pad columns are written as zeros (the expand conv reads them through zero filter rows); nothing
+ * behind column scales * wp of y is touched.  y aliases no input.  One writer per element, fixed summation order (tap r * 3 + s,
+ * then channels), no atomics: two launches give the same bits.
+ * params: tlxmi_res2_chain_param_bytes(d) bytes, np = w rounded up to 16, kp = w rounded up to 32, everything beyond w zero:
+ *     fp16 filt[nc][9][np][kp]   (conv s, tap r * 3 + s, row = output channel, column = input channel),
+ *     fp32 scale[nc][np], then fp32 shift[nc][np].
+ * A workgroup owns a band of tlxmi_res2_chain_band_rows(d) rows of one image over the full width and keeps two tiles of
+ * (band + 2 nc) x (W + 2) positions of kp * 2 + 16 bytes in LDS.
+ * tlxmi_res2_chain_supported() is pure host code and answers 1 exactly for: fp16; N, H, W >= 1; 2 <= scales <= 8; 8 <= w <= 208;
+ * w <= wp <= roundup(w, 16) and wp % 8 == 0; x_ld, y_ld >= scales * wp and multiples of 8; act none or ReLU;
+ * (pixels * ld + 64) * 2 below 2^31 for both pitches (32-bit byte offsets); and one band row within the LDS:
+ *     2 * (1 + 2 nc) * (W + 2) * (kp * 2 + 16) <= 160 KiB
+ * (26 channels x 4 slices: W <= 144; 208 x 4: W <= 23; 14 x 8: W <= 66).  1 means the call is taken, given x, params and y 16-byte
+ * aligned (TLXMI_ERR_ALIGNMENT otherwise; a null pointer is TLXMI_ERR_BAD_ARG); anything else returns TLXMI_ERR_UNSUPPORTED (run
+ * tlxmi_conv2d, tlxmi_affine_act and tlxmi_copy_channels instead).  param_bytes is 0 outside the ranges of scales and w;
+ * band_rows is 0 where supported() is.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_res2_chain_desc {
+    int32_t dtype;
+    int32_t N, H, W;
+    int32_t w, wp, scales;
+    int32_t x_ld, y_ld;
+    int32_t act;
+} tlxmi_res2_chain_desc;
+int tlxmi_res2_chain_supported(const tlxmi_res2_chain_desc* d);
+int tlxmi_res2_chain_band_rows(const tlxmi_res2_chain_desc* d);
+size_t tlxmi_res2_chain_param_bytes(const tlxmi_res2_chain_desc* d);
+int tlxmi_res2_chain(const tlxmi_res2_chain_desc* d, const void* x, const void* params, void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

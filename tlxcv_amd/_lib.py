@@ -61,6 +61,10 @@ class MixConvDwDesc(C.Structure):
         (n, C.c_int32) for n in ("stride", "x_ld", "y_ld", "pool_ld", "act")]
 
 
+class Res2ChainDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "w", "wp", "scales", "x_ld", "y_ld", "act")]
+
+
 class LkaGateDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in ("C", "a1_ld", "t_ld", "res_ld", "y_ld")]
 
@@ -189,6 +193,7 @@ PROTOTYPES = {
     "tlxmi_shuffle_concat": [_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp],
     "tlxmi_ghost_module": [C.POINTER(GhostModuleDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_mixconv_dw": [C.POINTER(MixConvDwDesc), _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_res2_chain": [C.POINTER(Res2ChainDesc), _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -225,6 +230,9 @@ _SPECIAL = {
     "tlxmi_ghost_module_param_bytes": ([_i, _i], C.c_size_t),
     "tlxmi_mixconv_dw_supported": ([C.POINTER(MixConvDwDesc), _i], C.c_int),
     "tlxmi_mixconv_dw_param_bytes": ([C.POINTER(MixConvDwDesc)], C.c_size_t),
+    "tlxmi_res2_chain_supported": ([C.POINTER(Res2ChainDesc)], C.c_int),
+    "tlxmi_res2_chain_band_rows": ([C.POINTER(Res2ChainDesc)], C.c_int),
+    "tlxmi_res2_chain_param_bytes": ([C.POINTER(Res2ChainDesc)], C.c_size_t),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

@@ -90,6 +90,13 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # result, on tlxmi_mixconv_dw: ONE launch, an 8-channel slab of an image (or of a row tile) in LDS, one read and
                                   # one write of the map; elsewhere and off = one tlxmi_dwconv2d a group (through dense copies where a group does
                                   # not start and end on 16-byte chunks) -> tlxmi_global_avgpool (the A/B and the tests' other arm)
+            "res2chain": True,    # Res2Net's hierarchical 3x3 chain of a stride-1 block (fp16, 2 .. 8 slices of 8 .. 208 channels at a padded pitch; the
+                                  # shapes the measured table keeps — the 56 x 56 blocks of 26w x 4s, the 56 x 56 and 28 x 28 ones of 14w x 8s:
+                                  # engine.RES2_CHAIN_WINS):
+                                  # conv -> add -> conv -> add -> conv -> copy on tlxmi_res2_chain: ONE launch, a band of rows of an image in LDS with
+                                  # a halo that shrinks a row a conv, every 3x3 as nine MFMA taps, the map read once and written once; elsewhere
+                                  # and off = tlxmi_conv2d -> tlxmi_affine_act (the add) -> tlxmi_conv2d ... -> tlxmi_copy_channels (the A/B and
+                                  # the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1899,6 +1906,146 @@ def mixconv_dw(x, params, stride, act, pool=False, fused=None, out=None):
     probe.append((e0, e1, (N * H * W * Cc + N * Ho * Wo * Cc + taps) * es, 2 * N * Ho * Wo * taps,
                   (N, H, W, Cc, Cc, "mixconv_dw" if fused else "dw-per-group")))
     return (out, pooled) if pool else out
+
+
+# ---------------------------------------------------------------------------------------------
+# Res2Net's hierarchical 3x3 chain
+# ---------------------------------------------------------------------------------------------
+def res2_chain_pack(filters, bns, w):
+    """The parameter image tlxmi_res2_chain reads (include/tlxmi.h), as one uint8 tensor on the operands' device.  filters: one
+    (w, w, 3, 3) tensor a conv, in chain order; bns: one (scale, shift) fp32 [w] pair a conv.  np = w rounded up to 16, kp = w rounded
+    up to 32: fp16 filt[nc][9][np][kp] (tap r * 3 + s, row = output channel, column = input channel, zero padded), then fp32
+    scale[nc][np], shift[nc][np]."""
+    nc, dev = len(filters), filters[0].device
+    np_, kp = (w + 15) // 16 * 16, (w + 31) // 32 * 32
+    f = torch.zeros((nc, 9, np_, kp), dtype=torch.float16, device=dev)
+    aff = torch.zeros((2, nc, np_), dtype=torch.float32, device=dev)
+    for j, (wt, (sc, sh)) in enumerate(zip(filters, bns)):
+        f[j, :, :w, :w] = wt.detach().to(torch.float32).permute(2, 3, 0, 1).reshape(9, w, w).to(torch.float16)
+        aff[0, j, :w], aff[1, j, :w] = sc.detach().to(torch.float32), sh.detach().to(torch.float32)
+    return torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in (f, aff)])
+
+
+class Res2ChainParams:
+    """The 3x3 convs of one Res2Net block (scales - 1 of them, w -> w channels each) in the forms both arms of res2_chain() read: a conv's
+    filter zero-padded to wp x wp channels (PackedFilter) with its folded BatchNorm zero-padded to wp, for tlxmi_conv2d on a slice of
+    the padded map; and — fp16, 2 <= scales <= 8, 8 <= w <= 208, w <= wp <= roundup(w, 16) — the one-buffer image of tlxmi_res2_chain
+    (res2_chain_pack).  filters: one (w, w, 3, 3) tensor a conv; bns: one (scale, shift) fp32 [w] pair a conv; wp: the slice pitch, a
+    multiple of 8."""
+
+    def __init__(self, filters, bns, w, wp, dtype):
+        if len(filters) != len(bns) or not filters or wp < w or wp % 8 or any(tuple(f.shape) != (w, w, 3, 3) for f in filters):
+            raise RuntimeError(f"Res2ChainParams: {len(filters)} filters of (w, w, 3, 3) with w = {w}, as many (scale, shift) pairs and a pitch "
+                               f"wp >= w that is a multiple of 8 are expected, got wp = {wp}, {[tuple(f.shape) for f in filters]}")
+        self.w, self.wp, self.scales, self.dtype = int(w), int(wp), len(filters) + 1, dtype
+        dev = filters[0].device
+        self.per_conv = []
+        for wt, (sc, sh) in zip(filters, bns):
+            full = torch.zeros((wp, wp, 3, 3), dtype=torch.float32, device=dev)
+            full[:w, :w] = wt.detach().to(torch.float32)
+            s, t = torch.zeros(wp, dtype=torch.float32, device=dev), torch.zeros(wp, dtype=torch.float32, device=dev)
+            s[:w], t[:w] = _f32(sc), _f32(sh)
+            self.per_conv.append((PackedFilter(full, dtype), s, t))
+        self.blob = None
+        d = _res2_chain_desc(dtype, 1, 1, 1, self.w, self.wp, self.scales, self.scales * self.wp, self.scales * self.wp, ACT_NONE) \
+            if dtype == torch.float16 else None
+        if d is not None and _lib.load().tlxmi_res2_chain_supported(C.byref(d)):
+            self.blob = res2_chain_pack([f.to(dev) for f in filters], [(_f32(a), _f32(b)) for a, b in bns], self.w)
+            assert self.blob.numel() == _lib.load().tlxmi_res2_chain_param_bytes(C.byref(d))
+
+
+def _res2_chain_desc(dtype, N, H, W, w, wp, scales, x_ld, y_ld, act):
+    return _lib.Res2ChainDesc(dtype=dt_code(dtype), N=N, H=H, W=W, w=w, wp=wp, scales=scales, x_ld=x_ld, y_ld=y_ld, act=act)
+
+
+def res2_chain_takes(x, w, wp, scales, act=ACT_RELU, y_ld=None):
+    """Whether tlxmi_res2_chain takes this NHWC map (the library's predicate: include/tlxmi.h)."""
+    if x.dim() != 4 or not x.is_contiguous() or x.dtype != torch.float16:
+        return False
+    N, H, W, ld = x.shape
+    y_ld = scales * wp if y_ld is None else int(y_ld)
+    return bool(_lib.load().tlxmi_res2_chain_supported(C.byref(_res2_chain_desc(x.dtype, N, H, W, w, wp, scales, ld, y_ld, act))))
+
+
+# (H, W, w, scales) of the chains where the one launch was measured FASTER than the layer-by-layer arm beyond the spread of both, at batch
+# 256 on one MI355X (tools/res2net_bench.py, profiles/res2net/res2net_bench_b256.txt): res2_chain() keeps the launch there and runs the
+# layered arm everywhere else by default.  The launch wins where w <= 32 — a conv's filter fragments stay in registers — and the map is
+# large: 0.86 of the layered time at Res2Net-50 26w x 4s's 56 x 56 blocks, 0.85 / 0.43 at 14w x 8s's 56 x 56 / 28 x 28 blocks; it takes
+# 1.7 - 3.0 x the layered time at the wider slices of the later stages (DESIGN 4.29 says why)
+RES2_CHAIN_WINS = frozenset({(56, 56, 26, 4), (56, 56, 14, 8), (28, 28, 28, 8)})
+
+
+def _res2_chain_routed(H, W, w, scales):
+    return (H, W, w, scales) in RES2_CHAIN_WINS
+
+
+def res2_chain_supported(x, w, wp, scales, act=ACT_RELU, y_ld=None):
+    """Whether res2_chain() runs tlxmi_res2_chain on this map by default: the "res2chain" option on, the library takes the shape
+    (res2_chain_takes) and the measured table keeps it (RES2_CHAIN_WINS)."""
+    return bool(_options["res2chain"] and x.dim() == 4 and _res2_chain_routed(x.shape[1], x.shape[2], w, scales)
+                and res2_chain_takes(x, w, wp, scales, act, y_ld))
+
+
+def res2_chain(x, params, act, fused=None, out=None):
+    """The hierarchical 3x3 chain of a stride-1 Res2Net block (res2net.py:76-90) on an NHWC map x (N, H, W, x_ld) whose slice s is the
+    columns [s wp, s wp + w): y_0 = act(bn_0(conv_0(x_0))), y_s = act(bn_s(conv_s(x_s + y_{s-1}))), the last slice passes through
+    -> y (N, H, W, scales * wp), or written into `out` (its last axis is the pitch; nothing behind scales * wp is written), the pad
+    columns [s wp + w, (s + 1) wp) zero.  One launch (tlxmi_res2_chain) when the "res2chain" option is on, the library takes the shape
+    and the measured table keeps it (res2_chain_supported); otherwise — and for fp32 — tlxmi_conv2d on a slice, tlxmi_affine_act with
+    res (the add) into a dense scratch slice, tlxmi_conv2d ... and tlxmi_copy_channels for the last slice.  The layered arm reads the
+    pad columns of x through zero filter columns, so they must be finite there (the reduce conv of the model writes zeros).
+    fused=True / False forces one form (tests, tools/); True raises where the launch is not supported."""
+    global _probe
+    need_gpu(x, "input")
+    N, H, W, ld = x.shape
+    w, wp, S = params.w, params.wp, params.scales
+    if x.dtype != params.dtype or ld < S * wp or ld % 8 or not x.is_contiguous():
+        raise RuntimeError(f"res2_chain: x must be a dense NHWC map of the parameters' dtype with at least {S * wp} channels at a pitch that "
+                           f"is a multiple of 8, got {tuple(x.shape)} {x.dtype}")
+    if out is None:
+        out = torch.empty((N, H, W, S * wp), dtype=x.dtype, device=x.device)
+    y_ld = out.shape[-1]
+    if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, H, W) or y_ld < S * wp or y_ld % 8 or not out.is_contiguous():
+        raise RuntimeError(f"res2_chain: out must be a dense ({N}, {H}, {W}, >= {S * wp}) map of x's dtype at a pitch that is a multiple of 8")
+    if fused is None:       # the option and the table first: the library's predicate is asked only where they keep the launch
+        fused = bool(_options["res2chain"] and params.blob is not None and _res2_chain_routed(H, W, w, S)
+                     and res2_chain_takes(x, w, wp, S, act, y_ld))
+    elif fused and not (params.blob is not None and res2_chain_takes(x, w, wp, S, act, y_ld)):
+        raise RuntimeError(f"res2_chain: tlxmi_res2_chain does not take {tuple(x.shape)} {x.dtype} with w {w}, wp {wp}, scales {S}, act {act}, y_ld {y_ld}")
+    es = x.element_size()
+    if getattr(_tls, "act_max", None) is not None:
+        _note_act(x.numel() * es, out.numel() * es)
+
+    def launch():
+        if fused:
+            desc = _res2_chain_desc(x.dtype, N, H, W, w, wp, S, ld, y_ld, act)
+            _lib.call("tlxmi_res2_chain", C.byref(desc), _p(x), _p(params.blob), _p(out), _stream())
+            return
+        rows, dt = N * H * W, dt_code(x.dtype)
+        scratch = torch.empty((N, H, W, wp), dtype=x.dtype, device=x.device) if S > 2 else None
+        for j, (pk, s, t) in enumerate(params.per_conv):
+            dst = out[..., j * wp:(j + 1) * wp]
+            if j == 0:
+                conv2d(x[..., :wp], pk, 1, 1, 1, s, t, act=act, out=dst, out_ld=y_ld, x_ld=ld)
+            else:       # a_j = x_j + y_{j-1}: the add comes BEFORE the conv, so it cannot ride a conv epilogue
+                _lib.call("tlxmi_affine_act", _p(x[..., j * wp:(j + 1) * wp]), _p(None), _p(None), _p(out[..., (j - 1) * wp:j * wp]), _p(scratch),
+                          dt, rows, wp, ld, y_ld, wp, ACT_NONE, 0.0, 0, _stream())
+                conv2d(scratch, pk, 1, 1, 1, s, t, act=act, out=dst, out_ld=y_ld)
+        _lib.call("tlxmi_copy_channels", _p(x[..., (S - 1) * wp:S * wp]), _p(out[..., (S - 1) * wp:S * wp]), dt, rows, wp, ld, y_ld, _stream())
+    if _probe is None:
+        launch()
+        return out
+    probe, _probe = _probe, None      # the chain is one entry
+    try:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+    finally:
+        _probe = probe
+    probe.append((e0, e1, (2 * N * H * W * S * w + (S - 1) * 9 * w * w) * es, 2 * N * H * W * (S - 1) * 9 * w * w,
+                  (N, H, W, S * w, S * w, "res2_chain" if fused else "conv-add-conv-copy")))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

@@ -41,3 +41,5 @@ from .gvt import (GroupAttention, SBlock, GroupBlock, PyramidVisionTransformer, 
 # (the MixNet file's ConvBlock / SEBlock / get_activation_layer stay in their module: GhostNet's SEBlock owns that name here)
 from .mixnet import (MixNet, MixUnit, MixInitBlock, MixConv, MixConvBlock, mixconv1x1_block, round_channels, mixnet_s, mixnet_m,  # noqa: F401
                      mixnet_l)
+# (the Res2Net file's ConvBNLayer / BottleneckBlock stay in their module: DenseNet's ConvBNLayer owns that name here)
+from .res2net import Res2Net, res2net  # noqa: F401
