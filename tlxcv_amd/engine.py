@@ -297,6 +297,53 @@ def _note_act(*nbytes):
         _tls.act_max = m
 
 
+def _sizing():
+    """True inside a sizing forward (_sized()): a launch then reports its operand bytes to _note_act().  The byte arguments stay behind
+    this guard: an eager forward outside it pays one attribute lookup per launch and no numel() products."""
+    return getattr(_tls, "act_max", None) is not None
+
+
+def _timed(launch, entry):
+    """launch() -> its result.  With a probe list installed, one (start_event, end_event, bytes, flops, label) entry is recorded around
+    it; entry() -> (bytes, flops, label) is evaluated after the launch.  The list is taken away meanwhile, so engine calls inside
+    launch() record nothing (a chain of launches is one entry); if launch() raises nothing is appended and the list is put back."""
+    global _probe
+    if _probe is None:
+        return launch()
+    probe, _probe = _probe, None
+    try:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = launch()
+        e1.record()
+    finally:
+        _probe = probe
+    probe.append((e0, e1, *entry()))
+    return res
+
+
+def _use_fused(op, fused, takes, default, describe):
+    """The fused=None / True / False argument of a two-arm op -> whether tlxmi_<op> runs.  None: `default` (the option, the routing
+    table and the library's predicate, in the order the op asks them); True: raises where the library does not take the call
+    (`takes`; describe() names the operands); False: the layered arm.  takes / default: values, or callables asked only when needed."""
+    if fused is None:
+        return bool(default() if callable(default) else default)
+    if fused and not (takes() if callable(takes) else takes):
+        raise RuntimeError(f"{op}: tlxmi_{op} does not take {describe()}")
+    return bool(fused)
+
+
+def _out_map(op, out, N, H, W, min_c, dtype, device, default_ld, multiple=1, what=""):
+    """The output of a fused op: `out`, or a new (N, H, W, default_ld) map -> (out, its pixel pitch).  A dense NHWC map of that dtype
+    and those pixels whose last axis, the pitch, holds at least min_c channels and is a multiple of `multiple`; else "out must be <what>"."""
+    if out is None:
+        out = torch.empty((N, H, W, default_ld), dtype=dtype, device=device)
+    y_ld = out.shape[-1]
+    if out.dtype != dtype or tuple(out.shape[:3]) != (N, H, W) or y_ld < min_c or y_ld % multiple or not out.is_contiguous():
+        raise RuntimeError(f"{op}: out must be {what}")
+    return out, y_ld
+
+
 def image_bytes(model, x):
     """Bytes per image of the largest activation operand of model's forward on inputs shaped like x (at the current precision),
     or None while it has not been measured (the first eager forward of that shape measures it; see two_streams())."""
@@ -356,7 +403,7 @@ def two_streams(min_batch, plan=None, eager=True):
         def wrapper(self, x, *args, **kwargs):
             if args or kwargs or not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4):
                 return fwd(self, x, *args, **kwargs)
-            if getattr(_tls, "act_max", None) is not None:      # inside the sizing forward of an enclosing model
+            if _sizing():      # inside the sizing forward of an enclosing model
                 return fwd(self, x)
             key = (tuple(x.shape[1:]), x.dtype, precision())
             per = image_bytes(self, x)
@@ -608,6 +655,33 @@ class PackedGroupFilter:
                   dt_code(dtype), _stream())
 
 
+def _round_up(n, k):
+    return (int(n) + k - 1) // k * k
+
+
+def _zero_padded(t, shape, dtype, device=None):
+    """Zeros of `shape` / `dtype` with t converted and written into the leading corner, on `device` (default: t's).  t: a tensor, or a
+    sequence of equal tensors that become the rows of a new leading axis."""
+    if not isinstance(t, torch.Tensor):
+        device = device or t[0].device
+        t = torch.stack([v.detach().to(device=device, dtype=dtype) for v in t])
+    out = torch.zeros(shape, dtype=dtype, device=device or t.device)
+    out[tuple(slice(0, n) for n in t.shape)] = t.detach().to(dtype)
+    return out
+
+
+def _dw_rsc(wdw, n_pad, dtype, device=None):
+    """A depthwise filter (n, 1, k, k) -> [k][k][n_pad] in `dtype`, the channels behind n zero: what tlxmi_dwconv2d reads; reshaped to
+    (k * k, n_pad) its rows are the taps r * k + s of the parameter images."""
+    k = int(wdw.shape[-1])
+    return _zero_padded(wdw.detach()[:, 0].permute(1, 2, 0), (k, k, n_pad), dtype, device)
+
+
+def _param_image(*tensors):
+    """Dense tensors of any dtype, one behind the other, as the one uint8 buffer a fused kernel stages."""
+    return torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in tensors])
+
+
 def fold_bn(gamma, beta, mean, var, eps, conv_bias=None):
     """Eval-mode BatchNorm (+ optional conv bias) -> per-channel fp32 (scale, shift)."""
     ref = next(t for t in (gamma, beta, mean, var, conv_bias) if t is not None)
@@ -675,7 +749,7 @@ def conv2d(x, pk, stride=1, padding=0, dilation=1, scale=None, shift=None, res=N
             return None
         out = torch.empty((N, Ho // 2, Wo // 2, pk.Cout), dtype=x.dtype, device=x.device)
     M = N * Ho * Wo
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * x.element_size(), M * out_ld * x.element_size(), M * d.res_ld * x.element_size() if res is not None else 0)
     splits = 0 if maxpool3s2 else _conv_splits(d, M, pk, x, out_ld, y_nstride, res_nstride, res_bcast)
 
@@ -686,18 +760,12 @@ def conv2d(x, pk, stride=1, padding=0, dilation=1, scale=None, shift=None, res=N
             _lib.call("tlxmi_conv2d_splitk", C.byref(d), splits, _p(x), _p(pk.buf), _p(part), _p(scale), _p(shift), _p(res), _p(out), _stream())
         else:
             _lib.call("tlxmi_conv2d", C.byref(d), _p(x), _p(pk.buf), _p(scale), _p(shift), _p(res), _p(out), _stream())
-    if _probe is None:
-        launch()
+    if _probe is None:      # 60 - 100 of a small model's launches come through here: the host-bound forwards (two_streams()) pay neither the
+        launch()            # helper's call nor the entry's closure (measured: 0.5 - 1 % of MobileNetV3-small's eager forward)
         return out
-    es = x.element_size()
-    alg_bytes = (N * H * W * pk.Cin + (M // 4 if maxpool3s2 else M) * pk.Cout * (2 if res is not None else 1)
-                 + pk.Cout * pk.Cin * pk.R * pk.S) * es
-    flops = 2 * M * pk.Cout * pk.Cin * pk.R * pk.S
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    launch()
-    e1.record()
-    _probe.append((e0, e1, alg_bytes, flops, (N, H, W, pk.Cin, pk.Cout, pk.R, sh, res is not None)))
+    _timed(launch, lambda: ((N * H * W * pk.Cin + (M // 4 if maxpool3s2 else M) * pk.Cout * (2 if res is not None else 1)
+                             + pk.Cout * pk.Cin * pk.R * pk.S) * x.element_size(), 2 * M * pk.Cout * pk.Cin * pk.R * pk.S,
+                            (N, H, W, pk.Cin, pk.Cout, pk.R, sh, res is not None)))
     return out
 
 
@@ -752,7 +820,7 @@ def bottleneck_seam(t2, pk3, scale3, shift3, skip, pk1, scale1, shift1, proj=Non
     y = torch.empty((N, (H + 1) // 2, (W + 1) // 2, pk3.Cout) if y_stride2 else (N, H, W, pk3.Cout), dtype=t2.dtype, device=t2.device)
     t1 = torch.empty((N, H, W, pk1.Cout), dtype=t2.dtype, device=t2.device)
     rows = N * H * W
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(t2.numel() * t2.element_size(), skip.numel() * skip.element_size(), y.numel() * y.element_size(), t1.numel() * t1.element_size())
     d = _lib.SeamDesc(dtype=dt_code(t2.dtype), rows=rows, K1=pk3.Cin, N1=pk3.Cout, N2=pk1.Cout, t2_ld=ld, skip_ld=skip.shape[-1],
                       y_ld=pk3.Cout, t1_ld=pk1.Cout, act=ACT_RELU)
@@ -767,18 +835,11 @@ def bottleneck_seam(t2, pk3, scale3, shift3, skip, pk1, scale1, shift1, proj=Non
         pkd, sd, hd = proj
         args = (C.byref(d), _p(t2), _p(pk3.buf), _p(scale3), _p(shift3), _p(skip), _p(pkd.buf), _p(sd), _p(hd), _p(y), _p(pk1.buf), _p(scale1),
                 _p(shift1), _p(t1), _stream())
-    if _probe is None:
-        _lib.call(name, *args)
-        return y, t1
-    es = t2.element_size()
     skip_ch = pk3.Cout if proj is None else proj[0].Cin
-    alg_bytes = (rows * (pk3.Cin + skip_ch + pk1.Cout) + y.numel() + pk3.Cout * pk3.Cin + pk1.Cout * pk1.Cin) * es
-    flops = 2 * rows * (pk3.Cout * pk3.Cin + pk1.Cout * pk1.Cin + (0 if proj is None else pk3.Cout * proj[0].Cin))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.call(name, *args)
-    e1.record()
-    _probe.append((e0, e1, alg_bytes, flops, (N, H, W, pk3.Cin, pk3.Cout, pk1.Cout, "seam+dec" if y_stride2 else "seam" if proj is None else "seam+proj", True)))
+    _timed(lambda: _lib.call(name, *args),
+           lambda: ((rows * (pk3.Cin + skip_ch + pk1.Cout) + y.numel() + pk3.Cout * pk3.Cin + pk1.Cout * pk1.Cin) * t2.element_size(),
+                    2 * rows * (pk3.Cout * pk3.Cin + pk1.Cout * pk1.Cin + (0 if proj is None else pk3.Cout * proj[0].Cin)),
+                    (N, H, W, pk3.Cin, pk3.Cout, pk1.Cout, "seam+dec" if y_stride2 else "seam" if proj is None else "seam+proj", True)))
     return y, t1
 
 
@@ -830,19 +891,13 @@ def conv1x1_proj(t2, x2, pk, stride, shift=None, act=ACT_NONE, act_param=0.0, ou
     d = _proj_desc(t2, x2, pk, stride, out.shape[-1], act, act_param, k2)
     M = N * Ho * Wo
     es = t2.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(t2.numel() * es, x2.numel() * es, M * d.y_ld * es)
     args = (C.byref(d), _p(t2), _p(x2), _p(pk.buf), _p(shift), _p(out), _stream())
-    if _probe is None:
-        _lib.call("tlxmi_conv1x1_proj", *args)
-        return out
     # algorithmic bytes: the rows of t2, the pixels of x2 the stride selects, the output, the filter
-    alg_bytes = (M * (d.K1 + d.K2) + M * pk.Cout + pk.Cout * pk.Cin) * es
-    flops = 2 * M * pk.Cout * pk.Cin
-    e0, e1 = _probe_pair()
-    _lib.call("tlxmi_conv1x1_proj", *args)
-    e1.record()
-    _probe.append((e0, e1, alg_bytes, flops, (N, Ho, Wo, d.K1, pk.Cout, d.K2, "expand+proj", int(stride))))
+    _timed(lambda: _lib.call("tlxmi_conv1x1_proj", *args),
+           lambda: ((M * (d.K1 + d.K2) + M * pk.Cout + pk.Cout * pk.Cin) * es, 2 * M * pk.Cout * pk.Cin,
+                    (N, Ho, Wo, d.K1, pk.Cout, d.K2, "expand+proj", int(stride))))
     return out
 
 
@@ -872,21 +927,13 @@ def group_conv2d(x, pk, stride=1, padding=0, dilation=1, scale=None, shift=None,
                       y_nstride=0, res_nstride=0, act=act, act_param=float(act_param),
                       flags=(EPI_RES_AFTER_ACT if res_after_act else 0) | plan_flags())
     args = (C.byref(d), pk.groups, _p(x), _p(pk.buf), _p(scale), _p(shift), _p(res), _p(out), _stream())
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * x.element_size(), out.numel() * out.element_size(), res.numel() * res.element_size() if res is not None else 0)
-    if _probe is None:
-        _lib.call("tlxmi_group_conv2d", *args)
-        return out
-    es = x.element_size()
     M = N * Ho * Wo
     cg = pk.Cin // pk.groups
-    alg_bytes = (N * H * W * pk.Cin + M * pk.Cout * (2 if res is not None else 1) + pk.Cout * cg * pk.R * pk.S) * es
-    flops = 2 * M * pk.Cout * cg * pk.R * pk.S
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.call("tlxmi_group_conv2d", *args)
-    e1.record()
-    _probe.append((e0, e1, alg_bytes, flops, (N, H, W, pk.Cin, pk.Cout, pk.R, sh, f"g{pk.groups}")))
+    _timed(lambda: _lib.call("tlxmi_group_conv2d", *args),
+           lambda: ((N * H * W * pk.Cin + M * pk.Cout * (2 if res is not None else 1) + pk.Cout * cg * pk.R * pk.S) * x.element_size(),
+                    2 * M * pk.Cout * cg * pk.R * pk.S, (N, H, W, pk.Cin, pk.Cout, pk.R, sh, f"g{pk.groups}")))
     return out
 
 
@@ -1025,14 +1072,11 @@ def mlp_seam(x, pk1, b1, pk2, b2, res, out=None):
     if not res.is_contiguous():
         raise RuntimeError("mlp_seam: the residual must be dense")
     y = out if out is not None else torch.empty((*shp[:-1], N), dtype=x.dtype, device=x.device)
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(rows * max(K, N) * x.element_size())
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    _lib.call("tlxmi_mlp_seam", dt_code(x.dtype), rows, K, pk1.Cout, N, _p(x), K, _p(pk1.buf), _p(b1), _p(pk2.buf), _p(b2), _p(res), N, _p(y), N, _stream())
-    if _probe is not None:
-        e1.record()
-        _probe.append((e0, e1, (rows * (K + 2 * N) + 2 * pk1.Cout * K) * 2, 2 * rows * pk1.Cout * (K + N), (rows, 1, 1, K, N, pk1.Cout, "mlp seam", True)))
+    _timed(lambda: _lib.call("tlxmi_mlp_seam", dt_code(x.dtype), rows, K, pk1.Cout, N, _p(x), K, _p(pk1.buf), _p(b1), _p(pk2.buf), _p(b2), _p(res), N,
+                             _p(y), N, _stream()),
+           lambda: ((rows * (K + 2 * N) + 2 * pk1.Cout * K) * 2, 2 * rows * pk1.Cout * (K + N), (rows, 1, 1, K, N, pk1.Cout, "mlp seam", True)))
     return y
 
 
@@ -1062,12 +1106,6 @@ class LinearLN:
         self.K, self.Cout = w.shape[1], w.shape[0]
 
 
-def _probe_pair():
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    return e0, e1
-
-
 def linear_stats(x, pk, bias=None, res=None, out=None):
     """y = x W^T + bias (+ res) as linear(), plus per row (sum, sum of squares) of y over every 256-channel tile column from the same
     epilogue: returns (y, partials (rows, 4, 2) fp32, pair p < ceil(Cout / 256) written) — the statistics of the LayerNorm that follows,
@@ -1084,17 +1122,12 @@ def linear_stats(x, pk, bias=None, res=None, out=None):
         raise RuntimeError("linear_stats: the residual must be a dense tensor of the input's dtype")
     y = out if out is not None else torch.empty((*shp[:-1], pk.Cout), dtype=x.dtype, device=x.device)
     part = torch.empty((rows, 4, 2), dtype=torch.float32, device=x.device)      # pair p < ceil(Cout / 256) written
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(rows * max(K, pk.Cout) * x.element_size())
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    _lib.call("tlxmi_linear_stats", dt_code(x.dtype), rows, K, pk.Cout, K, pk.Cout, _p(x), _p(pk.buf), _p(bias), _p(res),
-              pk.Cout if res is not None else 0, _p(y), _p(part), plan_flags(), _stream())
-    if _probe is not None:
-        e1.record()
-        es = x.element_size()
-        _probe.append((e0, e1, (rows * K + rows * pk.Cout * (2 if res is not None else 1) + pk.Cout * K) * es + part.numel() * 4,
-                       2 * rows * pk.Cout * K, (rows, 1, 1, K, pk.Cout, 1, 1, res is not None)))
+    _timed(lambda: _lib.call("tlxmi_linear_stats", dt_code(x.dtype), rows, K, pk.Cout, K, pk.Cout, _p(x), _p(pk.buf), _p(bias), _p(res),
+                             pk.Cout if res is not None else 0, _p(y), _p(part), plan_flags(), _stream()),
+           lambda: ((rows * K + rows * pk.Cout * (2 if res is not None else 1) + pk.Cout * K) * x.element_size() + part.numel() * 4,
+                    2 * rows * pk.Cout * K, (rows, 1, 1, K, pk.Cout, 1, 1, res is not None)))
     return y, part
 
 
@@ -1109,17 +1142,12 @@ def linear_ln(x, prep, part, eps, act=ACT_NONE, out=None):
     if tuple(part.shape) != (rows, 4, 2) or part.dtype != torch.float32 or not part.is_contiguous():
         raise RuntimeError(f"linear_ln: statistics of shape {tuple(part.shape)} for {rows} rows (expected {(rows, 4, 2)} fp32)")
     y = out if out is not None else torch.empty((*shp[:-1], prep.Cout), dtype=x.dtype, device=x.device)
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(rows * max(prep.K, prep.Cout) * x.element_size())
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    _lib.call("tlxmi_linear_ln", dt_code(x.dtype), rows, prep.K, prep.Cout, prep.K, prep.Cout, _p(x), _p(prep.pk.buf), _p(prep.c1), _p(prep.c2),
-              _p(part), C.c_float(float(eps)), act, _p(y), plan_flags(), _stream())
-    if _probe is not None:
-        e1.record()
-        es = x.element_size()
-        _probe.append((e0, e1, (rows * prep.K + rows * prep.Cout + prep.Cout * prep.K) * es + part.numel() * 4,
-                       2 * rows * prep.Cout * prep.K, (rows, 1, 1, prep.K, prep.Cout, 1, 1, False)))
+    _timed(lambda: _lib.call("tlxmi_linear_ln", dt_code(x.dtype), rows, prep.K, prep.Cout, prep.K, prep.Cout, _p(x), _p(prep.pk.buf), _p(prep.c1),
+                             _p(prep.c2), _p(part), C.c_float(float(eps)), act, _p(y), plan_flags(), _stream()),
+           lambda: ((rows * prep.K + rows * prep.Cout + prep.Cout * prep.K) * x.element_size() + part.numel() * 4,
+                    2 * rows * prep.Cout * prep.K, (rows, 1, 1, prep.K, prep.Cout, 1, 1, False)))
     return y
 
 
@@ -1172,22 +1200,18 @@ def dwconv7_stats(x, w_rsc, bias=None, stats=True, fused=None):
     if fused is None:
         fused = dwconv7_supported(x)
     es = x.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * es)
-    part = None
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    if fused:
-        y = torch.empty_like(x)
-        if stats:
-            part = torch.empty((N * H * W, 4, 2), dtype=torch.float32, device=x.device)      # pair p < ceil(C / 256) written
+    y = torch.empty_like(x) if fused else None
+    part = torch.empty((N * H * W, 4, 2), dtype=torch.float32, device=x.device) if fused and stats else None      # pair p < ceil(C / 256) written
+
+    def launch():
+        if not fused:
+            return dwconv2d(x, w_rsc, 1, 3, 1, None, bias)
         _lib.call("tlxmi_dwconv7_stats", C.byref(_dwconv7_desc(x, Cc, Cc)), _p(x), _p(w_rsc), _p(bias), _p(y), _p(part), _stream())
-    else:
-        y = dwconv2d(x, w_rsc, 1, 3, 1, None, bias)
-    if _probe is not None:
-        e1.record()
-        _probe.append((e0, e1, 2 * x.numel() * es + 49 * Cc * es + (part.numel() * 4 if part is not None else 0), 2 * 49 * x.numel(),
-                       (N, H, W, Cc, Cc, 7, 1, "dwconv7" if fused else "dwconv2d")))
+        return y
+    y = _timed(launch, lambda: (2 * x.numel() * es + 49 * Cc * es + (part.numel() * 4 if part is not None else 0), 2 * 49 * x.numel(),
+                                (N, H, W, Cc, Cc, 7, 1, "dwconv7" if fused else "dwconv2d")))
     return y, part
 
 
@@ -1203,7 +1227,6 @@ def sepconv2d(x, w_dw, dw_scale, dw_shift, pk, pw_scale, pw_shift, dilation, act
     fp16, the conv is dilated and the library takes the shape; otherwise tlxmi_dwconv2d then tlxmi_conv2d (fp32 always: the
     parity reference).  Dilation 1 keeps the pair: there the depthwise runs on dwconv_strip_kernel, and the pair measured faster
     than the fused kernel at DeepLabV3+'s decoder shapes.  fused=True / False forces one form (tests, tools/)."""
-    global _probe
     need_gpu(x, "input")
     N, H, W, ld = x.shape
     R, S, Cc = w_dw.shape
@@ -1219,7 +1242,7 @@ def sepconv2d(x, w_dw, dw_scale, dw_shift, pk, pw_scale, pw_shift, dilation, act
         out_ld = out.shape[-1]
     es = x.element_size()
     M = N * H * W
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * es, M * Cc * es, M * out_ld * es)
     desc = _lib.SepConvDesc(dtype=dt_code(x.dtype), N=N, H=H, W=W, C=Cc, Cout=pk.Cout, R=3, S=3, stride_h=1, stride_w=1, pad_h=d,
                             pad_w=d, dil_h=d, dil_w=d, x_ld=ld, y_ld=out_ld, act=act, act_param=float(act_param))
@@ -1233,20 +1256,8 @@ def sepconv2d(x, w_dw, dw_scale, dw_shift, pk, pw_scale, pw_shift, dilation, act
         else:
             t = dwconv2d(x, w_dw, 1, d, d, dw_scale, dw_shift)
             _conv2d(t, pk, 1, 0, 1, pw_scale, pw_shift, act=act, act_param=act_param, out=out, out_ld=out_ld)
-    if _probe is None:
-        launch()
-        return out
-    probe, _probe = _probe, None      # the pair is one entry
-    try:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch()
-        e1.record()
-    finally:
-        _probe = probe
-    alg_bytes = (M * Cc + M * pk.Cout + 9 * Cc + pk.Cout * Cc) * es
-    flops = 2 * M * Cc * 9 + 2 * M * pk.Cout * Cc
-    probe.append((e0, e1, alg_bytes, flops, (N, H, W, Cc, pk.Cout, "sep", d, fused)))
+    _timed(launch, lambda: ((M * Cc + M * pk.Cout + 9 * Cc + pk.Cout * Cc) * es, 2 * M * Cc * 9 + 2 * M * pk.Cout * Cc,
+                            (N, H, W, Cc, pk.Cout, "sep", d, fused)))      # the pair is one entry
     return out
 
 
@@ -1257,7 +1268,6 @@ def preact_conv1x1(x, pre_scale, pre_shift, pk, scale=None, shift=None, act=ACT_
     written into `out` (a column slice of a wider buffer, pixel pitch out_ld).  One launch (tlxmi_preact_conv1x1) when the "preact"
     option is on, the precision is fp16 and the library takes the shape; otherwise tlxmi_affine_act into a dense K-channel temporary
     then tlxmi_conv2d (fp32 always: the parity reference).  fused=True / False forces one form (tests, tools/)."""
-    global _probe
     need_gpu(x, "input")
     if x.dim() == 2:
         x = x.view(x.shape[0], 1, 1, x.shape[1])
@@ -1275,7 +1285,7 @@ def preact_conv1x1(x, pre_scale, pre_shift, pk, scale=None, shift=None, act=ACT_
         out_ld = out.shape[-1]
     es = x.element_size()
     M = N * H * W
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * es, M * out_ld * es)
     if fused is None:
         fused = bool(_options["preact"] and x.dtype == torch.float16
@@ -1287,14 +1297,8 @@ def preact_conv1x1(x, pre_scale, pre_shift, pk, scale=None, shift=None, act=ACT_
         conv2d(t, pk, 1, 0, 1, scale, shift, act=act, out=out, out_ld=out_ld)
         return out
     args = (F16, M, K, pk.Cout, ld, out_ld, _p(x), _p(pre_scale), _p(pre_shift), pre_act, _p(pk.buf), _p(scale), _p(shift), act, _p(out), _stream())
-    if _probe is None:
-        _lib.call("tlxmi_preact_conv1x1", *args)
-        return out
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.call("tlxmi_preact_conv1x1", *args)
-    e1.record()
-    _probe.append((e0, e1, (M * K + M * pk.Cout + pk.Cout * K) * es, 2 * M * pk.Cout * K, (N, H, W, K, pk.Cout, "preact")))
+    _timed(lambda: _lib.call("tlxmi_preact_conv1x1", *args),
+           lambda: ((M * K + M * pk.Cout + pk.Cout * K) * es, 2 * M * pk.Cout * K, (N, H, W, K, pk.Cout, "preact")))
     return out
 
 
@@ -1353,22 +1357,18 @@ def lka_dw(t, w0, b0, w1, b1, fused=None):
     if fused is None:
         fused = lka_dw_supported(t, Cc)
     es = t.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(t.numel() * es)
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    if fused:
-        y = torch.empty((N, H, W, Cc), dtype=t.dtype, device=t.device)
-        _lib.call("tlxmi_lka_dw", C.byref(_lka_dw_desc(t, Cc, Cc)), _p(t), _p(w0), _p(b0), _p(w1), _p(b1), _p(y), _stream())
-    else:
+    M = N * H * W
+
+    def launch():
+        if fused:
+            y = torch.empty((N, H, W, Cc), dtype=t.dtype, device=t.device)
+            _lib.call("tlxmi_lka_dw", C.byref(_lka_dw_desc(t, Cc, Cc)), _p(t), _p(w0), _p(b0), _p(w1), _p(b1), _p(y), _stream())
+            return y
         y = dwconv2d(dwconv2d(t, w0, 1, 2, 1, None, b0), w1, 1, 9, 3, None, b1)
-        if ld != Cc:
-            y = y[..., :Cc].contiguous()
-    if _probe is not None:
-        e1.record()
-        M = N * H * W
-        _probe.append((e0, e1, (2 * M * Cc + 74 * Cc) * es, 2 * 74 * M * Cc, (N, H, W, Cc, Cc, "lka_dw" if fused else "dwconv2d x2")))
-    return y
+        return y if ld == Cc else y[..., :Cc].contiguous()
+    return _timed(launch, lambda: ((2 * M * Cc + 74 * Cc) * es, 2 * 74 * M * Cc, (N, H, W, Cc, Cc, "lka_dw" if fused else "dwconv2d x2")))
 
 
 def _lka_gate_desc(rows, Cc, dtype):
@@ -1390,7 +1390,6 @@ def lka_gate(a1, t, pk1, scale1, shift1, pk2, scale2, shift2, res, res_scale, fu
     or None (1 / 0) -> y of a1's shape.  One launch (tlxmi_lka_gate: both products on MFMA, g never in memory) when the "lka" option
     is on, the precision is fp16, the library takes the shape (C a multiple of 32 up to 256) and C <= LKA_GATE_MAX_C; otherwise
     tlxmi_conv2d -> tlxmi_mul -> tlxmi_affine_act -> tlxmi_conv2d (fp32 always: the parity reference).  fused=True / False forces one form (tests, tools/)."""
-    global _probe
     need_gpu(a1, "input")
     Cc = a1.shape[-1]
     rows = a1.numel() // Cc
@@ -1402,7 +1401,7 @@ def lka_gate(a1, t, pk1, scale1, shift1, pk2, scale2, shift2, res, res_scale, fu
     if fused is None:
         fused = lka_gate_supported(rows, Cc, a1.dtype)
     es = a1.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(a1.numel() * es)
 
     def launch():
@@ -1416,18 +1415,8 @@ def lka_gate(a1, t, pk1, scale1, shift1, pk2, scale2, shift2, res, res_scale, fu
         g = mul(v4(t), a2)
         r = affine_act(v4(res), res_scale) if res_scale is not None else v4(res)
         return conv2d(g, pk2, 1, 0, 1, scale2, shift2, res=r).view(a1.shape)
-    if _probe is None:
-        return launch()
-    probe, _probe = _probe, None      # the chain is one entry
-    try:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        y = launch()
-        e1.record()
-    finally:
-        _probe = probe
-    probe.append((e0, e1, (4 * rows * Cc + 2 * Cc * Cc) * es, 4 * rows * Cc * Cc, (rows, 1, 1, Cc, Cc, "lka_gate" if fused else "conv-mul-affine-conv")))
-    return y
+    return _timed(launch, lambda: ((4 * rows * Cc + 2 * Cc * Cc) * es, 4 * rows * Cc * Cc,
+                                   (rows, 1, 1, Cc, Cc, "lka_gate" if fused else "conv-mul-affine-conv")))      # the chain is one entry
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1445,21 +1434,10 @@ def shuffle_unit_pack(w1, s1, t1, wdw, s2, t2, w2, s3, t3):
     up to 32, fp16 w1[Kp][Kp], fp16 w2[Kp][Kp], fp16 wdw[9][Kp] (tap r * 3 + s), fp32 s1, t1, s2, t2, s3, t3 [Kp] each, everything
     beyond h zero.  w1, w2: (h, h, 1, 1) or (h, h) filters (out, in); wdw: (h, 1, 3, 3); the scales / shifts: fp32 [h] (folded BatchNorms)."""
     h = int(w1.shape[0])
-    kp = (h + 31) // 32 * 32
+    kp = _round_up(h, 32)
     dev = w1.device
-    img = []
-    for w in (w1, w2):
-        m = torch.zeros((kp, kp), dtype=torch.float16, device=dev)
-        m[:h, :h] = w.detach().reshape(h, h).to(torch.float16)
-        img.append(m)
-    d = torch.zeros((9, kp), dtype=torch.float16, device=dev)
-    d[:, :h] = wdw.detach().reshape(h, 9).t().to(torch.float16)
-    img.append(d)
-    aff = torch.zeros((6, kp), dtype=torch.float32, device=dev)
-    for i, v in enumerate((s1, t1, s2, t2, s3, t3)):
-        aff[i, :h] = v.detach().to(torch.float32)
-    img.append(aff)
-    return torch.cat([m.contiguous().view(torch.uint8).reshape(-1) for m in img])
+    return _param_image(_zero_padded((w1.reshape(h, h), w2.reshape(h, h)), (2, kp, kp), torch.float16, dev), _dw_rsc(wdw, kp, torch.float16, dev),
+                        _zero_padded((s1, t1, s2, t2, s3, t3), (6, kp), torch.float32, dev))
 
 
 class ShuffleUnitParams:
@@ -1470,15 +1448,11 @@ class ShuffleUnitParams:
     def __init__(self, w1, bn1, wdw, bn2, w2, bn3, dtype):
         self.h = h = int(w1.shape[0])
         self.dtype = dtype
-        v = vec(dtype)
-        self.hp = hp = (h + v - 1) // v * v
+        self.hp = hp = _round_up(h, vec(dtype))
         (self.s1, self.t1), (s2, t2), (self.s3, self.t3) = ((_f32(a), _f32(b)) for a, b in (bn1, bn2, bn3))
         self.pk1, self.pk2 = PackedFilter(w1, dtype), PackedFilter(w2, dtype)
-        dev = self.s1.device
-        self.wdw = torch.zeros((3, 3, hp), dtype=dtype, device=dev)
-        self.wdw[..., :h] = wdw.detach()[:, 0].permute(1, 2, 0).to(dtype)
-        self.s2, self.t2 = torch.zeros(hp, dtype=torch.float32, device=dev), torch.zeros(hp, dtype=torch.float32, device=dev)
-        self.s2[:h], self.t2[:h] = s2, t2
+        self.wdw = _dw_rsc(wdw, hp, dtype, self.s1.device)
+        self.s2, self.t2 = _zero_padded(s2, (hp,), torch.float32), _zero_padded(t2, (hp,), torch.float32)
         self.blob = None
         if dtype == torch.float16 and _lib.load().tlxmi_shuffle_unit_param_bytes(h):
             self.blob = shuffle_unit_pack(w1, self.s1, self.t1, wdw, s2, t2, w2, self.s3, self.t3)
@@ -1521,7 +1495,7 @@ def shuffle_concat(a, b, out=None, out_ld=None, cols=None):
     if out.dtype != a.dtype or out_ld < 2 * h:
         raise RuntimeError("shuffle_concat: out must have the operands' dtype and a pitch of at least twice their channels")
     es = a.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(a.numel() * es, b.numel() * es, rows * out_ld * es)
     _lib.call("tlxmi_shuffle_concat", _p(a), _p(b), _p(out), dt_code(a.dtype), rows, h, a.shape[-1], b.shape[-1], out_ld, _stream())
     return out
@@ -1536,27 +1510,21 @@ def shuffle_unit(x, params, act, fused=None, out=None):
     tlxmi_dwconv2d -> tlxmi_conv2d -> tlxmi_shuffle_concat (fp32 always: the parity reference), the branch half copied out first where
     it does not start on a 16-byte boundary.  fused=True / False forces one form (tests, tools/); True raises where the launch is not
     supported."""
-    global _probe
     need_gpu(x, "input")
     N, H, W, ld = x.shape
     h = params.h
     c = 2 * h
     if x.dtype != params.dtype or ld < c or not x.is_contiguous():
         raise RuntimeError(f"shuffle_unit: x must be a dense NHWC map of the parameters' dtype with at least {c} channels, got {tuple(x.shape)} {x.dtype}")
-    if out is None:
-        out = torch.empty((N, H, W, shuffle_pitch(c)), dtype=x.dtype, device=x.device)
-    y_ld = out.shape[-1]
-    if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, H, W) or y_ld < c or not out.is_contiguous():
-        raise RuntimeError("shuffle_unit: out must be a dense map of x's dtype and pixels with at least c channels")
+    out, y_ld = _out_map("shuffle_unit", out, N, H, W, c, x.dtype, x.device, shuffle_pitch(c),
+                         what="a dense map of x's dtype and pixels with at least c channels")
     desc = _shuffle_unit_desc(x, c, y_ld, act)
     takes = bool(x.dtype == torch.float16 and params.blob is not None and _lib.load().tlxmi_shuffle_unit_supported(C.byref(desc)))
-    if fused is None:
-        fused = takes and _options["shuffle_unit"]
-    elif fused and not takes:
-        raise RuntimeError(f"shuffle_unit: tlxmi_shuffle_unit does not take {tuple(x.shape)} {x.dtype} with h = {h}, act {act}, y_ld {y_ld}")
+    fused = _use_fused("shuffle_unit", fused, takes, takes and _options["shuffle_unit"],
+                       lambda: f"{tuple(x.shape)} {x.dtype} with h = {h}, act {act}, y_ld {y_ld}")
     es = x.element_size()
     M = N * H * W
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * es, M * y_ld * es)
 
     def launch():
@@ -1575,18 +1543,8 @@ def shuffle_unit(x, params, act, fused=None, out=None):
         f = torch.empty((N, H, W, hp), dtype=x.dtype, device=x.device)
         _conv2d(t, params.pk2, 1, 0, 1, params.s3, params.t3, act=act, out=f, out_ld=hp)
         shuffle_concat(x, f, out, y_ld, cols=h)
-    if _probe is None:
-        launch()
-        return out
-    probe, _probe = _probe, None      # the chain is one entry
-    try:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch()
-        e1.record()
-    finally:
-        _probe = probe
-    probe.append((e0, e1, (2 * M * c + 2 * h * h + 9 * h) * es, 2 * M * h * (2 * h + 9), (N, H, W, c, c, "shuffle_unit" if fused else "conv-dw-conv-shuffle")))
+    _timed(launch, lambda: ((2 * M * c + 2 * h * h + 9 * h) * es, 2 * M * h * (2 * h + 9),
+                            (N, H, W, c, c, "shuffle_unit" if fused else "conv-dw-conv-shuffle")))      # the chain is one entry
     return out
 
 
@@ -1599,16 +1557,10 @@ def ghost_module_pack(w1, s1, t1, wdw, s2, t2):
     everything beyond Cin / m zero.  w1: (m, Cin, 1, 1) or (m, Cin) (out, in); wdw: (m, 1, 3, 3); the scales / shifts: fp32 [m]
     (folded BatchNorms)."""
     m, cin = int(w1.shape[0]), int(w1.shape[1])
-    kp, mp = (cin + 31) // 32 * 32, (m + 15) // 16 * 16
+    kp, mp = _round_up(cin, 32), _round_up(m, 16)
     dev = w1.device
-    f = torch.zeros((mp, kp), dtype=torch.float16, device=dev)
-    f[:m, :cin] = w1.detach().reshape(m, cin).to(torch.float16)
-    d = torch.zeros((9, mp), dtype=torch.float16, device=dev)
-    d[:, :m] = wdw.detach().reshape(m, 9).t().to(torch.float16)
-    aff = torch.zeros((4, mp), dtype=torch.float32, device=dev)
-    for i, v in enumerate((s1, t1, s2, t2)):
-        aff[i, :m] = v.detach().to(torch.float32)
-    return torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in (f, d, aff)])
+    return _param_image(_zero_padded(w1.reshape(m, cin), (mp, kp), torch.float16), _dw_rsc(wdw, mp, torch.float16, dev),
+                        _zero_padded((s1, t1, s2, t2), (4, mp), torch.float32, dev))
 
 
 class GhostModuleParams:
@@ -1621,15 +1573,11 @@ class GhostModuleParams:
         self.m = m = int(w1.shape[0])
         self.cin = int(w1.shape[1])
         self.dtype = dtype
-        v = vec(dtype)
-        self.mp = mp = (m + v - 1) // v * v
+        self.mp = mp = _round_up(m, vec(dtype))
         (self.s1, self.t1), (s2, t2) = ((_f32(a), _f32(b)) for a, b in (bn1, bn2))
         self.pk1 = PackedFilter(w1, dtype)
-        dev = self.s1.device
-        self.wdw = torch.zeros((3, 3, mp), dtype=dtype, device=dev)
-        self.wdw[..., :m] = wdw.detach()[:, 0].permute(1, 2, 0).to(dtype)
-        self.s2, self.t2 = torch.zeros(mp, dtype=torch.float32, device=dev), torch.zeros(mp, dtype=torch.float32, device=dev)
-        self.s2[:m], self.t2[:m] = s2, t2
+        self.wdw = _dw_rsc(wdw, mp, dtype, self.s1.device)
+        self.s2, self.t2 = _zero_padded(s2, (mp,), torch.float32), _zero_padded(t2, (mp,), torch.float32)
         self.blob = None
         if dtype == torch.float16 and _lib.load().tlxmi_ghost_module_param_bytes(self.cin, m):
             self.blob = ghost_module_pack(w1, self.s1, self.t1, wdw, s2, t2)
@@ -1678,18 +1626,14 @@ def ghost_module(x, params, act, res=None, fused=None, out=None):
     from there into out[..., m:] (through a dense copy where m is no whole number of 16-byte chunks) -> tlxmi_affine_act for the
     shortcut (fp32 always: the parity reference; there the pitches are whole chunks and res has zero pad columns).  fused=True /
     False forces one form (tests, tools/); True raises where the launch is not supported."""
-    global _probe
     need_gpu(x, "input")
     N, H, W, ld = x.shape
     m, cin = params.m, params.cin
     c = 2 * m
     if x.dtype != params.dtype or ld < cin or not x.is_contiguous():
         raise RuntimeError(f"ghost_module: x must be a dense NHWC map of the parameters' dtype with at least {cin} channels, got {tuple(x.shape)} {x.dtype}")
-    if out is None:
-        out = torch.empty((N, H, W, shuffle_pitch(c)), dtype=x.dtype, device=x.device)
-    y_ld = out.shape[-1]
-    if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, H, W) or y_ld < c or not out.is_contiguous():
-        raise RuntimeError("ghost_module: out must be a dense map of x's dtype and pixels with at least 2 m channels")
+    out, y_ld = _out_map("ghost_module", out, N, H, W, c, x.dtype, x.device, shuffle_pitch(c),
+                         what="a dense map of x's dtype and pixels with at least 2 m channels")
     res_ld = 0
     if res is not None:
         res_ld = res.shape[-1]
@@ -1697,14 +1641,11 @@ def ghost_module(x, params, act, res=None, fused=None, out=None):
             raise RuntimeError("ghost_module: res must be a dense map of x's dtype and pixels with at least 2 m channels")
     desc = _ghost_module_desc(x, cin, m, y_ld, res_ld, act)
     takes = bool(x.dtype == torch.float16 and params.blob is not None and _lib.load().tlxmi_ghost_module_supported(C.byref(desc)))
-    if fused is None:
-        fused = takes and _options["ghost_module"] and _ghost_module_routed(H, W, cin, m)
-    elif fused and not takes:
-        raise RuntimeError(f"ghost_module: tlxmi_ghost_module does not take {tuple(x.shape)} {x.dtype} with Cin = {cin}, m = {m}, act {act}, "
-                           f"y_ld {y_ld}, res_ld {res_ld}")
+    fused = _use_fused("ghost_module", fused, takes, lambda: takes and _options["ghost_module"] and _ghost_module_routed(H, W, cin, m),
+                       lambda: f"{tuple(x.shape)} {x.dtype} with Cin = {cin}, m = {m}, act {act}, y_ld {y_ld}, res_ld {res_ld}")
     es = x.element_size()
     M = N * H * W
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * es, M * y_ld * es, M * res_ld * es)
 
     def launch():
@@ -1732,19 +1673,8 @@ def ghost_module(x, params, act, res=None, fused=None, out=None):
                 raise RuntimeError(f"ghost_module: layer by layer, the shortcut needs pitches that are whole 16-byte chunks (y_ld {y_ld}, res_ld {res_ld})")
             _lib.call("tlxmi_affine_act", _p(out), None, None, _p(res), _p(out), dt_code(x.dtype), M, cw, y_ld, res_ld, y_ld, ACT_NONE, 0.0, 0,
                       _stream())
-    if _probe is None:
-        launch()
-        return out
-    probe, _probe = _probe, None      # the chain is one entry
-    try:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch()
-        e1.record()
-    finally:
-        _probe = probe
-    probe.append((e0, e1, (M * (cin + c * (2 if res is not None else 1)) + m * cin + 9 * m) * es, 2 * M * m * (cin + 9),
-                  (N, H, W, cin, c, "ghost_module" if fused else "conv-dw-add")))
+    _timed(launch, lambda: ((M * (cin + c * (2 if res is not None else 1)) + m * cin + 9 * m) * es, 2 * M * m * (cin + 9),
+                            (N, H, W, cin, c, "ghost_module" if fused else "conv-dw-add")))      # the chain is one entry
     return out
 
 
@@ -1773,8 +1703,7 @@ def mixconv_dw_pack(filters, scale, shift, dtype):
         K = int(kc[8 * s:8 * s + 8].max())
         o = (kmax - K) // 2
         w[s, :K * K] = full[8 * s:8 * s + 8, o:o + K, o:o + K].reshape(8, K * K).t().to(dtype)
-    aff = torch.stack([scale.detach().to(torch.float32), shift.detach().to(torch.float32)])
-    return torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in (w, aff)])
+    return _param_image(w, torch.stack([scale.detach().to(torch.float32), shift.detach().to(torch.float32)]))
 
 
 class MixConvParams:
@@ -1794,12 +1723,9 @@ class MixConvParams:
         self.per_group = []
         a = 0
         for f, n, k in zip(filters, self.groups, self.kernels):
-            npad = (n + v - 1) // v * v
-            w = torch.zeros((k, k, npad), dtype=dtype, device=dev)
-            w[..., :n] = f.detach()[:, 0].permute(1, 2, 0).to(dtype)
-            s, t = torch.zeros(npad, dtype=torch.float32, device=dev), torch.zeros(npad, dtype=torch.float32, device=dev)
-            s[:n], t[:n] = self.scale[a:a + n], self.shift[a:a + n]
-            self.per_group.append((a, n, npad, w, s, t))
+            npad = _round_up(n, v)
+            s, t = _zero_padded(self.scale[a:a + n], (npad,), torch.float32), _zero_padded(self.shift[a:a + n], (npad,), torch.float32)
+            self.per_group.append((a, n, npad, _dw_rsc(f, npad, dtype, dev), s, t))
             a += n
         self.blob = None
         in_range = (self.C % 8 == 0 and 1 <= len(filters) <= 5 and all(3 <= k <= 11 and k % 2 for k in self.kernels)
@@ -1842,7 +1768,6 @@ def mixconv_dw(x, params, stride, act, pool=False, fused=None, out=None):
     the "mixconv" option is on and the library takes the shape (mixconv_dw_supported); otherwise one tlxmi_dwconv2d a group — on the
     column slice where it starts and ends on 16-byte chunks, through a dense zero-padded copy of the slice otherwise — and
     tlxmi_global_avgpool.  fused=True / False forces one form (tests, tools/); True raises where the launch is not supported."""
-    global _probe
     need_gpu(x, "input")
     N, H, W, ld = x.shape
     Cc = params.C
@@ -1855,20 +1780,14 @@ def mixconv_dw(x, params, stride, act, pool=False, fused=None, out=None):
         raise RuntimeError(f"mixconv_dw: windows {params.kernels} at pad (k - 1) // 2 do not give one output extent on {H} x {W}")
     k0 = params.kernels[0]
     Ho, Wo = (H + 2 * ((k0 - 1) // 2) - k0) // stride + 1, (W + 2 * ((k0 - 1) // 2) - k0) // stride + 1
-    if out is None:
-        out = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
-    y_ld = out.shape[-1]
-    if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, Ho, Wo) or y_ld < Cc or not out.is_contiguous():
-        raise RuntimeError(f"mixconv_dw: out must be a dense ({N}, {Ho}, {Wo}, >= {Cc}) map of x's dtype")
+    out, y_ld = _out_map("mixconv_dw", out, N, Ho, Wo, Cc, x.dtype, x.device, Cc, what=f"a dense ({N}, {Ho}, {Wo}, >= {Cc}) map of x's dtype")
     desc = _mixconv_desc(x.dtype, N, H, W, Cc, params.groups, params.kernels, stride, ld, y_ld, Cc, act)
     takes = bool(params.blob is not None and _lib.load().tlxmi_mixconv_dw_supported(C.byref(desc), 1 if pool else 0))
-    if fused is None:
-        fused = takes and _options["mixconv"]
-    elif fused and not takes:
-        raise RuntimeError(f"mixconv_dw: tlxmi_mixconv_dw does not take {tuple(x.shape)} {x.dtype} with groups {params.groups}, windows "
-                           f"{params.kernels}, stride {stride}, act {act}, y_ld {y_ld}, pool {pool}")
+    fused = _use_fused("mixconv_dw", fused, takes, takes and _options["mixconv"],
+                       lambda: f"{tuple(x.shape)} {x.dtype} with groups {params.groups}, windows {params.kernels}, stride {stride}, act {act}, "
+                               f"y_ld {y_ld}, pool {pool}")
     es = x.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * es, out.numel() * es)
     pooled = torch.empty((N, Cc), dtype=x.dtype, device=x.device) if pool else None
 
@@ -1891,20 +1810,11 @@ def mixconv_dw(x, params, stride, act, pool=False, fused=None, out=None):
             wide = torch.zeros((N, Ho, Wo, cp), dtype=x.dtype, device=x.device)
             wide[..., :Cc] = out[..., :Cc]
             pooled.copy_(global_avgpool(wide)[:, :Cc])
-    if _probe is None:
-        launch()
-        return (out, pooled) if pool else out
-    probe, _probe = _probe, None      # the chain is one entry
-    try:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch()
-        e1.record()
-    finally:
-        _probe = probe
-    taps = sum(n * k * k for n, k in zip(params.groups, params.kernels))
-    probe.append((e0, e1, (N * H * W * Cc + N * Ho * Wo * Cc + taps) * es, 2 * N * Ho * Wo * taps,
-                  (N, H, W, Cc, Cc, "mixconv_dw" if fused else "dw-per-group")))
+
+    def entry():
+        taps = sum(n * k * k for n, k in zip(params.groups, params.kernels))
+        return (N * H * W * Cc + N * Ho * Wo * Cc + taps) * es, 2 * N * Ho * Wo * taps, (N, H, W, Cc, Cc, "mixconv_dw" if fused else "dw-per-group")
+    _timed(launch, entry)      # the chain is one entry
     return (out, pooled) if pool else out
 
 
@@ -1917,13 +1827,10 @@ def res2_chain_pack(filters, bns, w):
     up to 32: fp16 filt[nc][9][np][kp] (tap r * 3 + s, row = output channel, column = input channel, zero padded), then fp32
     scale[nc][np], shift[nc][np]."""
     nc, dev = len(filters), filters[0].device
-    np_, kp = (w + 15) // 16 * 16, (w + 31) // 32 * 32
-    f = torch.zeros((nc, 9, np_, kp), dtype=torch.float16, device=dev)
-    aff = torch.zeros((2, nc, np_), dtype=torch.float32, device=dev)
-    for j, (wt, (sc, sh)) in enumerate(zip(filters, bns)):
-        f[j, :, :w, :w] = wt.detach().to(torch.float32).permute(2, 3, 0, 1).reshape(9, w, w).to(torch.float16)
-        aff[0, j, :w], aff[1, j, :w] = sc.detach().to(torch.float32), sh.detach().to(torch.float32)
-    return torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in (f, aff)])
+    np_, kp = _round_up(w, 16), _round_up(w, 32)
+    taps = [wt.detach().to(torch.float32).permute(2, 3, 0, 1).reshape(9, w, w) for wt in filters]
+    return _param_image(_zero_padded(taps, (nc, 9, np_, kp), torch.float16, dev),
+                        _zero_padded([sc for sc, _ in bns] + [sh for _, sh in bns], (2 * nc, np_), torch.float32, dev))
 
 
 class Res2ChainParams:
@@ -1941,11 +1848,8 @@ class Res2ChainParams:
         dev = filters[0].device
         self.per_conv = []
         for wt, (sc, sh) in zip(filters, bns):
-            full = torch.zeros((wp, wp, 3, 3), dtype=torch.float32, device=dev)
-            full[:w, :w] = wt.detach().to(torch.float32)
-            s, t = torch.zeros(wp, dtype=torch.float32, device=dev), torch.zeros(wp, dtype=torch.float32, device=dev)
-            s[:w], t[:w] = _f32(sc), _f32(sh)
-            self.per_conv.append((PackedFilter(full, dtype), s, t))
+            full = _zero_padded(wt, (wp, wp, 3, 3), torch.float32, dev)
+            self.per_conv.append((PackedFilter(full, dtype), _zero_padded(_f32(sc), (wp,), torch.float32, dev), _zero_padded(_f32(sh), (wp,), torch.float32, dev)))
         self.blob = None
         d = _res2_chain_desc(dtype, 1, 1, 1, self.w, self.wp, self.scales, self.scales * self.wp, self.scales * self.wp, ACT_NONE) \
             if dtype == torch.float16 else None
@@ -1995,25 +1899,20 @@ def res2_chain(x, params, act, fused=None, out=None):
     res (the add) into a dense scratch slice, tlxmi_conv2d ... and tlxmi_copy_channels for the last slice.  The layered arm reads the
     pad columns of x through zero filter columns, so they must be finite there (the reduce conv of the model writes zeros).
     fused=True / False forces one form (tests, tools/); True raises where the launch is not supported."""
-    global _probe
     need_gpu(x, "input")
     N, H, W, ld = x.shape
     w, wp, S = params.w, params.wp, params.scales
     if x.dtype != params.dtype or ld < S * wp or ld % 8 or not x.is_contiguous():
         raise RuntimeError(f"res2_chain: x must be a dense NHWC map of the parameters' dtype with at least {S * wp} channels at a pitch that "
                            f"is a multiple of 8, got {tuple(x.shape)} {x.dtype}")
-    if out is None:
-        out = torch.empty((N, H, W, S * wp), dtype=x.dtype, device=x.device)
-    y_ld = out.shape[-1]
-    if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, H, W) or y_ld < S * wp or y_ld % 8 or not out.is_contiguous():
-        raise RuntimeError(f"res2_chain: out must be a dense ({N}, {H}, {W}, >= {S * wp}) map of x's dtype at a pitch that is a multiple of 8")
-    if fused is None:       # the option and the table first: the library's predicate is asked only where they keep the launch
-        fused = bool(_options["res2chain"] and params.blob is not None and _res2_chain_routed(H, W, w, S)
-                     and res2_chain_takes(x, w, wp, S, act, y_ld))
-    elif fused and not (params.blob is not None and res2_chain_takes(x, w, wp, S, act, y_ld)):
-        raise RuntimeError(f"res2_chain: tlxmi_res2_chain does not take {tuple(x.shape)} {x.dtype} with w {w}, wp {wp}, scales {S}, act {act}, y_ld {y_ld}")
+    out, y_ld = _out_map("res2_chain", out, N, H, W, S * wp, x.dtype, x.device, S * wp, multiple=8,
+                         what=f"a dense ({N}, {H}, {W}, >= {S * wp}) map of x's dtype at a pitch that is a multiple of 8")
+    takes = lambda: params.blob is not None and res2_chain_takes(x, w, wp, S, act, y_ld)      # noqa: E731
+    # the option and the table first: the library's predicate is asked only where they keep the launch
+    fused = _use_fused("res2_chain", fused, takes, lambda: _options["res2chain"] and _res2_chain_routed(H, W, w, S) and takes(),
+                       lambda: f"{tuple(x.shape)} {x.dtype} with w {w}, wp {wp}, scales {S}, act {act}, y_ld {y_ld}")
     es = x.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * es, out.numel() * es)
 
     def launch():
@@ -2032,19 +1931,8 @@ def res2_chain(x, params, act, fused=None, out=None):
                           dt, rows, wp, ld, y_ld, wp, ACT_NONE, 0.0, 0, _stream())
                 conv2d(scratch, pk, 1, 1, 1, s, t, act=act, out=dst, out_ld=y_ld)
         _lib.call("tlxmi_copy_channels", _p(x[..., (S - 1) * wp:S * wp]), _p(out[..., (S - 1) * wp:S * wp]), dt, rows, wp, ld, y_ld, _stream())
-    if _probe is None:
-        launch()
-        return out
-    probe, _probe = _probe, None      # the chain is one entry
-    try:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch()
-        e1.record()
-    finally:
-        _probe = probe
-    probe.append((e0, e1, (2 * N * H * W * S * w + (S - 1) * 9 * w * w) * es, 2 * N * H * W * (S - 1) * 9 * w * w,
-                  (N, H, W, S * w, S * w, "res2_chain" if fused else "conv-add-conv-copy")))
+    _timed(launch, lambda: ((2 * N * H * W * S * w + (S - 1) * 9 * w * w) * es, 2 * N * H * W * (S - 1) * 9 * w * w,
+                            (N, H, W, S * w, S * w, "res2_chain" if fused else "conv-add-conv-copy")))      # the chain is one entry
     return out
 
 
@@ -2329,7 +2217,7 @@ def sr_attention(q, kv, heads, scale, fused=None):
     k, v = kv[..., :Cc], kv[..., Cc:]
     out = torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device)
     es = q.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(B * Lq * Cc * es, kv.numel() * es)
     d = _lib.MhaDesc(dtype=dt_code(q.dtype), B=B, Lq=Lq, Lk=Lk, heads=heads, hd=Cc // heads, scale=float(scale), mask_mode=0,
                      q_batch_stride=q.stride(0), q_row_stride=q.stride(1), k_batch_stride=k.stride(0), k_row_stride=k.stride(1),
@@ -2337,16 +2225,13 @@ def sr_attention(q, kv, heads, scale, fused=None):
     if fused is None:
         fused = bool(_options["sr_attn"] and q.dtype == torch.float16 and _lib.load().tlxmi_sr_attention_supported(C.byref(d))
                      and all(t.data_ptr() % 16 == 0 for t in (q, k, v, out)))
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    if fused:
-        _lib.call("tlxmi_sr_attention", C.byref(d), _p(q), _p(k), _p(v), _p(out), _stream())
-    else:
-        _lib.call("tlxmi_mha", C.byref(d), _p(q), _p(k), _p(v), None, _p(out), None, _stream())
-    if _probe is not None:
-        e1.record()
-        _probe.append((e0, e1, (2 * B * Lq * Cc + 2 * B * Lk * Cc) * es, 4 * B * Lq * Lk * Cc,
-                       (B, Lq, Lk, heads, Cc // heads, "sr_attn" if fused else "mha")))
+
+    def launch():
+        if fused:
+            _lib.call("tlxmi_sr_attention", C.byref(d), _p(q), _p(k), _p(v), _p(out), _stream())
+        else:
+            _lib.call("tlxmi_mha", C.byref(d), _p(q), _p(k), _p(v), None, _p(out), None, _stream())
+    _timed(launch, lambda: ((2 * B * Lq * Cc + 2 * B * Lk * Cc) * es, 4 * B * Lq * Lk * Cc, (B, Lq, Lk, heads, Cc // heads, "sr_attn" if fused else "mha")))
     return out
 
 
@@ -2452,7 +2337,7 @@ def gsa_block(x, packed, kv, heads, scale, eps, fused=None, out=None):
     if tuple(y.shape) != tuple(x.shape) or y.dtype != x.dtype or y.stride(-1) != 1:
         raise RuntimeError("gsa_block: out must have x's shape and dtype and a dense feature axis")
     es = x.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(B * Lq * Cc * es, kv.numel() * es)
     k, v = kv[..., :Cc], kv[..., Cc:]
     d = _gsa_desc(x, kv, y, heads, scale, eps)
@@ -2461,13 +2346,9 @@ def gsa_block(x, packed, kv, heads, scale, eps, fused=None, out=None):
     if fused:
         if packed.block is None or packed.block.device != x.device:
             raise RuntimeError(f"gsa_block: no packed parameter block for C = {Cc} on {x.device}")
-        if _probe is not None:
-            e0, e1 = _probe_pair()
-        _lib.call("tlxmi_gsa_block", C.byref(d), _p(x), _p(k), _p(v), _p(packed.block), _p(y), _stream())
-        if _probe is not None:
-            e1.record()
-            _probe.append((e0, e1, (2 * B * Lq * Cc + 2 * B * Lk * Cc) * es + packed.block.numel() * 2,
-                           4 * B * Lq * Cc * Cc + 4 * B * Lq * Lk * Cc, (B, Lq, Lk, heads, Cc // heads, "gsa_block")))
+        _timed(lambda: _lib.call("tlxmi_gsa_block", C.byref(d), _p(x), _p(k), _p(v), _p(packed.block), _p(y), _stream()),
+               lambda: ((2 * B * Lq * Cc + 2 * B * Lk * Cc) * es + packed.block.numel() * 2, 4 * B * Lq * Cc * Cc + 4 * B * Lq * Lk * Cc,
+                        (B, Lq, Lk, heads, Cc // heads, "gsa_block")))
         return y
     pkq, pkp = packed.linears(x.dtype)
     xc = x if x.is_contiguous() else x.contiguous()
@@ -2527,22 +2408,20 @@ def cswin_attention(qkv, B, H, W, heads, splits, w_lepe, b_lepe, scale, fused=No
     q, k, v = qkv[..., :Cc], qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:]
     out = torch.empty((B, H * W, Cc), dtype=qkv.dtype, device=qkv.device)
     es = qkv.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(out.numel() * es, qkv.numel() * es)
     hd = Cc // heads
     d = _cswin_desc(qkv.dtype, B, H, W, heads, hd, stripes, scale, q, k, v, out)
     if fused is None:
         fused = bool(_options["cswin_attn"] and qkv.dtype == torch.float16 and _lib.load().tlxmi_cswin_attention_supported(C.byref(d))
                      and all(t.data_ptr() % 16 == 0 for t in (q, k, v, out, w_lepe) + ((b_lepe,) if b_lepe is not None else ())))
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    _lib.call("tlxmi_cswin_attention" if fused else "tlxmi_cswin_attention_plain", C.byref(d), _p(q), _p(k), _p(v), _p(w_lepe), _p(b_lepe),
-              _p(out), _stream())
-    if _probe is not None:
-        e1.record()
+
+    def entry():
         keys = sum(hs * ws for hs, ws in stripes) / nb                  # keys a query meets, averaged over the branches
-        _probe.append((e0, e1, 4 * B * H * W * Cc * es + w_lepe.numel() * es, int(4 * B * H * W * keys * Cc) + 18 * B * H * W * Cc,
-                       (B, H, W, heads, hd, tuple(stripes), "cswin_attn" if fused else "cswin_plain")))
+        return (4 * B * H * W * Cc * es + w_lepe.numel() * es, int(4 * B * H * W * keys * Cc) + 18 * B * H * W * Cc,
+                (B, H, W, heads, hd, tuple(stripes), "cswin_attn" if fused else "cswin_plain"))
+    _timed(lambda: _lib.call("tlxmi_cswin_attention" if fused else "tlxmi_cswin_attention_plain", C.byref(d), _p(q), _p(k), _p(v), _p(w_lepe),
+                             _p(b_lepe), _p(out), _stream()), entry)
     return out
 
 
@@ -2617,21 +2496,17 @@ def levit_attention(kv, bias_grid, heads, kd, d, Rk, scale, q=None, Rq=None, str
         raise RuntimeError("levit_attention: act is ACT_NONE or ACT_HARDSWISH")
     out = torch.empty((B, Rq * Rq, heads * d), dtype=kv.dtype, device=kv.device)
     es = kv.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(out.numel() * es, kv.numel() * es)
     dsc = _levit_desc(kv.dtype, B, heads, kd, d, Rq, Rk, stride, scale, act, qv, kview, vview, out, q_hs, per, per)
     if fused is None:
         fused = bool(_options["levit_attn"] and kv.dtype == torch.float16 and _lib.load().tlxmi_levit_attention_supported(C.byref(dsc))
                      and all(t.data_ptr() % 16 == 0 for t in (qv, kview, vview, out, bias_grid)))
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    _lib.call("tlxmi_levit_attention" if fused else "tlxmi_levit_attention_plain", C.byref(dsc), _p(qv), _p(kview), _p(vview), _p(bias_grid),
-              _p(out), _stream())
-    if _probe is not None:
-        e1.record()
-        Lq, Lk = Rq * Rq, Rk * Rk
-        _probe.append((e0, e1, B * heads * (Lq * kd + Lk * (kd + d) + Lq * d) * es + heads * Lk * 4, 2 * B * heads * Lq * Lk * (kd + d),
-                       (B, Rq, Rk, stride, heads, kd, d, "levit_attn" if fused else "levit_plain")))
+    Lq, Lk = Rq * Rq, Rk * Rk
+    _timed(lambda: _lib.call("tlxmi_levit_attention" if fused else "tlxmi_levit_attention_plain", C.byref(dsc), _p(qv), _p(kview), _p(vview),
+                             _p(bias_grid), _p(out), _stream()),
+           lambda: (B * heads * (Lq * kd + Lk * (kd + d) + Lq * d) * es + heads * Lk * 4, 2 * B * heads * Lq * Lk * (kd + d),
+                    (B, Rq, Rk, stride, heads, kd, d, "levit_attn" if fused else "levit_plain")))
     return out
 
 
@@ -2692,21 +2567,16 @@ def tnt_inner(x, packed, heads, eps_in=1e-5, eps_mlp=1e-5, eps_proj=1e-5, y_norm
         raise RuntimeError("tnt_inner: out must have x's shape and dtype, a dense channel axis and evenly spaced rows")
     yn = torch.empty((patches, pixels * D), dtype=x.dtype, device=x.device) if y_norm else None
     es = x.element_size()
-    if getattr(_tls, "act_max", None) is not None:
+    if _sizing():
         _note_act(x.numel() * es)
     dsc = _tnt_desc(x.dtype, patches, pixels, D, heads, hidden, (eps_in, eps_mlp, eps_proj), x.stride(1), y.stride(1), pixels * D)
     if fused is None:
         fused = bool(_options["tnt_inner"] and x.dtype == torch.float16 and _lib.load().tlxmi_tnt_inner_supported(C.byref(dsc))
                      and all(t_.data_ptr() % 16 == 0 for t_ in (x, y, packed) + ((yn,) if yn is not None else ())))
-    if _probe is not None:
-        e0, e1 = _probe_pair()
-    _lib.call("tlxmi_tnt_inner" if fused else "tlxmi_tnt_inner_plain", C.byref(dsc), _p(x), _p(packed), _p(y), _p(yn), _stream())
-    if _probe is not None:
-        e1.record()
-        hd = D // heads
-        flops = 2 * patches * pixels * (4 * D * D + 2 * D * hidden + 2 * heads * pixels * hd)
-        _probe.append((e0, e1, patches * pixels * D * es * (3 if y_norm else 2) + packed.numel() * 4, flops,
-                       (patches, pixels, D, heads, "tnt_inner" if fused else "tnt_plain")))
+    _timed(lambda: _lib.call("tlxmi_tnt_inner" if fused else "tlxmi_tnt_inner_plain", C.byref(dsc), _p(x), _p(packed), _p(y), _p(yn), _stream()),
+           lambda: (patches * pixels * D * es * (3 if y_norm else 2) + packed.numel() * 4,
+                    2 * patches * pixels * (4 * D * D + 2 * D * hidden + 2 * heads * pixels * (D // heads)),
+                    (patches, pixels, D, heads, "tnt_inner" if fused else "tnt_plain")))
     return y, yn
 
 

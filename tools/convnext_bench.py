@@ -10,23 +10,13 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
-from tlxcv_amd import engine as E, seeded, models  # noqa: E402
-from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tlxcv_amd import engine as E, models  # noqa: E402
+from tools.ab import model_on_off, timed  # noqa: E402
 
 COPY_TBS = 4.75          # profiles/r01/roofline_denominators.txt: copy 1 GiB -> 1 GiB, read + write
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
 
 
 def kernels():
@@ -74,27 +64,7 @@ def kernels():
 
 
 def model():
-    m = models.convnext()
-    m.load_dict(seeded.fill(seeded.shapes_of(m), 1))
-    m = m.to(dev).set_eval()
-    x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-    graphs = {}
-    for on in (True, False):
-        E.set_option("dwconv7", on)
-        with torch.no_grad():
-            graphs[on] = GraphedForward(m, x)
-    E.set_option("dwconv7", True)
-    t = {True: [], False: []}
-    for _ in range(reps):
-        for on in (True, False):
-            t[on].append(timed(lambda: graphs[on](), 20))
-    print(f"# ConvNeXt-T batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 20 forwards (min..max)")
-    for on in (True, False):
-        v = sorted(t[on])
-        med = v[len(v) // 2]
-        print(f"dwconv7 {'on ' if on else 'off'}: {med / 1e3:7.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-    d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-    print(f"max|logit difference| on vs off: {d:.3e}")
+    model_on_off("dwconv7", [("ConvNeXt-T", models.convnext, 1)], batch, reps, forwards=20, ms_width=7)
 
 
 if __name__ == "__main__":

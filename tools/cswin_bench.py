@@ -17,47 +17,13 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
-from tlxcv_amd import engine as E, seeded, models  # noqa: E402
-from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tlxcv_amd import engine as E, models  # noqa: E402
+from tools.ab import ab, model_on_off  # noqa: E402
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 STAGES = ((1, 56, 2, 1), (2, 28, 4, 2), (3, 14, 8, 7), (4, 7, 16, None))      # (stage, H = W, heads, split; None = one branch, the whole map)
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: (fn, calls per graph, replays per round)} -> {name: (median us per call, min, max)}, alternated; and the last outputs."""
-    graphs, outs = {}, {}
-    for k, (f, calls, _) in arms.items():
-        for _ in range(2):
-            outs[k] = f()
-        torch.cuda.synchronize()
-        graphs[k] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[k]):
-            for _ in range(calls):
-                f()
-        graphs[k].replay()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k, (_, calls, replays) in arms.items():
-            t[k].append(timed(graphs[k].replay, replays) / calls)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res, outs
 
 
 def stages():
@@ -71,7 +37,9 @@ def stages():
             w = (torch.randn(3, 3, Cc, generator=g) / 3).half().to(dev)
             bias = (torch.randn(Cc, generator=g) * 0.1).to(dev)
             run = lambda fused: E.cswin_attention(qkv, b, hw, hw, heads, splits, w, bias, 32 ** -0.5, fused=fused)      # noqa: E731
-            res, outs = ab({"mfma": (lambda: run(True), 10, 5), "plain": (lambda: run(False), 2, 2)})
+            arms = {"mfma": (lambda: run(True), 10, 5), "plain": (lambda: run(False), 2, 2)}
+            outs = {k: f() for k, (f, _, _) in arms.items()}
+            res = ab(arms, reps)
             tokens = E.cswin_stripes(hw, hw, splits)[0][0] * E.cswin_stripes(hw, hw, splits)[0][1]
             nbytes = 4 * b * hw * hw * Cc * 2
             for k, (med, lo, hi) in res.items():
@@ -87,28 +55,7 @@ def stages():
 
 
 def model():
-    m = models.CSwintransformer_thiny()
-    m.load_dict(seeded.fill(seeded.shapes_of(m), 16))
-    m = m.to(dev).set_eval()
-    x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-    graphs = {}
-    for on in (True, False):
-        E.set_option("cswin_attn", on)
-        with torch.no_grad():
-            graphs[on] = GraphedForward(m, x)
-    E.set_option("cswin_attn", True)
-    iters = {True: 10, False: 2}
-    t = {True: [], False: []}
-    for _ in range(reps):
-        for on in (True, False):
-            t[on].append(timed(lambda: graphs[on](), iters[on]))
-    print(f"# CSWin-tiny batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 10 (on) / 2 (off) forwards (min..max)")
-    for on in (True, False):
-        v = sorted(t[on])
-        med = v[len(v) // 2]
-        print(f"cswin_attn {'on ' if on else 'off'}: {med / 1e3:8.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-    d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-    print(f"max|logit difference| on vs off: {d:.3e}")
+    model_on_off("cswin_attn", [("CSWin-tiny", models.CSwintransformer_thiny, 16)], batch, reps, forwards=(10, 2))
 
 
 if __name__ == "__main__":

@@ -19,8 +19,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
-from tlxcv_amd import engine as E, seeded, models  # noqa: E402
-from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tlxcv_amd import engine as E, models  # noqa: E402
+from tools.ab import ab, copy_floor, model_on_off  # noqa: E402
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
@@ -38,40 +38,6 @@ def module_shapes(name):
             hw //= 2
         out.setdefault((hw, g2.in_channels, g2.out_channels // 2, True), []).append(f"{i}.2")
     return out
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: (fn, calls per graph, replays per round)} -> {name: (median us per call, min, max)}."""
-    graphs = {}
-    for k, (f, calls, _) in arms.items():
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        graphs[k] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[k]):
-            for _ in range(calls):
-                f()
-        graphs[k].replay()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k, (_, calls, replays) in arms.items():
-            t[k].append(timed(graphs[k].replay, replays) / calls)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res
 
 
 def module():
@@ -101,12 +67,10 @@ def module():
             del y_f, y_l
             calls = 10 if hw <= 56 else 4
             out = ab({"fused": (lambda: E.ghost_module(x, params, act, res=res, fused=True, out=y), calls, 5),
-                      "layers": (lambda: E.ghost_module(x, params, act, res=res, fused=False, out=y), calls, 5)})
+                      "layers": (lambda: E.ghost_module(x, params, act, res=res, fused=False, out=y), calls, 5)}, reps)
             nbytes = batch * hw * hw * (cin + 2 * m * (2 if second else 1)) * 2
             nbytes -= nbytes % 32
-            src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-            dst = torch.empty_like(src)
-            copy = ab({"copy": (lambda: dst.copy_(src), calls, 5)})["copy"]
+            copy = copy_floor(nbytes, calls, reps)
             bw = nbytes / copy[0] / 1e3                                             # GB/s: nbytes / 2 read + nbytes / 2 written
             print(f"## {name[9:]} {'ghost_module_2' if second else 'ghost_module_1'} of blocks {', '.join(b[:-2] for b in blocks)}: ({batch}, {hw}, {hw}), "
                   f"Cin = {cin}, m = {m}{', + shortcut' if second else ', ReLU'}")
@@ -118,33 +82,11 @@ def module():
             print(f"max|fused - layers| on the seeded maps: {d:.3e}; fused / layers = {out['fused'][0] / out['layers'][0]:.4f}: "
                   f"{'the fused arm is faster beyond the spread' if keeps else 'NOT faster beyond the spread: route this shape to the layers'}; "
                   f"the engine's default route here: {'fused' if routed else 'layers'}", flush=True)
-            del x, res, y, src, dst
+            del x, res, y
 
 
 def model():
-    for name, seed in (("ghostnet_x0_5", 32), ("ghostnet_x1_0", 31)):
-        m = getattr(models, name)()
-        m.load_dict(seeded.fill(seeded.shapes_of(m), seed))
-        m = m.to(dev).set_eval()
-        x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-        graphs = {}
-        for on in (True, False):
-            E.set_option("ghost_module", on)
-            with torch.no_grad():
-                graphs[on] = GraphedForward(m, x)
-        E.set_option("ghost_module", True)
-        t = {True: [], False: []}
-        for _ in range(reps):
-            for on in (True, False):
-                t[on].append(timed(lambda: graphs[on](), 5))
-        print(f"# {name} batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 5 forwards (min..max)")
-        for on in (True, False):
-            v = sorted(t[on])
-            med = v[len(v) // 2]
-            print(f"ghost_module {'on ' if on else 'off'}: {med / 1e3:8.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-        d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-        print(f"max|logit difference| on vs off: {d:.3e}")
-        del graphs, m
+    model_on_off("ghost_module", [(n, getattr(models, n), s) for n, s in (("ghostnet_x0_5", 32), ("ghostnet_x1_0", 31))], batch, reps)
 
 
 if __name__ == "__main__":

@@ -21,8 +21,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
-from tlxcv_amd import _lib, engine as E, seeded, models  # noqa: E402
-from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tlxcv_amd import engine as E, models  # noqa: E402
+from tools.ab import ab, copy_floor, model_on_off  # noqa: E402
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
@@ -30,46 +30,6 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 
 SHAPES = [("alt_gvt_small stage 1", 3136, 64, 2), ("alt_gvt_small stage 2", 784, 128, 4), ("pcpvt_small stage 1", 3136, 64, 1),
           ("pcpvt_small stage 2", 784, 128, 2)]
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: (fn, calls per graph, replays per round, env of the tuning flavour or None)} -> {name: (median us per call, min, max)}."""
-    graphs = {}
-    for k, (f, calls, _, env) in arms.items():
-        def capture():
-            for _ in range(2):
-                f()
-            torch.cuda.synchronize()
-            graphs[k] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graphs[k]):
-                for _ in range(calls):
-                    f()
-            graphs[k].replay()
-        if env is None:
-            capture()
-        else:
-            with _lib.tuning(**env):
-                capture()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k, (_, calls, replays, _) in arms.items():
-            t[k].append(timed(graphs[k].replay, replays) / calls)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res
 
 
 class _Layer:
@@ -103,12 +63,10 @@ def kernel():
             E.linear(o, pkp, packed.bp, res=x, out=x)
 
         fused = lambda: E.gsa_block(x, packed, kv, heads, scale, eps, fused=True, out=x)      # noqa: E731
-        res = ab({"fused": (fused, 10, 5, None), "fused_l2": (fused, 10, 5, {"TLXMI_GSA_WLDS": "0"}), "layers": (layers, 10, 5, None)})
+        res = ab({"fused": (fused, 10, 5, None), "fused_l2": (fused, 10, 5, {"TLXMI_GSA_WLDS": "0"}), "layers": (layers, 10, 5, None)}, reps)
         assert torch.isfinite(x).all()
         nbytes = (2 * batch * Lq * Cc + batch * 49 * 2 * Cc) * 2 + packed.block.numel() * 2
-        src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-        dst = torch.empty_like(src)
-        copy = ab({"copy": (lambda: dst.copy_(src), 10, 5, None)})["copy"]
+        copy = copy_floor(nbytes, 10, reps)
         bw = nbytes / copy[0] / 1e3                                             # GB/s: nbytes / 2 read + nbytes / 2 written
         print(f"## {name}: ({batch}, {Lq}, 49, {Cc}, {heads} heads)")
         for k, (med, lo, hi) in res.items():
@@ -122,29 +80,7 @@ def kernel():
 
 
 def model():
-    for name, seed in (("alt_gvt_small", 17), ("pcpvt_small", 17)):
-        m = getattr(models, name)()
-        m.load_dict(seeded.fill(seeded.shapes_of(m), seed))
-        m = m.to(dev).set_eval()
-        x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-        graphs = {}
-        for on in (True, False):
-            E.set_option("gsa_block", on)
-            with torch.no_grad():
-                graphs[on] = GraphedForward(m, x)
-        E.set_option("gsa_block", True)
-        t = {True: [], False: []}
-        for _ in range(reps):
-            for on in (True, False):
-                t[on].append(timed(lambda: graphs[on](), 5))
-        print(f"# {name} batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 5 forwards (min..max)")
-        for on in (True, False):
-            v = sorted(t[on])
-            med = v[len(v) // 2]
-            print(f"gsa_block {'on ' if on else 'off'}: {med / 1e3:8.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-        d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-        print(f"max|logit difference| on vs off: {d:.3e}")
-        del graphs, m
+    model_on_off("gsa_block", [(n, getattr(models, n), s) for n, s in (("alt_gvt_small", 17), ("pcpvt_small", 17))], batch, reps)
 
 
 if __name__ == "__main__":

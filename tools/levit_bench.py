@@ -20,46 +20,13 @@ import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
 from tlxcv_amd import engine as E, seeded, models  # noqa: E402
 from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tools.ab import ab, model_on_off, timed  # noqa: E402
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 # (layers of this shape in levit_128s, Rq, Rk, stride, heads, kd, d)
 SHAPES = ((2, 14, 14, 1, 4, 16, 32), (1, 7, 14, 2, 8, 16, 64), (3, 7, 7, 1, 6, 16, 32), (1, 4, 7, 2, 16, 16, 64), (4, 4, 4, 1, 8, 16, 32))
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: (fn, calls per graph, replays per round)} -> {name: (median us per call, min, max)}, alternated; and the last outputs."""
-    graphs, outs = {}, {}
-    for k, (f, calls, _) in arms.items():
-        for _ in range(2):
-            outs[k] = f()
-        torch.cuda.synchronize()
-        graphs[k] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[k]):
-            for _ in range(calls):
-                f()
-        graphs[k].replay()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k, (_, calls, replays) in arms.items():
-            t[k].append(timed(graphs[k].replay, replays) / calls)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res, outs
 
 
 def shapes():
@@ -73,7 +40,9 @@ def shapes():
         grid = (torch.randn(heads, Rk, Rk, generator=g) * 0.5).to(dev)
         run = lambda fused: E.levit_attention(kv, grid, heads, kd, d, Rk, kd ** -0.5, q=q, Rq=Rq if sub else None, stride=stride,      # noqa: E731
                                               fused=fused)
-        res, outs = ab({"mfma": (lambda: run(True), 10, 5), "plain": (lambda: run(False), 2, 2)})
+        arms = {"mfma": (lambda: run(True), 10, 5), "plain": (lambda: run(False), 2, 2)}
+        outs = {k: f() for k, (f, _, _) in arms.items()}
+        res = ab(arms, reps)
         nbytes = batch * heads * (Rq * Rq * kd + Rk * Rk * (kd + d) + Rq * Rq * d) * 2 + heads * Rk * Rk * 4
         tag = f"q{Rq}x{Rq} k{Rk}x{Rk} stride {stride} heads {heads:2d} kd {kd} d {d:3d} (x{n})"
         for k, (med, lo, hi) in res.items():
@@ -88,28 +57,7 @@ def shapes():
 
 
 def model():
-    m = models.levit_128s()
-    m.load_dict(seeded.fill(seeded.shapes_of(m), 16))
-    m = m.to(dev).set_eval()
-    x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-    graphs = {}
-    for on in (True, False):
-        E.set_option("levit_attn", on)
-        with torch.no_grad():
-            graphs[on] = GraphedForward(m, x)
-    E.set_option("levit_attn", True)
-    iters = {True: 10, False: 4}
-    t = {True: [], False: []}
-    for _ in range(reps):
-        for on in (True, False):
-            t[on].append(timed(lambda: graphs[on](), iters[on]))
-    print(f"# levit_128s batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 10 (on) / 4 (off) forwards (min..max)")
-    for on in (True, False):
-        v = sorted(t[on])
-        med = v[len(v) // 2]
-        print(f"levit_attn {'on ' if on else 'off'}: {med / 1e3:8.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-    d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-    print(f"max|logit difference| on vs off: {d:.3e}")
+    model_on_off("levit_attn", [("levit_128s", models.levit_128s, 16)], batch, reps, forwards=(10, 4))
 
 
 def streams():

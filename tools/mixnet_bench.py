@@ -16,8 +16,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
-from tlxcv_amd import engine as E, seeded, models  # noqa: E402
-from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tlxcv_amd import engine as E, models  # noqa: E402
+from tools.ab import ab, copy_floor, model_on_off  # noqa: E402
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
@@ -36,40 +36,6 @@ def unit_shapes(name):
         if u.stride == 2:
             hw //= 2
     return out
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: (fn, calls per graph, replays per round)} -> {name: (median us per call, min, max)}."""
-    graphs = {}
-    for k, (f, calls, _) in arms.items():
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        graphs[k] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[k]):
-            for _ in range(calls):
-                f()
-        graphs[k].replay()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k, (_, calls, replays) in arms.items():
-            t[k].append(timed(graphs[k].replay, replays) / calls)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res
 
 
 def shape():
@@ -97,12 +63,10 @@ def shape():
         del rf, rl
         calls = 10 if hw <= 56 else 4
         out = ab({"fused": (lambda: E.mixconv_dw(x, params, st, act, pool=pool, fused=True, out=y), calls, 5),
-                  "groups": (lambda: E.mixconv_dw(x, params, st, act, pool=pool, fused=False, out=y), calls, 5)})
+                  "groups": (lambda: E.mixconv_dw(x, params, st, act, pool=pool, fused=False, out=y), calls, 5)}, reps)
         nbytes = (x.numel() + y.numel()) * 2
         nbytes -= nbytes % 32
-        src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-        dst = torch.empty_like(src)
-        copy = ab({"copy": (lambda: dst.copy_(src), calls, 5)})["copy"]
+        copy = copy_floor(nbytes, calls, reps)
         floor = nbytes / HBM * 1e6                                                  # us
         print(f"## units {' '.join(where)}: ({batch}, {hw}, {hw}, {Cc}) in {G} groups of {groups[0]}, windows {kernels}, stride {st}, "
               f"act {act}{', + SE pool' if pool else ''}")
@@ -113,33 +77,11 @@ def shape():
         wins = out["fused"][2] < out["groups"][1]
         print(f"max|fused - groups| on the seeded maps: {d:.3e} (pool {dp:.3e}); fused / groups = {out['fused'][0] / out['groups'][0]:.4f}: "
               f"{'the fused arm is faster beyond the spread' if wins else 'NOT faster beyond the spread'}", flush=True)
-        del x, y, src, dst
+        del x, y
 
 
 def model():
-    for name, seed in (("mixnet_s", 53), ("mixnet_m", 52), ("mixnet_l", 53)):
-        m = getattr(models, name)()
-        m.load_dict(seeded.fill(seeded.shapes_of(m), seed))
-        m = m.to(dev).set_eval()
-        x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-        graphs = {}
-        for on in (True, False):
-            E.set_option("mixconv", on)
-            with torch.no_grad():
-                graphs[on] = GraphedForward(m, x)
-        E.set_option("mixconv", True)
-        t = {True: [], False: []}
-        for _ in range(reps):
-            for on in (True, False):
-                t[on].append(timed(lambda: graphs[on](), 5))
-        print(f"# {name} batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 5 forwards (min..max)")
-        for on in (True, False):
-            v = sorted(t[on])
-            med = v[len(v) // 2]
-            print(f"mixconv {'on ' if on else 'off'}: {med / 1e3:8.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-        d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-        print(f"max|logit difference| on vs off: {d:.3e}")
-        del graphs, m
+    model_on_off("mixconv", [(n, getattr(models, n), s) for n, s in (("mixnet_s", 53), ("mixnet_m", 52), ("mixnet_l", 53))], batch, reps)
 
 
 if __name__ == "__main__":

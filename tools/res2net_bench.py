@@ -20,6 +20,7 @@ import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
 from tlxcv_amd import engine as E, seeded, models  # noqa: E402
 from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tools.ab import ab, copy_floor, timed  # noqa: E402
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
@@ -37,40 +38,6 @@ def chain_shapes(scales, width):
         else:
             out.setdefault((hw, b.w, b.wp, b.scales), []).append(str(i))
     return out
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: (fn, calls per graph, replays per round)} -> {name: (median us per call, min, max)}."""
-    graphs = {}
-    for k, (f, calls, _) in arms.items():
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        graphs[k] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[k]):
-            for _ in range(calls):
-                f()
-        graphs[k].replay()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k, (_, calls, replays) in arms.items():
-            t[k].append(timed(graphs[k].replay, replays) / calls)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res
 
 
 def shape(variants):
@@ -96,12 +63,10 @@ def shape(variants):
             del rf, rl
             calls = 10
             out = ab({"fused": (lambda: E.res2_chain(x, params, E.ACT_RELU, fused=True, out=y), calls, 5),
-                      "layered": (lambda: E.res2_chain(x, params, E.ACT_RELU, fused=False, out=y), calls, 5)})
+                      "layered": (lambda: E.res2_chain(x, params, E.ACT_RELU, fused=False, out=y), calls, 5)}, reps)
             nbytes = 2 * batch * hw * hw * S * w * 2
             nbytes -= nbytes % 32
-            src = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            dst = torch.empty_like(src)
-            copy = ab({"copy": (lambda: dst.copy_(src), calls, 5)})["copy"]
+            copy = copy_floor(2 * nbytes, calls, reps)      # (a copy OF nbytes: as many read and as many written)
             floor = nbytes / HBM * 1e6                                                  # us
             print(f"## {width}w x {scales}s blocks {' '.join(where)}: ({batch}, {hw}, {hw}, {S} x {w} at pitch {wp}), {S - 1} convs")
             for k, (med, lo, hi) in out.items():
@@ -112,7 +77,7 @@ def shape(variants):
             print(f"max|fused - layered| on the seeded maps: {d:.3e}; fused / layered = {out['fused'][0] / out['layered'][0]:.4f}: "
                   f"{'the fused arm is faster beyond the spread' if wins else 'NOT faster beyond the spread'}; the router sends it to the "
                   f"{'fused' if E._res2_chain_routed(hw, hw, w, S) else 'layered'} arm", flush=True)
-            del x, y, src, dst
+            del x, y
 
 
 def model():

@@ -16,8 +16,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
-from tlxcv_amd import engine as E, seeded, models  # noqa: E402
-from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tlxcv_amd import engine as E, models  # noqa: E402
+from tools.ab import ab, copy_floor, model_on_off  # noqa: E402
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
@@ -25,40 +25,6 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 
 SHAPES = [("x0_5 stage 2", 28, 48), ("x0_5 stage 3", 14, 96), ("x0_5 stage 4", 7, 192),
           ("x1_0 stage 2", 28, 116), ("x1_0 stage 3", 14, 232), ("x1_0 stage 4", 7, 464)]
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: (fn, calls per graph, replays per round)} -> {name: (median us per call, min, max)}."""
-    graphs = {}
-    for k, (f, calls, _) in arms.items():
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        graphs[k] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[k]):
-            for _ in range(calls):
-                f()
-        graphs[k].replay()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k, (_, calls, replays) in arms.items():
-            t[k].append(timed(graphs[k].replay, replays) / calls)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res
 
 
 def unit():
@@ -83,11 +49,9 @@ def unit():
             y_l = E.shuffle_unit(x, params, E.ACT_RELU, fused=False)
             d = (y_f.float() - y_l.float()).abs().max().item()
             arms = dict({"fused": (lambda: E.shuffle_unit(x, params, E.ACT_RELU, fused=True, out=y), 10, 5)}, **arms)
-        res = ab(arms)
+        res = ab(arms, reps)
         nbytes = 2 * batch * hw * hw * c * 2
-        src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-        dst = torch.empty_like(src)
-        copy = ab({"copy": (lambda: dst.copy_(src), 10, 5)})["copy"]
+        copy = copy_floor(nbytes, 10, reps)
         bw = nbytes / copy[0] / 1e3                                             # GB/s: nbytes / 2 read + nbytes / 2 written
         print(f"## {name}: ({batch}, {hw}, {hw}, {c}), h = {h}")
         for k, (med, lo, hi) in res.items():
@@ -103,29 +67,7 @@ def unit():
 
 
 def model():
-    for name, seed in (("shufflenet_v2_x0_5", 19), ("shufflenet_v2_x1_0", 17)):
-        m = getattr(models, name)()
-        m.load_dict(seeded.fill(seeded.shapes_of(m), seed))
-        m = m.to(dev).set_eval()
-        x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-        graphs = {}
-        for on in (True, False):
-            E.set_option("shuffle_unit", on)
-            with torch.no_grad():
-                graphs[on] = GraphedForward(m, x)
-        E.set_option("shuffle_unit", True)
-        t = {True: [], False: []}
-        for _ in range(reps):
-            for on in (True, False):
-                t[on].append(timed(lambda: graphs[on](), 5))
-        print(f"# {name} batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 5 forwards (min..max)")
-        for on in (True, False):
-            v = sorted(t[on])
-            med = v[len(v) // 2]
-            print(f"shuffle_unit {'on ' if on else 'off'}: {med / 1e3:8.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-        d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-        print(f"max|logit difference| on vs off: {d:.3e}")
-        del graphs, m
+    model_on_off("shuffle_unit", [(n, getattr(models, n), s) for n, s in (("shufflenet_v2_x0_5", 19), ("shufflenet_v2_x1_0", 17))], batch, reps)
 
 
 if __name__ == "__main__":

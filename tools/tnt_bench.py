@@ -16,45 +16,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
 from tlxcv_amd import engine as E, seeded, models  # noqa: E402
-from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tools.ab import ab, copy_floor, model_on_off  # noqa: E402
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: (fn, calls per graph, replays per round)} -> {name: (median us per call, min, max)}, alternated."""
-    graphs = {}
-    for k, (f, calls, _) in arms.items():
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        graphs[k] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[k]):
-            for _ in range(calls):
-                f()
-        graphs[k].replay()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k, (_, calls, replays) in arms.items():
-            t[k].append(timed(graphs[k].replay, replays) / calls)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res
 
 
 def kernel():
@@ -74,12 +40,10 @@ def kernel():
     # LayerNorm keeps the rows O(1)
     x = x0.clone()
     run = lambda fused: E.tnt_inner(x, packed, 4, fused=fused, out=x)      # noqa: E731
-    res = ab({"fused": (lambda: run(True), 10, 5), "plain": (lambda: run(False), 2, 2)})
+    res = ab({"fused": (lambda: run(True), 10, 5), "plain": (lambda: run(False), 2, 2)}, reps)
     assert torch.isfinite(x).all()
     nbytes = 3 * patches * 16 * 24 * 2
-    src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
-    dst = torch.empty_like(src)
-    copy = ab({"copy": (lambda: dst.copy_(src), 10, 5)})["copy"]
+    copy = copy_floor(nbytes, 10, reps)
     bw = nbytes / copy[0] / 1e3                                             # GB/s: nbytes / 2 read + nbytes / 2 written
     for k, (med, lo, hi) in res.items():
         print(f"{k:5s} {med:10.1f} us ({lo:.1f}..{hi:.1f})  {nbytes / med / 1e3:7.1f} GB/s of x + y + y_norm", flush=True)
@@ -91,28 +55,7 @@ def kernel():
 
 
 def model():
-    m = models.tnt_small()
-    m.load_dict(seeded.fill(seeded.shapes_of(m), 16))
-    m = m.to(dev).set_eval()
-    x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-    graphs = {}
-    for on in (True, False):
-        E.set_option("tnt_inner", on)
-        with torch.no_grad():
-            graphs[on] = GraphedForward(m, x)
-    E.set_option("tnt_inner", True)
-    iters = {True: 10, False: 3}
-    t = {True: [], False: []}
-    for _ in range(reps):
-        for on in (True, False):
-            t[on].append(timed(lambda: graphs[on](), iters[on]))
-    print(f"# tnt_small batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 10 (on) / 3 (off) forwards (min..max)")
-    for on in (True, False):
-        v = sorted(t[on])
-        med = v[len(v) // 2]
-        print(f"tnt_inner {'on ' if on else 'off'}: {med / 1e3:8.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-    d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-    print(f"max|logit difference| on vs off: {d:.3e}")
+    model_on_off("tnt_inner", [("tnt_small", models.tnt_small, 16)], batch, reps, forwards=(10, 3))
 
 
 if __name__ == "__main__":

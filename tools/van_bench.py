@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
 from tlxcv_amd import engine as E, seeded, models  # noqa: E402
-from tlxcv_amd.graph import GraphedForward  # noqa: E402
+from tools.ab import ab, model_on_off  # noqa: E402
 import importlib  # noqa: E402
 
 V = importlib.import_module("tlxcv_amd.models.classification.van")      # (the package attribute `van` is the factory)
@@ -26,40 +26,6 @@ batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 copy_tbs = float(sys.argv[4]) if len(sys.argv) > 4 else 4.75
 STAGES = ((1, 56, 32), (2, 28, 64), (3, 14, 160), (4, 7, 256))      # (stage, H = W, C) at 224 x 224
-
-
-def timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters          # us
-
-
-def ab(arms):
-    """arms: {name: fn} -> {name: (median us per call, min, max)} from hipGraphs of 10 calls, alternated; and the last outputs."""
-    graphs, outs = {}, {}
-    for k, f in arms.items():
-        for _ in range(3):
-            outs[k] = f()
-        torch.cuda.synchronize()
-        graphs[k] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[k]):
-            for _ in range(10):
-                f()
-        graphs[k].replay()
-    torch.cuda.synchronize()
-    t = {k: [] for k in arms}
-    for _ in range(reps):
-        for k in arms:
-            t[k].append(timed(graphs[k].replay, 5) / 10)
-    res = {}
-    for k in arms:
-        v = sorted(t[k])
-        res[k] = (v[len(v) // 2], v[0], v[-1])
-    return res, outs
 
 
 def stages():
@@ -98,7 +64,8 @@ def stages():
                     ("mlp half", {"only": half(True, "mlp")}),
                 )
                 for name, arms in groups:
-                    res, outs = ab(arms)
+                    outs = {k: f() for k, f in arms.items()}
+                    res = ab({k: (f, 10, 5) for k, f in arms.items()}, reps)
                     for k, (med, lo, hi) in res.items():
                         extra = ""
                         if name == "lka_dw":
@@ -113,27 +80,7 @@ def stages():
 
 
 def model():
-    m = models.van()
-    m.load_dict(seeded.fill(seeded.shapes_of(m), 16))
-    m = m.to(dev).set_eval()
-    x = torch.from_numpy(seeded.image_batch(16, 0)).to(dev).repeat(batch // 16, 1, 1, 1).contiguous()
-    graphs = {}
-    for on in (True, False):
-        E.set_option("lka", on)
-        with torch.no_grad():
-            graphs[on] = GraphedForward(m, x)
-    E.set_option("lka", True)
-    t = {True: [], False: []}
-    for _ in range(reps):
-        for on in (True, False):
-            t[on].append(timed(lambda: graphs[on](), 10))
-    print(f"# VAN-B0 batch {batch}, 224 x 224, fp16, hipGraph replay; median of {reps} alternated rounds of 10 forwards (min..max)")
-    for on in (True, False):
-        v = sorted(t[on])
-        med = v[len(v) // 2]
-        print(f"lka {'on ' if on else 'off'}: {med / 1e3:7.3f} ms ({v[0] / 1e3:.3f}..{v[-1] / 1e3:.3f})  {batch / med * 1e6:8.0f} img/s", flush=True)
-    d = (graphs[True].static_out.float() - graphs[False].static_out.float()).abs().max().item()
-    print(f"max|logit difference| on vs off: {d:.3e}")
+    model_on_off("lka", [("VAN-B0", models.van, 16)], batch, reps, forwards=10, ms_width=7)
 
 
 if __name__ == "__main__":
