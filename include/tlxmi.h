@@ -644,6 +644,37 @@ size_t tlxmi_res2_chain_param_bytes(const tlxmi_res2_chain_desc* d);
 int tlxmi_res2_chain(const tlxmi_res2_chain_desc* d, const void* x, const void* params, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The input branches of GoogLeNet's Inception module (classification/googlenet.py:41-65) in one launch: everything that reads x.
+ *     y[p][0 .. f1)                         = relu( x[p] . W1 )                       fp32 accumulation on MFMA
+ *     t[p][0 .. f3R)                        =       x[p] . W3r                        the reduce convs have no activation
+ *     t[p][t_f5_off .. t_f5_off + f5R)      =       x[p] . W5r
+ *     y[p][y_proj_off .. y_proj_off + proj) = relu( maxpool3x3s1p1(x)[p] . Wp )       a position outside the image takes no part in the max
+ * fp16 only.  x: NHWC, N x H x W pixels at pitch x_ld, Cin channels read (columns behind Cin are never loaded).  y: the module's
+ * output map at pitch y_ld; t: the map of both reduce outputs at pitch t_ld.  Every other column of y (the slices of the 3 x 3 and
+ * 5 x 5 convs between f1 and y_proj_off, anything behind the projection) and of t is left untouched.  The pooled map is built from
+ * a haloed pixel tile in LDS and never stored; a tile takes no halo from the neighbouring image of the batch.  y and t alias no
+ * input.  One writer per element, fixed summation order, no atomics.
+ * params: tlxmi_inception_head_param_bytes(Cin, f1, f3R, f5R, proj) bytes: fp16 [R][Kp], row = output channel, the rows of W1, W3r,
+ * W5r, Wp in this order, each filter padded with zero rows to a multiple of 16, Kp = Cin rounded up to 64, zero behind Cin.
+ * tlxmi_inception_head_supported() is pure host code and answers 1 exactly for: fp16; N, H, W >= 1; Cin and the four widths
+ * multiples of 8, 8 <= Cin <= 2048, 8 <= width <= 1024; x_ld, y_ld, t_ld, y_proj_off, t_f5_off multiples of 8; x_ld >= Cin;
+ * f1 <= y_proj_off and y_proj_off + proj <= y_ld; f3R <= t_f5_off and t_f5_off + f5R <= t_ld; (pixels * ld + 2048) * 2 below 2^31
+ * for the three pitches (32-bit byte offsets).  1 means the call is taken, given x, params, y and t 16-byte aligned
+ * (TLXMI_ERR_ALIGNMENT otherwise); anything else returns TLXMI_ERR_UNSUPPORTED (run tlxmi_conv2d three times, tlxmi_maxpool2d and
+ * tlxmi_conv2d instead).  param_bytes is 0 outside the ranges.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_inception_head_desc {
+    int32_t dtype;
+    int32_t N, H, W, Cin;
+    int32_t f1, f3R, f5R, proj;
+    int32_t x_ld, y_ld, t_ld;
+    int32_t y_proj_off, t_f5_off;
+} tlxmi_inception_head_desc;
+int tlxmi_inception_head_supported(const tlxmi_inception_head_desc* d);
+size_t tlxmi_inception_head_param_bytes(int Cin, int f1, int f3R, int f5R, int proj);
+int tlxmi_inception_head(const tlxmi_inception_head_desc* d, const void* x, const void* params, void* y, void* t, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

@@ -65,6 +65,11 @@ class Res2ChainDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "w", "wp", "scales", "x_ld", "y_ld", "act")]
 
 
+class InceptionHeadDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "Cin", "f1", "f3R", "f5R", "proj", "x_ld", "y_ld", "t_ld", "y_proj_off",
+                                         "t_f5_off")]
+
+
 class LkaGateDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in ("C", "a1_ld", "t_ld", "res_ld", "y_ld")]
 
@@ -194,6 +199,7 @@ PROTOTYPES = {
     "tlxmi_ghost_module": [C.POINTER(GhostModuleDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_mixconv_dw": [C.POINTER(MixConvDwDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_res2_chain": [C.POINTER(Res2ChainDesc), _vp, _vp, _vp, _vp],
+    "tlxmi_inception_head": [C.POINTER(InceptionHeadDesc), _vp, _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -233,6 +239,8 @@ _SPECIAL = {
     "tlxmi_res2_chain_supported": ([C.POINTER(Res2ChainDesc)], C.c_int),
     "tlxmi_res2_chain_band_rows": ([C.POINTER(Res2ChainDesc)], C.c_int),
     "tlxmi_res2_chain_param_bytes": ([C.POINTER(Res2ChainDesc)], C.c_size_t),
+    "tlxmi_inception_head_supported": ([C.POINTER(InceptionHeadDesc)], C.c_int),
+    "tlxmi_inception_head_param_bytes": ([_i, _i, _i, _i, _i], C.c_size_t),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

@@ -97,6 +97,11 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # a halo that shrinks a row a conv, every 3x3 as nine MFMA taps, the map read once and written once; elsewhere
                                   # and off = tlxmi_conv2d -> tlxmi_affine_act (the add) -> tlxmi_conv2d ... -> tlxmi_copy_channels (the A/B and
                                   # the tests' other arm)
+            "inception_head": True,  # GoogLeNet's Inception modules (fp16, widths multiples of 8; the shapes the measured table keeps:
+                                  # engine.INCEPTION_HEAD_WINS — `_ince3a` alone as measured): the three 1x1 convs on x and maxpool 3/1/1 -> 1x1 conv on tlxmi_inception_head: ONE
+                                  # launch, x staged once in LDS with a halo, the pooled tile an MFMA operand that never leaves the CU, the four
+                                  # results written into their slices of the output map and of the mid map; elsewhere and off = tlxmi_conv2d x 3 ->
+                                  # tlxmi_maxpool2d -> tlxmi_conv2d (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -1934,6 +1939,135 @@ def res2_chain(x, params, act, fused=None, out=None):
     _timed(launch, lambda: ((2 * N * H * W * S * w + (S - 1) * 9 * w * w) * es, 2 * N * H * W * (S - 1) * 9 * w * w,
                             (N, H, W, S * w, S * w, "res2_chain" if fused else "conv-add-conv-copy")))      # the chain is one entry
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# GoogLeNet's Inception module: the branches that read x
+# ---------------------------------------------------------------------------------------------
+def inception_head_pack(w1, w3r, w5r, wp):
+    """The parameter image tlxmi_inception_head reads (include/tlxmi.h), as one uint8 tensor on the operands' device: fp16 [R][Kp], the
+    rows of the four 1x1 filters in the order W1, W3r, W5r, Wp, each padded with zero rows to a multiple of 16, Kp = Cin rounded up
+    to 64, zero behind Cin.  Each filter: (out, Cin, 1, 1) or (out, Cin)."""
+    cin = int(w1.shape[1])
+    kp = _round_up(cin, 64)
+    return _param_image(*[_zero_padded(w.reshape(w.shape[0], cin), (_round_up(w.shape[0], 16), kp), torch.float16, w1.device)
+                          for w in (w1, w3r, w5r, wp)])
+
+
+class InceptionParams:
+    """The four 1x1 filters of one Inception module that read its input, in the forms both arms of inception_head() read: a
+    PackedFilter each for the layer-by-layer arm, and — fp16 — the one-buffer image of tlxmi_inception_head (inception_head_pack).
+    w1, w3r, w5r, wp: (f1 | f3R | f5R | proj, Cin, 1, 1); f3, f5: the widths of the module's 3x3 and 5x5 convs, whose slices of the
+    output lie between w1's and wp's.  The slices of the output map y are [0, f1) | [o3, o3 + f3) | [o5y, o5y + f5) | [op, op + proj)
+    = the concatenation of the reference (googlenet.py:63); the mid map t holds the 3x3 reduce map at [0, f3R) and the 5x5 one at
+    [t5, t5 + f5R), t5 = f3R rounded up to 8, at pitch t_ld = t5 + f5R.  Every width must be a multiple of 8 (each slice then starts
+    on a 16-byte boundary in both dtypes; all nine modules of GoogLeNet do): other widths are REFUSED here, in both arms.
+    t5: another offset of the 5x5 reduce map in the mid map (a multiple of 8, at least f3R; tests)."""
+
+    def __init__(self, w1, w3r, w5r, wp, f3, f5, dtype, t5=None):
+        self.cin = int(w1.shape[1])
+        self.f1, self.f3r, self.f5r, self.proj, self.f3, self.f5 = (int(w1.shape[0]), int(w3r.shape[0]), int(w5r.shape[0]), int(wp.shape[0]),
+                                                                    int(f3), int(f5))
+        widths = (self.cin, self.f1, self.f3r, self.f5r, self.proj, self.f3, self.f5)
+        if any(int(w.shape[1]) != self.cin for w in (w3r, w5r, wp)) or any(n <= 0 or n % 8 for n in widths):
+            raise RuntimeError(f"InceptionParams: four 1x1 filters over the same Cin are expected, and Cin and every width a multiple of 8 "
+                               f"(a slice of the output map must start on a 16-byte boundary); got Cin / f1 / f3R / f5R / proj / f3 / f5 = {widths}")
+        self.dtype = dtype
+        self.o3, self.o5y, self.op = self.f1, self.f1 + self.f3, self.f1 + self.f3 + self.f5
+        self.cout = self.op + self.proj
+        self.t5 = _round_up(self.f3r, 8) if t5 is None else int(t5)
+        if self.t5 < self.f3r or self.t5 % 8:
+            raise RuntimeError(f"InceptionParams: t5 must be a multiple of 8 and at least f3R = {self.f3r}, got {self.t5}")
+        self.t_ld = self.t5 + self.f5r
+        self.pk1, self.pk3r, self.pk5r, self.pkp = (PackedFilter(w, dtype) for w in (w1, w3r, w5r, wp))
+        self.blob = None
+        nbytes = _lib.load().tlxmi_inception_head_param_bytes(self.cin, self.f1, self.f3r, self.f5r, self.proj) if dtype == torch.float16 else 0
+        if nbytes:
+            self.blob = inception_head_pack(*(w.detach() for w in (w1, w3r, w5r, wp)))
+            assert self.blob.numel() == nbytes
+
+
+def _inception_head_desc(x, p, y_ld, t_ld):
+    N, H, W, ld = x.shape
+    return _lib.InceptionHeadDesc(dtype=dt_code(x.dtype), N=N, H=H, W=W, Cin=p.cin, f1=p.f1, f3R=p.f3r, f5R=p.f5r, proj=p.proj, x_ld=ld,
+                                  y_ld=y_ld, t_ld=t_ld, y_proj_off=p.op, t_f5_off=p.t5)
+
+
+def inception_head_takes(x, params, y_ld=None, t_ld=None):
+    """Whether the library's tlxmi_inception_head takes this NHWC map with these parameters (fp16, the widths and pitches of
+    include/tlxmi.h): what fused=True needs."""
+    if x.dim() != 4 or x.dtype != torch.float16 or not x.is_contiguous() or params.blob is None:
+        return False
+    y_ld = params.cout if y_ld is None else int(y_ld)
+    t_ld = params.t_ld if t_ld is None else int(t_ld)
+    return bool(_lib.load().tlxmi_inception_head_supported(C.byref(_inception_head_desc(x, params, y_ld, t_ld))))
+
+
+# (H, W, Cin, f1, f3R, f5R, proj) of the module heads where the one launch was measured FASTER than the layer-by-layer arm beyond the spread of
+# both, at batch 256 on one MI355X (tools/googlenet_bench.py, profiles/googlenet/googlenet_bench_b256.txt, DESIGN 4.31): inception_head() keeps
+# the launch there and runs the layers everywhere else by default.  MEASURED: it wins at `_ince3a` alone (0.59 of the layers' time: 13 n-tiles,
+# one chunk at two workgroups a CU); `_ince3b` (0.96) and `_ince5a` (1.01) are inside the spread, the others take 1.06 - 1.15 (`_ince4a` .. `_ince4d`),
+# 1.38 (`_ince5b`) and 1.58 (`_ince4e`) x the layers' time.  Shapes other than those nine are unmeasured and run layer by layer.
+INCEPTION_HEAD_WINS = frozenset({(27, 27, 192, 64, 96, 16, 32)})
+
+
+def _inception_head_routed(H, W, p):
+    return (H, W, p.cin, p.f1, p.f3r, p.f5r, p.proj) in INCEPTION_HEAD_WINS
+
+
+def inception_head_supported(x, params, y_ld=None, t_ld=None):
+    """Whether inception_head() runs tlxmi_inception_head on this map by default: the "inception_head" option on, the measured table
+    keeps the shape (INCEPTION_HEAD_WINS) and the library takes the call (inception_head_takes)."""
+    return bool(_options["inception_head"] and x.dim() == 4 and _inception_head_routed(x.shape[1], x.shape[2], params)
+                and inception_head_takes(x, params, y_ld, t_ld))
+
+
+def inception_head(x, params, fused=None, out=None, mid=None):
+    """Everything of an Inception module (googlenet.py:41-65) that reads its input, on an NHWC map x (N, H, W, x_ld) whose first
+    Cin = params.cin channels are the input (the columns behind them are not read):
+        y[..., :f1] = relu(x . W1),   t[..., :f3R] = x . W3r,   t[..., t5:t5 + f5R] = x . W5r   (the reduce convs are linear),
+        y[..., op:op + proj] = relu(maxpool 3/1/1 (x) . Wp)        (positions outside the image take no part in the max)
+    -> (y, t): y (N, H, W, params.cout) or `out`, t (N, H, W, params.t_ld) or `mid` (their last axes are the pitches, multiples of 8).
+    The slices [f1, op) of y — the module's 3x3 and 5x5 convs write them from t — and every other column are left untouched.
+    params: InceptionParams.  One launch (tlxmi_inception_head: x read once, the pooled map kept in LDS) when the "inception_head"
+    option is on, the precision is fp16, the measured table keeps the shape and the library takes it (inception_head_supported);
+    otherwise — and always for fp32 — tlxmi_conv2d three times into the slices, tlxmi_maxpool2d, tlxmi_conv2d.  fused=True / False
+    forces one form (tests, tools/); True raises where the launch is not supported."""
+    need_gpu(x, "input")
+    N, H, W, ld = x.shape
+    p = params
+    if x.dtype != p.dtype or ld < p.cin or ld % 8 or not x.is_contiguous():
+        raise RuntimeError(f"inception_head: x must be a dense NHWC map of the parameters' dtype with at least {p.cin} channels at a pitch "
+                           f"that is a multiple of 8, got {tuple(x.shape)} {x.dtype}")
+    out, y_ld = _out_map("inception_head", out, N, H, W, p.cout, x.dtype, x.device, p.cout, multiple=8,
+                         what=f"a dense ({N}, {H}, {W}, >= {p.cout}) map of x's dtype at a pitch that is a multiple of 8")
+    mid, t_ld = _out_map("inception_head", mid, N, H, W, p.t_ld, x.dtype, x.device, p.t_ld, multiple=8,
+                         what=f"(mid) a dense ({N}, {H}, {W}, >= {p.t_ld}) map of x's dtype at a pitch that is a multiple of 8")
+    takes = lambda: inception_head_takes(x, p, y_ld, t_ld)      # noqa: E731
+    # the option and the table first: the library's predicate is asked only where they keep the launch
+    fused = _use_fused("inception_head", fused, takes, lambda: _options["inception_head"] and _inception_head_routed(H, W, p) and takes(),
+                       lambda: f"{tuple(x.shape)} {x.dtype} with Cin {p.cin}, widths {p.f1} / {p.f3r} / {p.f5r} / {p.proj}, y_ld {y_ld}, t_ld {t_ld}")
+    es = x.element_size()
+    M = N * H * W
+    if _sizing():
+        _note_act(x.numel() * es, M * y_ld * es, M * t_ld * es)
+
+    def launch():
+        if fused:
+            desc = _inception_head_desc(x, p, y_ld, t_ld)
+            _lib.call("tlxmi_inception_head", C.byref(desc), _p(x), _p(p.blob), _p(out), _p(mid), _stream())
+            return
+        xin = x[..., :p.cin]
+        conv2d(xin, p.pk1, act=ACT_RELU, out=out[..., :p.f1], out_ld=y_ld, x_ld=ld)
+        conv2d(xin, p.pk3r, out=mid[..., :p.f3r], out_ld=t_ld, x_ld=ld)
+        conv2d(xin, p.pk5r, out=mid[..., p.t5:p.t5 + p.f5r], out_ld=t_ld, x_ld=ld)
+        pooled = torch.empty((N, H, W, p.cin), dtype=x.dtype, device=x.device)
+        _lib.call("tlxmi_maxpool2d", _p(x), _p(pooled), dt_code(x.dtype), N, H, W, p.cin, ld, p.cin, 3, 3, 1, 1, 1, 1, H, W, _stream())
+        conv2d(pooled, p.pkp, act=ACT_RELU, out=out[..., p.op:p.op + p.proj], out_ld=y_ld)
+    nout = p.f1 + p.f3r + p.f5r + p.proj
+    _timed(launch, lambda: ((M * (p.cin + nout) + p.cin * nout) * es, 2 * M * p.cin * nout,
+                            (N, H, W, p.cin, nout, "inception_head" if fused else "conv-conv-conv-pool-conv")))      # the chain is one entry
+    return out, mid
 
 
 # ---------------------------------------------------------------------------------------------

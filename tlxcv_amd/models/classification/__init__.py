@@ -43,3 +43,4 @@ from .mixnet import (MixNet, MixUnit, MixInitBlock, MixConv, MixConvBlock, mixco
                      mixnet_l)
 # (the Res2Net file's ConvBNLayer / BottleneckBlock stay in their module: DenseNet's ConvBNLayer owns that name here)
 from .res2net import Res2Net, res2net  # noqa: F401
+from .googlenet import GoogLeNet, ConvLayer, Inception, googlenet  # noqa: F401
