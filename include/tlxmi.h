@@ -787,8 +787,14 @@ int tlxmi_linear_ln(int dtype, int64_t rows, int K, int Cout, int x_ld, int y_ld
  *   out: [B][Ntok][heads*hd]       softmax(scale * q k^T + bias + mask) v, heads re-interleaved
  *   bias: optional [heads][Ntok][Ntok] fp32 (Swin relative position bias, :205-215)
  *   mask: optional [nW][Ntok][Ntok] fp32, window index = b % nW (Swin shift mask, :216-220)
- * hd <= 128.  Ntok <= 256 runs the tuned kernels (fp16: MFMA, hd in {32, 64, 96}); longer sequences (ViT at
- * 384 x 384: 577 tokens) run a generic online-softmax kernel.
+ * hd <= 128, any Ntok.  Which kernel takes which (Ntok, hd):
+ *   Ntok <= 256, fp16, hd in {32, 64, 96}, qkv and out 16-byte aligned: the MFMA kernel;
+ *   Ntok <= 256 otherwise (fp32; any other hd; unaligned operands): the fp32-arithmetic rows kernel, which stages K and V of one
+ *     (batch, head) in LDS as fp32, while (2 * Ntok * (hd + 1) + 1536) * 4 bytes fit in 160 KB — up to 152 tokens at hd 128,
+ *     203 at hd 96, 243 at hd 80, all 256 at hd <= 76;
+ *   Ntok > 256 (ViT at 384 x 384: 577 tokens), fp16, hd in {32, 64}, no bias / mask, aligned: the chunked online-softmax MFMA kernel;
+ *   everything else — Ntok > 256, and the short sequences whose staging does not fit — a generic online-softmax kernel that reads
+ *     K and V from global memory (bias and mask included).
  * ---------------------------------------------------------------------------------------- */
 typedef struct tlxmi_attn_desc {
     int32_t dtype;

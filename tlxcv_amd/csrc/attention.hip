@@ -7,10 +7,11 @@
 //   out[b,i,h,:] = sum_j softmax_j(scale * q_i.k_j + bias[h,i,j] + mask[b % nW,i,j]) v_j
 //
 // Three kernels:
-//   attn_rows_kernel  — exact-fp32 arithmetic, any hd <= 128, N <= 256: K and V of one (b, head)
-//                       staged once in LDS as fp32, one wave per query row, wave-shuffle softmax.
-//                       This is the fp32 parity path and the generic fallback.
-//   attn_long_kernel  — any N (ViT at 384x384: 577 tokens, vision_transformer.py:209-215): one wave per
+//   attn_rows_kernel  — exact-fp32 arithmetic, any hd <= 128, N <= 256 while 2 N (hd + 1) + 1536 floats fit
+//                       in 160 KB of LDS: K and V of one (b, head) staged once in LDS as fp32, one wave
+//                       per query row, wave-shuffle softmax.  The fp32 parity path and the generic fallback.
+//   attn_long_kernel  — any N (ViT at 384x384: 577 tokens, vision_transformer.py:209-215), and the short
+//                       sequences whose staging does not fit (more than 152 tokens at hd 128): one wave per
 //                       query row, keys in tiles of 64 straight from global memory / L2, running max and
 //                       sum (the usual online softmax); a coverage path, not a tuned one.
 //   attn_mfma_kernel  — fp16 throughput path (see below), hd in {32, 64, 96}, N <= 256.
@@ -162,9 +163,13 @@ template <typename T> static int launch_long(const AttnArgs& a, hipStream_t st) 
     return check_launch("attention(long)");
 }
 
+// attn_rows_kernel's LDS: K and V of one (b, head) as fp32 rows of hd + 1, the probabilities [4][256], the queries [4][128]
+static size_t rows_lds_bytes(int N, int hd) { return ((size_t)2 * N * (hd + 1) + 4 * 256 + 4 * 128) * sizeof(float); }
+static bool rows_fits(int N, int hd) { return N <= 256 && rows_lds_bytes(N, hd) <= 160 * 1024; }
+
 template <typename T> static int launch_rows(const AttnArgs& a, hipStream_t st) {
-    const size_t lds = ((size_t)2 * a.N * (a.hd + 1) + 4 * 256 + 4 * 128) * sizeof(float);
-    if (lds > 160 * 1024) return fail(TLXMI_ERR_UNSUPPORTED, "attention: N=%d hd=%d needs %zu B of LDS", a.N, a.hd, lds);
+    const size_t lds = rows_lds_bytes(a.N, a.hd);
+    if (a.N > 256 || lds > 160 * 1024) return fail(TLXMI_ERR_UNSUPPORTED, "attention: N=%d hd=%d needs %zu B of LDS", a.N, a.hd, lds);
     if (lds > 64 * 1024)
         if (int rc = raise_lds_limit(reinterpret_cast<const void*>(&attn_rows_kernel<T>), 160 * 1024, "attention")) return rc;
     hipLaunchKernelGGL((attn_rows_kernel<T>), dim3(a.B * a.heads), dim3(256), lds, st, a);
@@ -282,9 +287,11 @@ extern "C" int tlxmi_attention(const tlxmi_attn_desc* d, const void* qkv, const 
         if (d->dtype == TLXMI_F16 && attn_flash_ok(a) && aligned16(qkv) && aligned16(out)) return launch_attn_flash(a, st);   // ViT at 384 x 384
         return d->dtype == TLXMI_F32 ? launch_long<float>(a, st) : launch_long<half_t>(a, st);
     }
-    if (d->dtype == TLXMI_F32) return launch_rows<float>(a, st);
-    if ((d->hd == 64 || d->hd == 32 || d->hd == 96) && aligned16(qkv) && aligned16(out)) return launch_attn_mfma(a, st);
-    return launch_rows<half_t>(a, st);
+    if (d->dtype == TLXMI_F16 && (d->hd == 64 || d->hd == 32 || d->hd == 96) && aligned16(qkv) && aligned16(out)) return launch_attn_mfma(a, st);
+    // the fp32 K / V staging of the rows kernel must fit in 160 KB of LDS (152 tokens at hd 128, 203 at 96, 243 at 80);
+    // past that the online-softmax kernel, which stages nothing, takes the short sequence too (bias and mask included)
+    if (!rows_fits(a.N, a.hd)) return d->dtype == TLXMI_F32 ? launch_long<float>(a, st) : launch_long<half_t>(a, st);
+    return d->dtype == TLXMI_F32 ? launch_rows<float>(a, st) : launch_rows<half_t>(a, st);
 }
 
 extern "C" int tlxmi_mha(const tlxmi_mha_desc* d, const void* q, const void* k, const void* v, const float* mask,
