@@ -151,9 +151,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
     }
 #pragma unroll
     for (int r = 0; r < RW; ++r) mean[r] = group_sum<LPR>(mean[r]) / (float)C;
+    // the first mean carries the rounding of a sum of C terms; with rstd up to 1 / sqrt(eps) = 1e3 that noise showed in the output
+    // (a constant row of 2.7 came out 9e-4 off beta).  The centred pass also sums x - mean: its mean corrects the first one.
+    float dsum[RW];
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
-        float sq = 0.f;
+        float sq = 0.f, sd = 0.f;
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             if (lane + LPR * i < nch) {
@@ -163,13 +166,19 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
                 for (int e = 0; e < V; ++e) {
                     const float d = f[e] - mean[r];
                     sq += d * d;
+                    sd += d;
                 }
             }
         }
         rstd[r] = sq;
+        dsum[r] = sd;
     }
 #pragma unroll
-    for (int r = 0; r < RW; ++r) rstd[r] = 1.f / sqrtf(group_sum<LPR>(rstd[r]) / (float)C + eps);
+    for (int r = 0; r < RW; ++r) {
+        const float dm = group_sum<LPR>(dsum[r]) / (float)C;
+        mean[r] += dm;
+        rstd[r] = 1.f / sqrtf(fmaxf(group_sum<LPR>(rstd[r]) / (float)C - dm * dm, 0.f) + eps);
+    }
     if (stats) {   // statistics only (internal; no entry point since round 4): (rstd, -mean * rstd) per row, nothing else is written
         if (lane == 0) {
 #pragma unroll

@@ -243,7 +243,7 @@ __global__ void maxpool_kernel(const T* __restrict__ x, T* __restrict__ y, int N
                 float v[V];
                 Chunk<T>::load(x + ((n * H + hi) * W + wi) * x_ld + cg * V, v);
 #pragma unroll
-                for (int e = 0; e < V; ++e) m[e] = fmaxf(m[e], v[e]);
+                for (int e = 0; e < V; ++e) m[e] = (v[e] > m[e] || v[e] != v[e]) ? v[e] : m[e];   // NaN propagates (F.max_pool2d); fmaxf drops it
             }
         }
         Chunk<T>::store(y + ((n * Ho + ho) * Wo + wo) * y_ld + cg * V, m);
@@ -539,10 +539,8 @@ __global__ void dwconv_kernel(const T* __restrict__ x, const T* __restrict__ w, 
             }
         }
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
-            float t = acc[e];
-            if (scale) t *= scale[cg * V + e];
-            if (shift) t += shift[cg * V + e];
+        for (int e = 0; e < V; ++e) {      // one fused multiply-add, as the strip kernel: the two give the same bits
+            const float t = fmaf(acc[e], scale ? scale[cg * V + e] : 1.f, shift ? shift[cg * V + e] : 0.f);
             acc[e] = apply_act(t, d.act, d.act_param);
         }
         Chunk<T>::store(y + ((n * d.Ho + ho) * d.Wo + wo) * d.y_ld + cg * V, acc);
@@ -609,7 +607,7 @@ __global__ __launch_bounds__(256) void dwconv_strip_kernel(const T* __restrict__
         for (int t = 0; t < TW; ++t) {
             if (wo0 + t >= d.Wo) break;
 #pragma unroll
-            for (int e = 0; e < V; ++e) acc[t][e] = apply_act(acc[t][e] * sc[e] + sf[e], d.act, d.act_param);
+            for (int e = 0; e < V; ++e) acc[t][e] = apply_act(fmaf(acc[t][e], sc[e], sf[e]), d.act, d.act_param);
             Chunk<T>::store(y + ((n * d.Ho + ho) * d.Wo + wo0 + t) * d.y_ld + cg * V, acc[t]);
         }
     }
