@@ -23,30 +23,13 @@ import torch
 from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
+from ..common import DropPath, NHWCBlock, drop_path  # noqa: F401  (DropPath, drop_path: re-exported)
 
 __all__ = ["ConvNeXt", "convnext", "Block", "ChannelsFirstLayerNorm", "DropPath", "drop_path"]
 
 trunc_normal_ = nn.initializers.TruncatedNormal(stddev=0.02)
 zeros_ = nn.initializers.Constant(value=0.0)
 ones_ = nn.initializers.Constant(value=1.0)
-
-
-def drop_path(x, drop_prob=0.0, training=False):
-    """Stochastic depth (convnext.py:19-33): the identity in eval mode, the only mode this engine runs."""
-    if drop_prob == 0.0 or not training:
-        return x
-    raise RuntimeError("tlxcv_amd: drop_path in training mode — this engine runs eval-mode forward passes only")
-
-
-class DropPath(nn.Module):
-    """convnext.py:36-49."""
-
-    def __init__(self, drop_prob=None):
-        super().__init__()
-        self.drop_prob = drop_prob
-
-    def forward(self, x):
-        return drop_path(x, self.drop_prob or 0.0, self.is_train)
 
 
 class ChannelsFirstLayerNorm(nn.Module):
@@ -67,7 +50,7 @@ class ChannelsFirstLayerNorm(nn.Module):
         return from_nhwc(self.run_nhwc(as_nhwc(x, "channels_first")), "channels_first")
 
 
-class Block(nn.Module):
+class Block(NHWCBlock):
     """convnext.py:77-118."""
 
     def __init__(self, dim, drop_path=0.0, layer_scale_init_value=1e-06):
@@ -90,8 +73,7 @@ class Block(nn.Module):
         dt = E.precision()
         B, H, W, C = x.shape
         dw, fc1 = self.dwconv, self.pwconv1
-        w_rsc = dw._cached("dw", lambda: dw.filters.detach()[:, 0].permute(1, 2, 0).contiguous().to(dt))
-        b_dw = dw._cached("bias", lambda: E._f32(dw.biases)) if dw.biases is not None else None
+        w_rsc, b_dw = dw.packed(), dw.bias32()
         fused = E.dwconv7_supported(x)
         fold = fused and E.linear_ln_supported(B * H * W, C, fc1.out_features, dt, act=E.ACT_GELU)
         y, part = E.dwconv7_stats(x, w_rsc, b_dw, stats=fold, fused=fused)          # :108
@@ -103,9 +85,8 @@ class Block(nn.Module):
 
     def scaled_fc2(self, h, res=None):
         """gamma * (h W2 + b2) (+ res) as ONE epilogue (:113-117): gamma is the fp32 per-channel scale, gamma * b2 the shift."""
-        dt = E.precision()
         fc2 = self.pwconv2
-        pk2 = fc2._cached("pk", lambda: E.PackedFilter(fc2.weights.detach().t().contiguous(), dt))
+        pk2 = fc2.packed()
         if self.gamma is not None:
             def build():
                 g = E._f32(self.gamma)
@@ -113,12 +94,8 @@ class Block(nn.Module):
                 return g.contiguous(), (g * b2).contiguous()
             scale, shift = self._cached("layer_scale", build, deps=(fc2,))
         else:
-            scale, shift = None, (fc2._cached("bias", lambda: E._f32(fc2.biases)) if fc2.biases is not None else None)
+            scale, shift = None, fc2.bias32()
         return E.conv2d(h, pk2, scale=scale, shift=shift, res=res)
-
-    def forward(self, x):
-        v = as_nhwc(x, "channels_first")
-        return from_nhwc(self.run_nhwc(v if v.is_contiguous() else v.contiguous()), "channels_first")
 
 
 class ConvNeXt(nn.Module):
@@ -165,8 +142,7 @@ class ConvNeXt(nn.Module):
                 and not x.permute(0, 2, 3, 1).is_contiguous()):
             # one pass over the image, as Swin's patch embedding: conv + bias + LayerNorm over the D channels of a pixel
             w64 = conv._cached("pe4", lambda: E.patch_embed4_filter(conv.filters))
-            bias = conv._cached("bias", lambda: E._f32(conv.biases)) if conv.biases is not None else None
-            y = E.patch_embed4(x, w64, bias, norm.weight.detach(), norm.bias.detach(), norm.epsilon)
+            y = E.patch_embed4(x, w64, conv.bias32(), norm.weight.detach(), norm.bias.detach(), norm.epsilon)
             return y.view(x.shape[0], x.shape[2] // 4, x.shape[3] // 4, D)
         if not x.permute(0, 2, 3, 1).is_contiguous():
             y = conv.run_stem(x, 4)                                                # 4x4 / 4 conv == 1x1 conv on 48 folded channels

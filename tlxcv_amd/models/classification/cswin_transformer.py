@@ -23,7 +23,7 @@ import torch
 from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc
-from .vision_transformer import DropPath
+from ..common import DropPath, token_rows
 
 __all__ = ["CSwinTransformer", "CSwintransformer_thiny", "PatchEmbedding", "LePEAttention", "CSwinBlock", "MergeBlock", "CSwinStage",
            "pack_lepe"]
@@ -37,16 +37,6 @@ def pack_lepe(get_vs, dtype):
         return w, None
     b = torch.cat([g.biases.detach().float() if g.biases is not None else torch.zeros(g.out_channels, device=w.device) for g in get_vs])
     return w, b.contiguous()
-
-
-def _rows(x, what):
-    """(B, N, C) tokens in the engine's precision, dense."""
-    E.need_gpu(x, "input")
-    if x.dim() != 3:
-        raise RuntimeError(f"{what}: (B, N, C) tokens are expected, got {tuple(x.shape)}")
-    if x.dtype != E.precision():
-        x = x.to(E.precision())
-    return x if x.is_contiguous() else x.contiguous()
 
 
 class PatchEmbedding(nn.Module):
@@ -76,7 +66,7 @@ class Mlp(nn.Module):
 
     def forward(self, x):
         self._require_eval()
-        return self.fc2.run(self.fc1.run(_rows(x, "Mlp"), act=E.ACT_GELU))
+        return self.fc2.run(self.fc1.run(token_rows(x, "Mlp"), act=E.ACT_GELU))
 
 
 class LePEAttention(nn.Module):
@@ -98,7 +88,7 @@ class LePEAttention(nn.Module):
 
     def forward(self, q, k, v):
         self._require_eval()
-        qkv = torch.cat((_rows(q, "LePEAttention"), _rows(k, "LePEAttention"), _rows(v, "LePEAttention")), -1)
+        qkv = torch.cat((token_rows(q, "LePEAttention"), token_rows(k, "LePEAttention"), token_rows(v, "LePEAttention")), -1)
         w, b = self._cached("lepe", lambda: pack_lepe([self.get_v], E.precision()), deps=(self.get_v,))
         return E.cswin_attention(qkv, qkv.shape[0], self.resolution, self.resolution, self.num_heads, [(self.h_split, self.w_split)], w, b,
                                  self.scale)
@@ -167,7 +157,7 @@ class CSwinBlock(nn.Module):
 
     def forward(self, x):
         self._require_eval()
-        return self.run_rows(_rows(x, "CSwinBlock"))[0]
+        return self.run_rows(token_rows(x, "CSwinBlock"))[0]
 
 
 class MergeBlock(nn.Module):
@@ -180,7 +170,7 @@ class MergeBlock(nn.Module):
 
     def forward(self, x):
         self._require_eval()
-        x = _rows(x, "MergeBlock")
+        x = token_rows(x, "MergeBlock")
         B, HW, Cc = x.shape
         H = int(round(HW ** 0.5))
         if H * H != HW:
@@ -205,7 +195,7 @@ class CSwinStage(nn.Module):
 
     def forward(self, x):
         self._require_eval()
-        x = _rows(x, "CSwinStage")
+        x = token_rows(x, "CSwinStage")
         rows, Cc = x.shape[0] * x.shape[1], x.shape[2]
         part = None
         for i, blk in enumerate(self.blocks):

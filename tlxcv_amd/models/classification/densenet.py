@@ -23,16 +23,10 @@ from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
 from ...tlx.nn.initializers import random_uniform, xavier_uniform
+from ..common import NHWCBlock
 
 __all__ = ['DenseNet', 'densenet121', 'densenet161', 'densenet169', 'densenet201', 'densenet264', 'BNACConvLayer', 'DenseLayer',
            'DenseBlock', 'TransitionLayer', 'ConvBNLayer']
-
-
-class _Named(nn.Module):
-    def add_sublayer(self, name, sublayer):
-        """Paddle's Layer.add_sublayer: register `sublayer` under `name` and return it."""
-        self.add_module(name, sublayer)
-        return sublayer
 
 
 def _folded(bn):
@@ -61,15 +55,10 @@ class BNACConvLayer(nn.Module):
         that FOLLOWS the conv, taken in its epilogue.  out / out_ld: a column slice of a wider buffer to write into."""
         self._require_eval()
         conv, bn = self._conv, self.batch_norm
-        dt = E.precision()
         ps, pt = _folded(bn)
-        if bn_out is not None:
-            scale, shift = conv._cached(("bn", id(bn_out)), lambda: bn_out.folded(None), deps=(bn_out,))
-        else:
-            scale, shift = None, None
+        scale, shift = conv.affine(bn_out)              # (the conv has no bias)
         if conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.n_group == 1 and self._pre_act is not None:
-            pk = conv._cached("pk", lambda: E.PackedFilter(conv.filters, dt))
-            return E.preact_conv1x1(v, ps, pt, pk, scale, shift, act=act, out=out, out_ld=out_ld, pre_act=self._pre_act)
+            return E.preact_conv1x1(v, ps, pt, conv.packed(), scale, shift, act=act, out=out, out_ld=out_ld, pre_act=self._pre_act)
         if v.shape[-1] != conv.in_channels or self._pre_act is None:
             raise NotImplementedError("BNACConvLayer: a conv that is not 1x1 reads a dense map, behind BatchNorm + ReLU or BatchNorm alone")
         t = E.affine_act(v, ps, pt, act=self._pre_act)
@@ -99,8 +88,7 @@ class DenseLayer(nn.Module):
         f1, f2 = self.bn_ac_func1, self.bn_ac_func2
         t = f1.run_nhwc(buf, f2.batch_norm, E.ACT_RELU)                # bn1 + relu -> 1x1 -> bn2 + relu, one launch
         conv = f2._conv
-        pk = conv._cached("pk", lambda: E.PackedFilter(conv.filters, E.precision()))
-        E.conv2d(t, pk, conv.stride, conv.padding, conv.dilation, out=buf[..., c:c + g], out_ld=buf.shape[-1])
+        E.conv2d(t, conv.packed(), conv.stride, conv.padding, conv.dilation, out=buf[..., c:c + g], out_ld=buf.shape[-1])
         return buf
 
     def forward(self, input):
@@ -109,11 +97,11 @@ class DenseLayer(nn.Module):
         if v.shape[-1] != self.num_channels:
             raise RuntimeError(f"DenseLayer: {self.num_channels} input channels expected (a multiple of {E.vec(E.precision())})")
         buf = _block_buffer(v, self.num_channels + self.growth_rate)
-        E.copy_channels_into(v if v.is_contiguous() else v.contiguous(), buf, 0)
+        E.copy_channels_into(v, buf, 0)
         return from_nhwc(self.run_into(buf), 'channels_first')
 
 
-class DenseBlock(_Named):
+class DenseBlock(nn.Module):
     """densenet.py:71-89."""
 
     def __init__(self, num_channels, num_layers, bn_size, growth_rate, dropout, name=None):
@@ -139,11 +127,11 @@ class DenseBlock(_Named):
         if v.shape[-1] != self.num_channels:
             raise RuntimeError(f"DenseBlock: {self.num_channels} input channels expected (a multiple of {E.vec(E.precision())})")
         buf = _block_buffer(v, self.out_channels)
-        E.copy_channels_into(v if v.is_contiguous() else v.contiguous(), buf, 0)
+        E.copy_channels_into(v, buf, 0)
         return from_nhwc(self.run_into(buf), 'channels_first')
 
 
-class TransitionLayer(nn.Module):
+class TransitionLayer(NHWCBlock):
     """densenet.py:92-104."""
 
     def __init__(self, num_channels, num_output_features):
@@ -158,11 +146,6 @@ class TransitionLayer(nn.Module):
             raise RuntimeError(f"DenseNet: a {t.shape[1]} x {t.shape[2]} map is smaller than the transition's 2 x 2 pool")
         p = self.pool2d_avg
         return E.avgpool2d(t, p.kernel_size, p.stride, p.padding, out=out, out_ld=out_ld)
-
-    def forward(self, input):
-        self._require_eval()
-        v = as_nhwc(input, 'channels_first')
-        return from_nhwc(self.run_nhwc(v if v.is_contiguous() else v.contiguous()), 'channels_first')
 
 
 class ConvBNLayer(nn.Module):
@@ -184,7 +167,7 @@ class ConvBNLayer(nn.Module):
         return self.batch_norm(self._conv(input))
 
 
-class DenseNet(_Named):
+class DenseNet(nn.Module):
     """densenet.py:125-211.
 
     Args:

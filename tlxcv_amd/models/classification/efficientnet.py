@@ -21,6 +21,7 @@ import torch
 from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
+from ..common import make_divisible
 
 __all__ = ["efficientnet", "EfficientNet"]
 
@@ -44,15 +45,6 @@ class StochasticDepth(nn.Module):
     def forward(self, input):
         self._require_eval()
         return input
-
-
-def _make_divisible(v, divisor, min_value=None):
-    if min_value is None:
-        min_value = divisor
-    new_v = max(min_value, int(v + divisor / 2) // divisor * divisor)
-    if new_v < 0.9 * v:
-        new_v += divisor
-    return new_v
 
 
 class ConvNormActivation(nn.Sequential):
@@ -122,7 +114,7 @@ class MBConvConfig:
 
     @staticmethod
     def adjust_channels(channels, width_mult, min_value=None):
-        return _make_divisible(channels * width_mult, 8, min_value)
+        return make_divisible(channels * width_mult, 8, min_value)
 
     @staticmethod
     def adjust_depth(num_layers, depth_mult):

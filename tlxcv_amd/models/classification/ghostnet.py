@@ -24,31 +24,16 @@ import torch
 
 from ... import engine as E
 from ...tlx import nn
-from ...tlx.nn import as_nhwc, from_nhwc
+from ...tlx.nn import as_nhwc
 from ...tlx.nn.initializers import xavier_uniform
+from ..common import NHWCBlock, make_divisible, pitched
 
 __all__ = ['GhostNet', 'ConvBNLayer', 'SEBlock', 'GhostModule', 'GhostBottleneck', 'ghostnet_x0_5', 'ghostnet_x1_0', 'ghostnet_x1_3']
 
 
-def _pitched(like, H, W, channels):
-    """A dense (N, H, W, shuffle_pitch(channels)) buffer for a `channels`-wide map: zero filled where the pitch is wider than the map."""
-    pitch = E.shuffle_pitch(channels)
-    make = torch.zeros if pitch != channels else torch.empty
-    return make((like.shape[0], H, W, pitch), dtype=like.dtype, device=like.device)
-
-
-class _NHWC(nn.Module):
-    """forward() on a logical (B, C, H, W) tensor around run_nhwc() (a channel axis it has to pad is padded with zeros: the pitch rule)."""
-
-    def forward(self, inputs):
-        self._require_eval()
-        v = as_nhwc(inputs, 'channels_first')
-        y = self.run_nhwc(v if v.is_contiguous() else v.contiguous())
-        return from_nhwc(y, 'channels_first', self.out_channels)
-
-
-class ConvBNLayer(_NHWC):
+class ConvBNLayer(NHWCBlock):
     """ghostnet.py:26-44: conv (no bias, padding (k - 1) // 2) -> BatchNorm (-> ReLU)."""
+    CROP = True
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, groups=1, act='relu', name=None):
         super().__init__()
@@ -64,24 +49,7 @@ class ConvBNLayer(_NHWC):
 
     def folded(self):
         """(scale, shift) of the BatchNorm, cached on the conv."""
-        conv, bn = self._conv, self.batch_norm
-        return conv._cached(("bn", id(bn)), lambda: bn.folded(conv.biases), deps=(bn,))
-
-    def _dw_padded(self, width):
-        """The depthwise [R][S][width] filter and folded BatchNorm [width], zero filled behind the conv's channels: the conv then runs
-        over a map's whole pitch and leaves zeros in the pad columns."""
-        conv = self._conv
-
-        def build():
-            dt = E.precision()
-            c = conv.in_channels
-            s, t = self.folded()
-            w = torch.zeros(conv.kernel_size + (width,), dtype=dt, device=s.device)
-            w[..., :c] = conv.filters.detach()[:, 0].permute(1, 2, 0).to(dt)
-            sp, tp = torch.zeros(width, dtype=torch.float32, device=s.device), torch.zeros(width, dtype=torch.float32, device=s.device)
-            sp[:c], tp[:c] = s, t
-            return w, sp, tp
-        return conv._cached(("dw_padded", width), build, deps=(self.batch_norm,))
+        return self._conv.folded(self.batch_norm)
 
     def run_nhwc(self, v):
         """v (N, H, W, pitch >= in_channels, the columns behind in_channels zero) -> (N, Ho, Wo, roundup(out_channels, 8)), the columns
@@ -91,16 +59,17 @@ class ConvBNLayer(_NHWC):
         if self.groups == 1:
             k, s, p = conv.kernel_size, conv.stride, conv.padding
             Ho, Wo = (v.shape[1] + 2 * p[0] - k[0]) // s[0] + 1, (v.shape[2] + 2 * p[1] - k[1]) // s[1] + 1
-            out = _pitched(v, Ho, Wo, self.out_channels)
+            out = pitched(v, Ho, Wo, self.out_channels, E.SHUFFLE_PAD)
             return conv.run_nhwc(v, self.batch_norm, act=self._act, out=out, out_ld=out.shape[-1])
         if self.groups != self.in_channels or self.in_channels != self.out_channels:
             raise NotImplementedError("ConvBNLayer: dense or depthwise convs (what GhostNet builds)")
-        w, sc, sh = self._dw_padded(v.shape[-1])
+        w, sc, sh = conv.dw_padded(v.shape[-1], self.batch_norm)      # over the whole pitch: the pad columns stay zero
         return E.dwconv2d(v, w, conv.stride, conv.padding, 1, sc, sh, act=self._act)
 
 
-class SEBlock(_NHWC):
+class SEBlock(NHWCBlock):
     """ghostnet.py:47-71: x * clip(excitation(relu(squeeze(mean(x)))), 0, 1)."""
+    CROP = True
 
     def __init__(self, num_channels, reduction_ratio=4, name=None):
         super().__init__()
@@ -126,15 +95,16 @@ class SEBlock(_NHWC):
         N, pitch = v.shape[0], v.shape[-1]
         pk1, b1, pk2, six, shift = self._packed()
         s = E.global_avgpool(v).view(N, 1, 1, pitch)
-        t = _pitched(s, 1, 1, pk1.Cout)
+        t = pitched(s, 1, 1, pk1.Cout, E.SHUFFLE_PAD)
         E.conv2d(s, pk1, 1, 0, 1, None, b1, act=E.ACT_RELU, out=t, out_ld=t.shape[-1])
-        g = torch.zeros_like(s) if pitch != pk2.Cout else torch.empty_like(s)
+        g = pitched(s, 1, 1, pk2.Cout, pitch)                   # the gate keeps v's own pitch
         E.conv2d(t, pk2, 1, 0, 1, six, shift, act=E.ACT_HARDSIGMOID, out=g, out_ld=pitch)       # clip(w t + b, 0, 1)
         return E.scale_channels(v, g.view(N, pitch))
 
 
-class GhostModule(_NHWC):
+class GhostModule(NHWCBlock):
     """ghostnet.py:74-94."""
+    CROP = True
 
     def __init__(self, in_channels, output_channels, kernel_size=1, ratio=2, dw_size=3, stride=1, relu=True, name=None):
         super().__init__()
@@ -164,8 +134,9 @@ class GhostModule(_NHWC):
         return E.ghost_module(v, self.module_params(), self._act, res=res)
 
 
-class GhostBottleneck(_NHWC):
+class GhostBottleneck(NHWCBlock):
     """ghostnet.py:97-140."""
+    CROP = True
 
     def __init__(self, in_channels, hidden_dim, output_channels, kernel_size, stride, use_se, name=None):
         super().__init__()
@@ -220,21 +191,21 @@ class GhostNet(nn.Module):
                      [5, 960, 160, 0, 1], [5, 960, 160, 1, 1], [5, 960, 160, 0, 1], [5, 960, 160, 1, 1]]
         self.scale = scale
         self.class_num = class_num
-        output_channels = int(self._make_divisible(16 * self.scale, 4))
+        output_channels = int(make_divisible(16 * self.scale, 4))
         self.conv1 = ConvBNLayer(in_channels=3, out_channels=output_channels, kernel_size=3, stride=2, groups=1, act='relu', name='conv1')
         idx = 0
         self.ghost_bottleneck_list = []
         for k, exp_size, c, use_se, s in self.cfgs:
             in_channels = output_channels
-            output_channels = int(self._make_divisible(c * self.scale, 4))
-            hidden_dim = int(self._make_divisible(exp_size * self.scale, 4))
+            output_channels = int(make_divisible(c * self.scale, 4))
+            hidden_dim = int(make_divisible(exp_size * self.scale, 4))
             ghost_bottleneck = self.add_sublayer(name='_ghostbottleneck_' + str(idx), sublayer=GhostBottleneck(
                 in_channels=in_channels, hidden_dim=hidden_dim, output_channels=output_channels, kernel_size=k, stride=s, use_se=use_se,
                 name='_ghostbottleneck_' + str(idx)))
             self.ghost_bottleneck_list.append(ghost_bottleneck)
             idx += 1
         in_channels = output_channels
-        output_channels = int(self._make_divisible(exp_size * self.scale, 4))
+        output_channels = int(make_divisible(exp_size * self.scale, 4))
         self.conv_last = ConvBNLayer(in_channels=in_channels, out_channels=output_channels, kernel_size=1, stride=1, groups=1, act='relu',
                                      name='conv_last')
         self.pool2d_gap = nn.AdaptiveAvgPool2d(1, data_format='channels_first')
@@ -265,12 +236,7 @@ class GhostNet(nn.Module):
 
     def _make_divisible(self, v, divisor, min_value=None):
         """ghostnet.py:200-212."""
-        if min_value is None:
-            min_value = divisor
-        new_v = max(min_value, int(v + divisor / 2) // divisor * divisor)
-        if new_v < 0.9 * v:
-            new_v += divisor
-        return new_v
+        return make_divisible(v, divisor, min_value)
 
 
 def _ghostnet(arch, scale, pretrained=False, **kwargs):

@@ -28,6 +28,7 @@ from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
 from ...tlx.nn.initializers import random_uniform
+from ..common import NHWCBlock
 
 __all__ = ['GoogLeNet', 'ConvLayer', 'Inception', 'googlenet']
 
@@ -50,8 +51,7 @@ class ConvLayer(nn.Module):
 
     def packed(self):
         """The conv's PackedFilter at the current precision."""
-        conv = self._conv
-        return conv._cached("pk", lambda: E.PackedFilter(conv.filters, E.precision()))
+        return self._conv.packed()
 
     def run_nhwc(self, v, act=E.ACT_NONE):
         self._require_eval()
@@ -62,7 +62,7 @@ class ConvLayer(nn.Module):
         return from_nhwc(self.run_nhwc(as_nhwc(inputs, 'channels_first')), 'channels_first', self._conv.out_channels)
 
 
-class Inception(nn.Module):
+class Inception(NHWCBlock):
     """googlenet.py:41-65.  (`output_channels` is unused there too.)"""
 
     def __init__(self, input_channels, output_channels, filter1, filter3R, filter3, filter5R, filter5, proj):
@@ -93,11 +93,6 @@ class Inception(nn.Module):
         E.conv2d(t[..., p.t5:p.t5 + p.f5r], self._conv5.packed(), 1, 2, 1, act=E.ACT_RELU, out=y[..., p.o5y:p.o5y + p.f5], out_ld=p.cout,
                  x_ld=p.t_ld)
         return y
-
-    def forward(self, inputs):
-        self._require_eval()
-        v = as_nhwc(inputs, 'channels_first')
-        return from_nhwc(self.run_nhwc(v if v.is_contiguous() else v.contiguous()), 'channels_first')
 
 
 class GoogLeNet(nn.Module):
@@ -181,8 +176,7 @@ class GoogLeNet(nn.Module):
             wt = fc.weights.detach().view(c, h, w, fc.out_features).permute(1, 2, 0, 3).reshape(fc.in_features, fc.out_features)
             return E.PackedFilter(wt.t().contiguous(), E.precision())
         pk = fc._cached(("pk_nhwc", h, w), build)
-        b = fc._cached("bias", lambda: E._f32(fc.biases)) if fc.biases is not None else None
-        return out.run(E.linear(u.view(N, h * w * c), pk, b, None, act))
+        return out.run(E.linear(u.view(N, h * w * c), pk, fc.bias32(), None, act))
 
     def forward(self, inputs, fused=None):
         out, out1, out2 = self.forward_features(inputs, fused)

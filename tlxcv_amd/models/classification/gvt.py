@@ -381,7 +381,7 @@ class PosCNN(nn.Module):
         if self.s != 1 or conv.n_group != conv.in_channels or conv.in_channels != conv.out_channels:
             y = conv.run_nhwc(v)
             return E.affine_act(y, res=v) if self.s == 1 else y
-        bias = conv._cached("bias", lambda: E._f32(conv.biases)) if conv.biases is not None else None
+        bias = conv.bias32()
         return E.dwconv2d(v, self.folded_taps(), 1, 1, 1, None, bias)
 
     def forward(self, x, H, W):

@@ -38,27 +38,10 @@ import torch
 from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc
+from ..common import act_code, token_rows
 
 __all__ = ["LeViT", "model_factory", "Attention", "AttentionSubsample", "Subsample", "Residual", "Conv2d_BN", "Linear_BN", "BN_Linear",
            "b16", "levit_128s", "levit_128", "levit_192", "levit_256", "levit_384", "specification"]
-
-
-def _rows(x, what):
-    """(B, N, C) tokens in the engine's precision, dense."""
-    E.need_gpu(x, "input")
-    if x.dim() != 3:
-        raise RuntimeError(f"{what}: (B, N, C) tokens are expected, got {tuple(x.shape)}")
-    if x.dtype != E.precision():
-        x = x.to(E.precision())
-    return x if x.is_contiguous() else x.contiguous()
-
-
-def _act_code(layer, what):
-    if isinstance(layer, nn.Identity):
-        return E.ACT_NONE
-    if not hasattr(layer, "ACT"):
-        raise NotImplementedError(f"{what}: activation {type(layer).__name__} has no epilogue form")
-    return layer.ACT
 
 
 def _n_offsets(Rq, Rk, stride):
@@ -181,11 +164,11 @@ class Residual(nn.Module):
 
     def forward(self, x):
         self._require_eval()
-        x = _rows(x, "Residual")
+        x = token_rows(x, "Residual")
         if isinstance(self.m, Attention):
             return self.m.run_rows(x, res=x)
         if _is_mlp(self.m):
-            return self.m[2].run(self.m[0].run(x, act=_act_code(self.m[1], "Residual")), res=x)
+            return self.m[2].run(self.m[0].run(x, act=act_code(self.m[1], "Residual")), res=x)
         raise NotImplementedError(f"Residual around {type(self.m).__name__}: Attention or Linear_BN / activation / Linear_BN is expected")
 
 
@@ -218,11 +201,11 @@ class Attention(nn.Module):
             raise RuntimeError(f"Attention: {self.resolution ** 2} tokens are expected (the bias table is sized at construction), got {N}")
         qkv = self.qkv.run(x)                                                                          # :202
         a = E.levit_attention(qkv, self.bias_grid(), self.num_heads, self.key_dim, self.d, self.resolution, self.scale,
-                              act=_act_code(self.proj[0], "Attention"))                                # :203-222 + the activation of :170
+                              act=act_code(self.proj[0], "Attention"))                                # :203-222 + the activation of :170
         return self.proj[1].run(a, res=res)                                                            # :223
 
     def forward(self, x):
-        return self.run_rows(_rows(x, "Attention"))
+        return self.run_rows(token_rows(x, "Attention"))
 
 
 class Subsample(nn.Module):
@@ -267,7 +250,7 @@ class AttentionSubsample(nn.Module):
 
     def forward(self, x):
         self._require_eval()
-        x = _rows(x, "AttentionSubsample")
+        x = token_rows(x, "AttentionSubsample")
         B, N, Cc = x.shape
         R = self.resolution
         if N != R * R:
@@ -275,7 +258,7 @@ class AttentionSubsample(nn.Module):
         kv = self.kv.run(x)                                                                            # :304
         q = self.q[1].run_conv1x1(x.view(B, R, R, Cc), self.stride).view(B, self.resolution_2, self.nh_kd)      # :309
         a = E.levit_attention(kv, self.bias_grid(), self.num_heads, self.key_dim, self.d, R, self.scale, q=q, Rq=self.resolution_,
-                              stride=self.stride, act=_act_code(self.proj[0], "AttentionSubsample"))   # :305-321 + the activation of :262
+                              stride=self.stride, act=act_code(self.proj[0], "AttentionSubsample"))   # :305-321 + the activation of :262
         return self.proj[1].run(a)                                                                     # :322
 
 
@@ -329,7 +312,7 @@ class LeViT(nn.Module):
                 raise NotImplementedError(f"LeViT: the stem is Conv2d_BN layers with activations between them, got {type(conv).__name__}")
             act = E.ACT_NONE
             if i + 1 < len(layers) and not isinstance(layers[i + 1], Conv2d_BN):
-                act = _act_code(layers[i + 1], "LeViT stem")
+                act = act_code(layers[i + 1], "LeViT stem")
                 i += 1
             if v is None:
                 c = conv.c

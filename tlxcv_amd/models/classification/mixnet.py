@@ -26,7 +26,8 @@ import torch
 
 from ... import _lib, engine as E
 from ...tlx import nn
-from ...tlx.nn import as_nhwc, from_nhwc
+from ...tlx.nn import as_nhwc
+from ..common import NHWCBlock, act_code, pitched
 
 __all__ = ['MixNet', 'MixUnit', 'MixInitBlock', 'MixConv', 'MixConvBlock', 'ConvBlock', 'SEBlock', 'mixconv1x1_block', 'round_channels',
            'get_activation_layer', 'get_mixnet', 'mixnet_s', 'mixnet_m', 'mixnet_l']
@@ -55,26 +56,7 @@ def get_activation_layer(activation):
     return activation
 
 
-def _act_code(layer):
-    """The engine's activation code of an activation layer (None: no activation)."""
-    if layer is None or isinstance(layer, nn.Identity):
-        return E.ACT_NONE
-    if not hasattr(layer, 'ACT') or getattr(layer, 'PARAM', 0.0):
-        raise NotImplementedError(f"MixNet: activation layer {type(layer).__name__}")
-    return layer.ACT
-
-
-class _NHWC(nn.Module):
-    """forward() on a logical (B, C, H, W) tensor around run_nhwc()."""
-
-    def forward(self, x):
-        self._require_eval()
-        v = as_nhwc(x, 'channels_first')
-        y = self.run_nhwc(v if v.is_contiguous() else v.contiguous())
-        return from_nhwc(y, 'channels_first')
-
-
-class ConvBlock(_NHWC):
+class ConvBlock(NHWCBlock):
     """mixnet.py:94-149: conv -> BatchNorm -> activation."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1, groups=1, bias=False, use_bn=True, bn_eps=1e-05,
@@ -92,14 +74,14 @@ class ConvBlock(_NHWC):
             self.bn = nn.BatchNorm2d(num_features=out_channels, epsilon=bn_eps, data_format='channels_first')
         if self.activate:
             self.activ = get_activation_layer(activation)
-        self._act = _act_code(self.activ if self.activate else None)
+        self._act = act_code(self.activ if self.activate else None, "MixNet")
 
     def run_nhwc(self, v, res=None):
         self._require_eval()
         return self.conv.run_nhwc(v, self.bn if self.use_bn else None, act=self._act, res=res)
 
 
-class SEBlock(_NHWC):
+class SEBlock(NHWCBlock):
     """mixnet.py:152-192: x * sigmoid(conv2(act(conv1(mean(x))))); the two 1x1 convs carry no bias (b_init=())."""
 
     def __init__(self, channels, reduction=16, mid_channels=None, round_mid=False, use_conv=True, mid_activation='relu', out_activation='sigmoid'):
@@ -140,14 +122,13 @@ class SEBlock(_NHWC):
             raise RuntimeError(f"SEBlock: a map of {self.channels} channels is expected, got {tuple(v.shape)}")
         pk1, b1, pk2, b2 = self._packed()
         s = (E.global_avgpool(v) if pooled is None else pooled).view(N, 1, 1, Cc)
-        pitch = E.shuffle_pitch(self.mid_channels)          # the hidden row: zero filled up to the next filter's padded width
-        t = (torch.zeros if pitch != self.mid_channels else torch.empty)((N, 1, 1, pitch), dtype=s.dtype, device=s.device)
-        E.conv2d(s, pk1, 1, 0, 1, None, b1, act=_act_code(self.activ), out=t, out_ld=pitch)
-        g = E.conv2d(t, pk2, 1, 0, 1, None, b2, act=_act_code(self.sigmoid))
+        t = pitched(s, 1, 1, self.mid_channels, E.SHUFFLE_PAD)      # the hidden row: zero filled up to the next filter's padded width
+        E.conv2d(s, pk1, 1, 0, 1, None, b1, act=act_code(self.activ, "MixNet"), out=t, out_ld=t.shape[-1])
+        g = E.conv2d(t, pk2, 1, 0, 1, None, b2, act=act_code(self.sigmoid, "MixNet"))
         return E.scale_channels(v, g.view(N, Cc))
 
 
-class MixConv(_NHWC):
+class MixConv(NHWCBlock):
     """mixnet.py:195-258: the channels are split into len(kernel_size) groups, each with its own conv; the outputs are concatenated."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1, groups=1, bias=False, axis=1):
@@ -237,7 +218,7 @@ class MixConv(_NHWC):
         return E.conv2d(v, pk, 1, 0, 1, scale, shift, res, act)
 
 
-class MixConvBlock(_NHWC):
+class MixConvBlock(NHWCBlock):
     """mixnet.py:261-314: MixConv -> BatchNorm -> activation."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1, groups=1, bias=False, use_bn=True, bn_eps=1e-05,
@@ -251,7 +232,7 @@ class MixConvBlock(_NHWC):
             self.bn = nn.BatchNorm2d(num_features=out_channels, epsilon=bn_eps, data_format='channels_first')
         if self.activate:
             self.activ = get_activation_layer(activation)
-        self._act = _act_code(self.activ if self.activate else None)
+        self._act = act_code(self.activ if self.activate else None, "MixNet")
 
     def run_nhwc(self, v, pool=False, res=None):
         self._require_eval()
@@ -264,7 +245,7 @@ def mixconv1x1_block(in_channels, out_channels, kernel_count, stride=1, groups=1
                         padding=[0] * kernel_count, groups=groups, bias=bias, use_bn=use_bn, bn_eps=bn_eps, activation=activation)
 
 
-class MixUnit(_NHWC):
+class MixUnit(NHWCBlock):
     """mixnet.py:349-430: [expansion 1x1] -> (mixed) depthwise conv -> [SE] -> projection 1x1 (+ x)."""
 
     def __init__(self, in_channels, out_channels, stride, exp_kernel_count, conv1_kernel_count, conv2_kernel_count, exp_factor, se_factor,
@@ -314,7 +295,7 @@ class MixUnit(_NHWC):
         return self.conv2.run_nhwc(x, res=v if self.residual else None)     # x + identity (:428-429) in the projection's epilogue
 
 
-class MixInitBlock(_NHWC):
+class MixInitBlock(NHWCBlock):
     """mixnet.py:433-457."""
 
     def __init__(self, in_channels, out_channels):

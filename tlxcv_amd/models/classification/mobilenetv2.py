@@ -12,28 +12,14 @@ from ... import engine as E
 from ... import tlx
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
+from ..common import NHWCBlock, make_divisible
 from .mobilenetv1 import ConvNormActivation
 
 __all__ = ["MobileNetV2", "mobilenet_v2", "MobileNetV3Small", "MobileNetV3Large", "mobilenet_v3_small",
            "mobilenet_v3_large"]
 
 
-def _make_divisible(v, divisor=8, min_value=None):
-    """utils/common_func.py:1-16."""
-    if min_value is None:
-        min_value = divisor
-    new_v = max(min_value, int(v + divisor / 2) // divisor * divisor)
-    if new_v < 0.9 * v:
-        new_v += divisor
-    return new_v
-
-
-class _NHWCBlock(nn.Module):
-    def forward(self, x):
-        return from_nhwc(self.run_nhwc(as_nhwc(x, 'channels_first')), 'channels_first')
-
-
-class InvertedResidual(_NHWCBlock):
+class InvertedResidual(NHWCBlock):
     """mobilenetv2.py:15-40."""
 
     def __init__(self, inp, oup, stride, expand_ratio, batch_norm=nn.BatchNorm2d):
@@ -71,11 +57,11 @@ class MobileNetV2(nn.Module):
         input_channel, last_channel, round_nearest = 32, 1280, 8
         setting = [[1, 16, 1, 1], [6, 24, 2, 2], [6, 32, 3, 2], [6, 64, 4, 2], [6, 96, 3, 1], [6, 160, 3, 2],
                    [6, 320, 1, 1]]
-        input_channel = _make_divisible(input_channel * scale, round_nearest)
-        self.last_channel = _make_divisible(last_channel * max(1.0, scale), round_nearest)
+        input_channel = make_divisible(input_channel * scale, round_nearest)
+        self.last_channel = make_divisible(last_channel * max(1.0, scale), round_nearest)
         features = [ConvNormActivation(3, input_channel, stride=2, activation_layer=nn.ReLU6)]
         for t, c, n, s in setting:
-            output_channel = _make_divisible(c * scale, round_nearest)
+            output_channel = make_divisible(c * scale, round_nearest)
             for i in range(n):
                 features.append(InvertedResidual(input_channel, output_channel, s if i == 0 else 1, expand_ratio=t))
                 input_channel = output_channel
@@ -108,7 +94,7 @@ def mobilenet_v2(pretrained=False, scale=1.0, **kwargs):
 
 
 # ---------------------------------------------------------------------------------------------
-class SqueezeExcitation(_NHWCBlock):
+class SqueezeExcitation(NHWCBlock):
     """mobilenetv3.py:21-56: scale = sigma(fc2(delta(fc1(avgpool(x))))); return scale * x."""
 
     def __init__(self, input_channels, squeeze_channels, activation=nn.ReLU, scale_activation=nn.Sigmoid):
@@ -148,10 +134,10 @@ class InvertedResidualConfig:
 
     @staticmethod
     def adjust_channels(channels, scale=1.0):
-        return _make_divisible(channels * scale, 8)
+        return make_divisible(channels * scale, 8)
 
 
-class InvertedResidualV3(_NHWCBlock):
+class InvertedResidualV3(NHWCBlock):
     """mobilenetv3.py:84-121."""
 
     def __init__(self, in_channels, expanded_channels, out_channels, filter_size, stride, use_se, activation_layer,
@@ -169,7 +155,7 @@ class InvertedResidualV3(_NHWCBlock):
                                                   padding=int((filter_size - 1) // 2), groups=expanded_channels,
                                                   batch_norm=batch_norm, activation_layer=activation_layer)
         if self.use_se:
-            self.mid_se = SqueezeExcitation(expanded_channels, _make_divisible(expanded_channels // 4),
+            self.mid_se = SqueezeExcitation(expanded_channels, make_divisible(expanded_channels // 4),
                                             scale_activation=nn.HardSigmoid)
         self.linear_conv = ConvNormActivation(in_channels=expanded_channels, out_channels=out_channels, kernel_size=1,
                                               stride=1, padding=0, batch_norm=batch_norm, activation_layer=None)
@@ -234,7 +220,7 @@ class MobileNetV3Small(MobileNetV3):
                   C(40, 5, 120, 48, True, 'hardswish', 1, scale), C(48, 5, 144, 48, True, 'hardswish', 1, scale),
                   C(48, 5, 288, 96, True, 'hardswish', 2, scale), C(96, 5, 576, 96, True, 'hardswish', 1, scale),
                   C(96, 5, 576, 96, True, 'hardswish', 1, scale)]                      # mobilenetv3.py:209-221
-        super().__init__(config, last_channel=_make_divisible(1024 * scale, 8), scale=scale, with_pool=with_pool,
+        super().__init__(config, last_channel=make_divisible(1024 * scale, 8), scale=scale, with_pool=with_pool,
                          num_classes=num_classes)
 
 
@@ -249,7 +235,7 @@ class MobileNetV3Large(MobileNetV3):
                   C(80, 3, 480, 112, True, 'hardswish', 1, scale), C(112, 3, 672, 112, True, 'hardswish', 1, scale),
                   C(112, 5, 672, 160, True, 'hardswish', 2, scale), C(160, 5, 960, 160, True, 'hardswish', 1, scale),
                   C(160, 5, 960, 160, True, 'hardswish', 1, scale)]                    # mobilenetv3.py:253-269
-        super().__init__(config, last_channel=_make_divisible(1280 * scale, 8), scale=scale, with_pool=with_pool,
+        super().__init__(config, last_channel=make_divisible(1280 * scale, 8), scale=scale, with_pool=with_pool,
                          num_classes=num_classes)
 
 

@@ -27,6 +27,7 @@ from ... import _lib, engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
 from ...tlx.nn.initializers import xavier_uniform
+from ..common import NHWCBlock
 
 __all__ = ['Res2Net', 'ConvBNLayer', 'BottleneckBlock', 'res2net']
 
@@ -36,7 +37,7 @@ def slice_pitch(w):
     return (w + 7) // 8 * 8
 
 
-class ConvBNLayer(nn.Module):
+class ConvBNLayer(NHWCBlock):
     """res2net.py:26-47: conv (no bias, padding (k - 1) // 2) -> BatchNorm (-> ReLU)."""
 
     def __init__(self, num_channels, num_filters, filter_size, stride=1, groups=1, act=None, name=None):
@@ -54,16 +55,11 @@ class ConvBNLayer(nn.Module):
 
     def folded(self):
         """(scale, shift) of the BatchNorm, cached on the conv."""
-        conv, bn = self._conv, self.batch_norm
-        return conv._cached(("bn", id(bn)), lambda: bn.folded(conv.biases), deps=(bn,))
+        return self._conv.folded(self.batch_norm)
 
     def run_nhwc(self, v, res=None, act=None):
         self._require_eval()
         return self._conv.run_nhwc(v, self.batch_norm, act=self._act if act is None else act, res=res)
-
-    def forward(self, inputs):
-        self._require_eval()
-        return from_nhwc(self.run_nhwc(as_nhwc(inputs, 'channels_first')), 'channels_first')
 
 
 class BottleneckBlock(nn.Module):

@@ -16,13 +16,14 @@ from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
 from ...tlx.nn.initializers import xavier_uniform
+from ..common import NHWCBlock
 
 __all__ = ['ResNeSt', 'resnest50_fast_1s1x64d', 'resnest50', 'resnest101']
 
 _ACT = {None: E.ACT_NONE, 'relu': E.ACT_RELU}
 
 
-class ConvBNLayer(nn.Module):
+class ConvBNLayer(NHWCBlock):
     def __init__(self, num_channels, num_filters, filter_size, stride=1, dilation=1, groups=1, act=None,
                  data_format='channels_first', name=None):
         super().__init__(name)
@@ -37,9 +38,6 @@ class ConvBNLayer(nn.Module):
     def run_nhwc(self, v, res=None, act=None):
         return self._conv.run_nhwc(v, self.batch_norm, self.act_code if act is None else act, res=res)
 
-    def forward(self, x):
-        return from_nhwc(self.run_nhwc(as_nhwc(x, self.data_format)), self.data_format)
-
 
 class rSoftmax(nn.Module):
     """resnest.py:53-82; SplatConv.run_nhwc applies it inside tlxmi_split_attention."""
@@ -49,7 +47,7 @@ class rSoftmax(nn.Module):
         self.radix, self.cardinality, self.data_format = radix, cardinality, data_format
 
 
-class SplatConv(nn.Module):
+class SplatConv(NHWCBlock):
     def __init__(self, in_channels, channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True, radix=2,
                  reduction_factor=4, rectify_avg=False, data_format='channels_first', name=None):
         super().__init__(name)
@@ -71,9 +69,6 @@ class SplatConv(nn.Module):
         gap = E.radix_gap(x1, self.radix).view(N, 1, 1, self.channels)         # :149-155
         att = self.conv3.run_nhwc(self.conv2.run_nhwc(gap))                    # :156-157
         return E.split_attention(x1, att.view(N, self.channels * self.radix), self.radix, self.cardinality)   # :158-165
-
-    def forward(self, x):
-        return from_nhwc(self.run_nhwc(as_nhwc(x, self.data_format)), self.data_format)
 
 
 class BottleneckBlock(nn.Module):
@@ -163,11 +158,9 @@ class BottleneckBlock(nn.Module):
         n_img = y.shape[0]
         if n_img < 12 or (c3.in_channels >= 256 and n_img < 96 and not E.in_halves()):
             return None
-        pk3 = c3._cached("pk", lambda: E.PackedFilter(c3.filters, dt))
-        pk1 = c1._cached("pk", lambda: E.PackedFilter(c1.filters, dt))
-        bn3, bn1 = self.conv3.batch_norm, nxt.conv1.batch_norm
-        s3, h3 = c3._cached(("bn", id(bn3)), lambda: bn3.folded(None), deps=(bn3,))
-        s1, h1 = c1._cached(("bn", id(bn1)), lambda: bn1.folded(None), deps=(bn1,))
+        pk3, pk1 = c3.packed(), c1.packed()
+        s3, h3 = c3.folded(self.conv3.batch_norm)
+        s1, h1 = c1.folded(nxt.conv1.batch_norm)
         return E.bottleneck_seam(y, pk3, s3, h3, self.skip(v), pk1, s1, h1)
 
     def forward(self, x):

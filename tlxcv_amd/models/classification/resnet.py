@@ -201,10 +201,9 @@ class BottleneckBlock(nn.Module):
         #  SEAM14_IMAGES above)
         if n_img < 12 or (c3.in_channels >= 256 and not SEAM14_IMAGES[0] <= n_img <= SEAM14_IMAGES[1]):
             return None
-        pk3 = c3._cached("pk", lambda: E.PackedFilter(c3.filters, dt))
-        pk1 = c1._cached("pk", lambda: E.PackedFilter(c1.filters, dt))
-        s3, h3 = c3._cached(("bn", id(self.bn3)), lambda: self.bn3.folded(None), deps=(self.bn3,))
-        s1, h1 = c1._cached(("bn", id(nxt.bn1)), lambda: nxt.bn1.folded(None), deps=(nxt.bn1,))
+        pk3, pk1 = c3.packed(), c1.packed()
+        s3, h3 = c3.folded(self.bn3)
+        s1, h1 = c1.folded(nxt.bn1)
         if self.downsample is None:
             N, H, W, _ = out.shape
             dec = y_stride2 and E.bottleneck_seam_dec_supported(c3.in_channels, c3.out_channels, c1.out_channels, N * H * W, H, W, dt)
@@ -214,9 +213,7 @@ class BottleneckBlock(nn.Module):
                 and c3.in_channels == 64 and c1.out_channels == 64 and cd.in_channels == 64 and v.shape[-1] == 64):
             # layer1.0: the projection shortcut (1x1, stride 1, 64 channels in) is computed inside the seam launch: its 411 MB
             # map (batch 256) is neither written nor read
-            pkd = cd._cached("pk", lambda: E.PackedFilter(cd.filters, dt))
-            sd, hd = cd._cached(("bn", id(bnd)), lambda: bnd.folded(None), deps=(bnd,))
-            return E.bottleneck_seam(out, pk3, s3, h3, v, pk1, s1, h1, proj=(pkd, sd, hd))
+            return E.bottleneck_seam(out, pk3, s3, h3, v, pk1, s1, h1, proj=(cd.packed(), *cd.folded(bnd)))
         return E.bottleneck_seam(out, pk3, s3, h3, self.shortcut(v), pk1, s1, h1)
 
 

@@ -17,6 +17,7 @@ from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc
 from ...tlx.nn.initializers import xavier_uniform
+from ..common import NHWCBlock
 
 __all__ = ['ResNeXt', 'resnext50_32x4d', 'resnext50_64x4d', 'resnext101_32x4d', 'resnext101_64x4d',
            'resnext152_32x4d', 'resnext152_64x4d']
@@ -24,7 +25,7 @@ __all__ = ['ResNeXt', 'resnext50_32x4d', 'resnext50_64x4d', 'resnext101_32x4d', 
 _ACT = {None: E.ACT_NONE, 'relu': E.ACT_RELU}
 
 
-class ConvBNLayer(nn.Module):
+class ConvBNLayer(NHWCBlock):
     def __init__(self, num_channels, num_filters, filter_size, stride=1, groups=1, act=None, name=None,
                  data_format='channels_first'):
         super().__init__(name)
@@ -39,9 +40,6 @@ class ConvBNLayer(nn.Module):
     def run_nhwc(self, v, res=None, act=None):
         """conv + BatchNorm (+ the layer's activation, or `act` when the caller fuses a later one) (+ residual)."""
         return self._conv.run_nhwc(v, self.batch_norm, self.act_code if act is None else act, res=res)
-
-    def forward(self, inputs):
-        return nn.from_nhwc(self.run_nhwc(as_nhwc(inputs, self.data_format)), self.data_format)
 
 
 class BottleneckBlock(nn.Module):
@@ -90,11 +88,9 @@ class BottleneckBlock(nn.Module):
         n_img = y.shape[0]
         if n_img < 12 or (c3.in_channels >= 256 and n_img < 96 and not E.in_halves()):
             return None
-        pk3 = c3._cached("pk", lambda: E.PackedFilter(c3.filters, dt))
-        pk1 = c1._cached("pk", lambda: E.PackedFilter(c1.filters, dt))
-        bn3, bn1 = self.conv2.batch_norm, nxt.conv0.batch_norm
-        s3, h3 = c3._cached(("bn", id(bn3)), lambda: bn3.folded(None), deps=(bn3,))
-        s1, h1 = c1._cached(("bn", id(bn1)), lambda: bn1.folded(None), deps=(bn1,))
+        pk3, pk1 = c3.packed(), c1.packed()
+        s3, h3 = c3.folded(self.conv2.batch_norm)
+        s1, h1 = c1.folded(nxt.conv0.batch_norm)
         return E.bottleneck_seam(y, pk3, s3, h3, self.skip(v), pk1, s1, h1)
 
     def forward(self, inputs):

@@ -14,11 +14,10 @@ The reference runs a stride-1 unit as split -> 1x1 + BN + act -> depthwise 3x3 +
   * the three stride-2 units run their branches on tlxmi_dwconv2d / tlxmi_conv2d and end in tlxmi_shuffle_concat;
   * the stem (3x3 / 2 + BN + act, max-pool 3 / 2 / 1), `_last_conv`, the pool and `_fc` run on what the other classifiers use.
 """
-import torch
-
 from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
+from ..common import NHWCBlock, act_code, pitched
 from .mobilenetv1 import ConvNormActivation
 
 __all__ = ['ShuffleNetV2', 'InvertedResidual', 'InvertedResidualDS', 'create_activation_layer', 'channel_shuffle', 'shufflenet_v2_x0_25',
@@ -47,58 +46,9 @@ def channel_shuffle(x, groups):
     return x.reshape(batch_size, num_channels, height, width)
 
 
-def _act_code(activation_layer):
-    return activation_layer.ACT if activation_layer is not None else E.ACT_NONE
-
-
-def _fold(cna):
-    """(scale, shift) of a ConvNormActivation's BatchNorm, cached on the conv."""
-    conv, bn = cna[0], cna[1]
-    return conv._cached(("bn", id(bn)), lambda: bn.folded(conv.biases), deps=(bn,))
-
-
-def _pk(cna):
-    conv = cna[0]
-    return conv._cached("pk", lambda: E.PackedFilter(conv.filters, E.precision()))
-
-
-def _dw_padded(cna, width):
-    """A depthwise ConvNormActivation's [3][3][width] filter and folded BatchNorm [width], zero filled behind its channels: the conv then
-    runs over a map's whole pitch and leaves zeros in the pad columns."""
-    conv = cna[0]
-
-    def build():
-        dt = E.precision()
-        c = conv.in_channels
-        s, t = _fold(cna)
-        w = torch.zeros((3, 3, width), dtype=dt, device=s.device)
-        w[..., :c] = conv.filters.detach()[:, 0].permute(1, 2, 0).to(dt)
-        sp, tp = torch.zeros(width, dtype=torch.float32, device=s.device), torch.zeros(width, dtype=torch.float32, device=s.device)
-        sp[:c], tp[:c] = s, t
-        return w, sp, tp
-    return conv._cached(("dw_padded", width), build, deps=(cna[1],))
-
-
-def _pitched(v, channels):
-    """A dense (N, H, W, pitch) buffer for a `channels`-wide map that a depthwise conv reads over its whole pitch: zero filled where the
-    pitch is wider than the map."""
-    N, H, W = v.shape[:3]
-    vw = E.vec(v.dtype)
-    pitch = (channels + vw - 1) // vw * vw
-    make = torch.zeros if pitch != channels else torch.empty
-    return make((N, H, W, pitch), dtype=v.dtype, device=v.device)
-
-
-class _Unit(nn.Module):
-    def forward(self, inputs):
-        self._require_eval()
-        v = as_nhwc(inputs, 'channels_first')       # (a channel axis it has to pad is padded with zeros: the pitch rule of the units)
-        y = self.run_nhwc(v if v.is_contiguous() else v.contiguous())
-        return from_nhwc(y, 'channels_first', self.out_channels)
-
-
-class InvertedResidual(_Unit):
+class InvertedResidual(NHWCBlock):
     """shufflenetv2.py:54-76."""
+    CROP = True
 
     def __init__(self, in_channels, out_channels, stride, activation_layer=nn.ReLU):
         super().__init__()
@@ -109,13 +59,14 @@ class InvertedResidual(_Unit):
         self._conv_linear = ConvNormActivation(in_channels=out_channels // 2, out_channels=out_channels // 2, kernel_size=1, stride=1,
                                                padding=0, groups=1, activation_layer=activation_layer)
         self.in_channels, self.out_channels, self.stride = in_channels, out_channels, stride
-        self._act = _act_code(activation_layer)
+        self._act = act_code(activation_layer, "ShuffleNetV2")
 
     def unit_params(self):
         """engine.ShuffleUnitParams of this unit at the current precision (cached; rebuilt when a weight changes)."""
         pw, dw, lin = self._conv_pw, self._conv_dw, self._conv_linear
-        return self._cached("unit", lambda: E.ShuffleUnitParams(pw[0].filters, _fold(pw), dw[0].filters, _fold(dw), lin[0].filters, _fold(lin),
-                                                                E.precision()), deps=(pw[0], pw[1], dw[0], dw[1], lin[0], lin[1]))
+        return self._cached("unit", lambda: E.ShuffleUnitParams(pw[0].filters, pw[0].folded(pw[1]), dw[0].filters, dw[0].folded(dw[1]),
+                                                                lin[0].filters, lin[0].folded(lin[1]), E.precision()),
+                            deps=(pw[0], pw[1], dw[0], dw[1], lin[0], lin[1]))
 
     def run_nhwc(self, v):
         """v (N, H, W, pitch >= in_channels) -> (N, H, W, roundup(out_channels, 8)), the columns behind out_channels zero."""
@@ -126,8 +77,9 @@ class InvertedResidual(_Unit):
         return E.shuffle_unit(v, self.unit_params(), self._act)
 
 
-class InvertedResidualDS(_Unit):
+class InvertedResidualDS(NHWCBlock):
     """shufflenetv2.py:79-107."""
+    CROP = True
 
     def __init__(self, in_channels, out_channels, stride, activation_layer=nn.ReLU):
         super().__init__()
@@ -142,7 +94,7 @@ class InvertedResidualDS(_Unit):
         self._conv_linear_2 = ConvNormActivation(in_channels=out_channels // 2, out_channels=out_channels // 2, kernel_size=1, stride=1,
                                                  padding=0, groups=1, activation_layer=activation_layer)
         self.in_channels, self.out_channels, self.stride = in_channels, out_channels, stride
-        self._act = _act_code(activation_layer)
+        self._act = act_code(activation_layer, "ShuffleNetV2")
 
     def run_nhwc(self, v):
         """v (N, H, W, pitch >= in_channels, the columns behind in_channels zero) -> (N, Ho, Wo, roundup(out_channels, 8))."""
@@ -150,18 +102,18 @@ class InvertedResidualDS(_Unit):
         if self._act is None:
             raise NotImplementedError("InvertedResidualDS: an activation the conv epilogue knows")
         s, act, h = self.stride, self._act, self.out_channels // 2
-        # branch 1: depthwise over the whole pitch (zeros stay zeros), then 1x1
-        w, sc, sh = _dw_padded(self._conv_dw_1, v.shape[-1])
-        t = E.dwconv2d(v, w, s, 1, 1, sc, sh)
-        a = _pitched(t, h)
-        E.conv2d(t, _pk(self._conv_linear_1), 1, 0, 1, *_fold(self._conv_linear_1), act=act, out=a, out_ld=a.shape[-1])
-        # branch 2: 1x1 -> depthwise -> 1x1
-        t = _pitched(v, h)
-        E.conv2d(v, _pk(self._conv_pw_2), 1, 0, 1, *_fold(self._conv_pw_2), act=act, out=t, out_ld=t.shape[-1])
-        w, sc, sh = _dw_padded(self._conv_dw_2, t.shape[-1])
-        t = E.dwconv2d(t, w, s, 1, 1, sc, sh)
-        b = _pitched(t, h)
-        E.conv2d(t, _pk(self._conv_linear_2), 1, 0, 1, *_fold(self._conv_linear_2), act=act, out=b, out_ld=b.shape[-1])
+        vw = E.vec(v.dtype)
+
+        def pointwise(cna, x):      # 1x1 + BN + act into a buffer the next depthwise conv reads over its whole pitch
+            y = pitched(x, x.shape[1], x.shape[2], h, vw)
+            E.conv2d(x, cna[0].packed(), 1, 0, 1, *cna[0].folded(cna[1]), act=act, out=y, out_ld=y.shape[-1])
+            return y
+
+        def depthwise(cna, x):      # over the whole pitch: zeros stay zeros
+            w, sc, sh = cna[0].dw_padded(x.shape[-1], cna[1])
+            return E.dwconv2d(x, w, s, 1, 1, sc, sh)
+        a = pointwise(self._conv_linear_1, depthwise(self._conv_dw_1, v))
+        b = pointwise(self._conv_linear_2, depthwise(self._conv_dw_2, pointwise(self._conv_pw_2, v)))
         return E.shuffle_concat(a, b, cols=h)
 
 
@@ -219,11 +171,6 @@ class ShuffleNetV2(nn.Module):
         if num_classes > 0:
             self._out_c = stage_out_channels[-1]
             self._fc = nn.Linear(in_features=stage_out_channels[-1], out_features=num_classes)
-
-    def add_sublayer(self, name, sublayer):
-        """Paddle's Layer.add_sublayer: register `sublayer` under `name` and return it."""
-        self.add_module(name, sublayer)
-        return sublayer
 
     def forward_features(self, inputs):
         """-> (B, H/32, W/32, stage_out_channels[-1]) NHWC behind `_last_conv` (:190-194)."""

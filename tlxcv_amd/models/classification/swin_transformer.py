@@ -27,6 +27,7 @@ import torch
 from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc
+from ..common import DropPath, drop_path  # noqa: F401  (re-exported)
 
 __all__ = ["SwinTransformer", "window_partition", "window_reverse", "drop_path", "DropPath", "swintransformer_tiny_patch4_window7_224", "swintransformer_small_patch4_window7_224",
            "swintransformer_base_patch4_window7_224", "swintransformer_large_patch4_window7_224",
@@ -37,24 +38,6 @@ trunc_normal_ = nn.initializers.TruncatedNormal(stddev=0.02)
 
 def to_2tuple(x):
     return tuple([x] * 2)
-
-
-def drop_path(x, drop_prob=0.0, training=False):
-    """Stochastic depth (swin_transformer.py:35-47): the identity in eval mode, the only mode this engine runs."""
-    if drop_prob == 0.0 or not training:
-        return x
-    raise RuntimeError("tlxcv_amd: drop_path in training mode — this engine runs eval-mode forward passes only")
-
-
-class DropPath(nn.Module):
-    """swin_transformer.py:50-59."""
-
-    def __init__(self, drop_prob=None):
-        super().__init__()
-        self.drop_prob = drop_prob
-
-    def forward(self, x):
-        return drop_path(x, self.drop_prob or 0.0, self.is_train)
 
 
 def window_partition(x, window_size):
@@ -86,10 +69,8 @@ class Mlp(nn.Module):
         if (res is not None and getattr(self.act, "ACT", None) == E.ACT_GELU and x.dtype == dt
                 and E.mlp_seam_supported(x.numel() // x.shape[-1], self.fc1.in_features, self.fc1.out_features, self.fc2.out_features, dt)):
             # fc1 + GELU + fc2 + residual as one launch: the (rows, 4 C) hidden map stays on the CU (round 5; stage 1 of Swin-B)
-            pk1 = self.fc1._cached("pk", lambda: E.PackedFilter(self.fc1.weights.detach().t().contiguous(), dt))
-            pk2 = self.fc2._cached("pk", lambda: E.PackedFilter(self.fc2.weights.detach().t().contiguous(), dt))
-            b1 = self.fc1._cached("bias", lambda: E._f32(self.fc1.biases)) if self.fc1.biases is not None else None
-            b2 = self.fc2._cached("bias", lambda: E._f32(self.fc2.biases)) if self.fc2.biases is not None else None
+            pk1, pk2 = self.fc1.packed(), self.fc2.packed()
+            b1, b2 = self.fc1.bias32(), self.fc2.bias32()
             return E.mlp_seam(x, pk1, b1, pk2, b2, res, out=res)
         return self.fc2.run(self.fc1.run(x, act=self.act.ACT), res=res, out=res)
 
@@ -324,7 +305,7 @@ class PatchEmbed(nn.Module):
                 and not x.permute(0, 2, 3, 1).is_contiguous() and (self.norm is None or isinstance(self.norm, nn.LayerNorm))):
             # conv + flatten + transpose + norm (:498-504) in one pass over the image: the layer is HBM traffic only
             w64 = conv._cached("pe4", lambda: E.patch_embed4_filter(conv.filters))
-            bias = conv._cached("bias", lambda: E._f32(conv.biases)) if conv.biases is not None else None
+            bias = conv.bias32()
             if self.norm is None:
                 return E.patch_embed4(x, w64, bias, None, None, 0.0, pos)
             return E.patch_embed4(x, w64, bias, self.norm.gamma.detach(), self.norm.beta.detach(), self.norm.epsilon, pos)

@@ -28,20 +28,11 @@ import torch
 
 from ... import engine as E
 from ...tlx import nn
-from .vision_transformer import DropPath
+from ..common import DropPath, token_rows
 
 __all__ = ["TNT", "Block", "Attention", "Mlp", "PixelEmbed", "tnt_small"]
 
 trunc_normal_ = nn.initializers.TruncatedNormal(stddev=0.02)
-
-
-def _rows(x, what):
-    E.need_gpu(x, "input")
-    if x.dim() != 3:
-        raise RuntimeError(f"{what}: (B, N, C) tokens are expected, got {tuple(x.shape)}")
-    if x.dtype != E.precision():
-        x = x.to(E.precision())
-    return x if x.is_contiguous() else x.contiguous()
 
 
 class Mlp(nn.Module):
@@ -58,7 +49,7 @@ class Mlp(nn.Module):
 
     def forward(self, x):
         self._require_eval()
-        return self.fc2.run(self.fc1.run(_rows(x, "Mlp"), act=self.act.ACT))
+        return self.fc2.run(self.fc1.run(token_rows(x, "Mlp"), act=self.act.ACT))
 
 
 def pack_qkv(qk_weights, v_weights, qk_biases=None, v_biases=None):
@@ -111,7 +102,7 @@ class Attention(nn.Module):
 
     def forward(self, x):
         self._require_eval()
-        return self.run(_rows(x, "Attention"))
+        return self.run(token_rows(x, "Attention"))
 
 
 class Block(nn.Module):
@@ -168,8 +159,7 @@ class Block(nn.Module):
         B, N, D = tok.shape
         yn = self.run_inner(pixel)                                                                    # :142-149
         # tok[:, 1:] += proj(yn): a Linear over the B x P patch rows whose residual and output are rows 1.. of every image    :150-151
-        pk = self.proj._cached("pk", lambda: E.PackedFilter(self.proj.weights.detach().t().contiguous(), E.precision()))
-        b = self.proj._cached("bias", lambda: E._f32(self.proj.biases)) if self.proj.biases is not None else None
+        pk, b = self.proj.packed(), self.proj.bias32()
         rest = tok[:, 1:]
         E.conv2d(yn.view(B, 1, N - 1, yn.shape[-1]), pk, shift=b, res=rest, res_ld=D, res_nstride=N * D, out=rest, out_ld=D, y_nstride=N * D)
         a, m = self.attn_out, self.mlp
@@ -187,7 +177,7 @@ class Block(nn.Module):
 
     def forward(self, pixel_embed, patch_embed):
         self._require_eval()
-        return self.run_inplace(_rows(pixel_embed, "Block").clone(), _rows(patch_embed, "Block").clone())
+        return self.run_inplace(token_rows(pixel_embed, "Block").clone(), token_rows(patch_embed, "Block").clone())
 
 
 class PixelEmbed(nn.Module):

@@ -28,21 +28,13 @@ from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc, from_nhwc
 from ...tlx.nn.initializers import Constant
-from .vision_transformer import DropPath
+from ..common import DropPath, NHWCBlock
 
 __all__ = ["VAN", "VAN_B0", "van", "Mlp", "LKA", "Attention", "Block", "OverlapPatchEmbed", "DWConv"]
 
 
 def _conv1x1(in_ch, out_ch):
     return nn.GroupConv2d(in_channels=in_ch, out_channels=out_ch, kernel_size=1, padding=0, data_format='channels_first')
-
-
-def _dw_filter(conv):
-    """[R][S][C] image of a depthwise conv's filter in the engine's precision, and its fp32 bias (or None)."""
-    dt = E.precision()
-    w = conv._cached("dw", lambda: conv.filters.detach()[:, 0].permute(1, 2, 0).contiguous().to(dt))
-    b = conv._cached("bias", lambda: E._f32(conv.biases)) if conv.biases is not None else None
-    return w, b
 
 
 def _bn_into_conv1x1(owner, key, bn, conv):
@@ -58,7 +50,7 @@ def _bn_into_conv1x1(owner, key, bn, conv):
     return owner._cached(key, build, deps=(bn, conv))
 
 
-class DWConv(nn.Module):
+class DWConv(NHWCBlock):
     """van.py:227-237: depthwise 3x3, no bias."""
 
     def __init__(self, dim=768):
@@ -69,12 +61,8 @@ class DWConv(nn.Module):
     def run_nhwc(self, v, act=E.ACT_NONE):
         return self.dwconv.run_nhwc(v, act=act)
 
-    def forward(self, x):
-        self._require_eval()
-        return from_nhwc(self.run_nhwc(as_nhwc(x, 'channels_first')), 'channels_first')
 
-
-class Mlp(nn.Module):
+class Mlp(NHWCBlock):
     """van.py:56-80."""
 
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0):
@@ -100,12 +88,7 @@ class Mlp(nn.Module):
         h = self.dwconv.run_nhwc(h, act=E.ACT_GELU)
         if scale is None and shift is None:
             return self.fc2.run_nhwc(h, res=res)
-        pk2 = self.fc2._cached("pk", lambda: E.PackedFilter(self.fc2.filters, E.precision()))
-        return E.conv2d(h, pk2, 1, 0, 1, scale, shift, res)
-
-    def forward(self, x):
-        self._require_eval()
-        return from_nhwc(self.run_nhwc(as_nhwc(x, 'channels_first')), 'channels_first')
+        return E.conv2d(h, self.fc2.packed(), 1, 0, 1, scale, shift, res)
 
 
 class LKA(nn.Module):
@@ -120,9 +103,8 @@ class LKA(nn.Module):
 
     def run_dw(self, t):
         """conv_spatial(conv0(t)) on engine.lka_dw."""
-        w0, b0 = _dw_filter(self.conv0)
-        w1, b1 = _dw_filter(self.conv_spatial)
-        return E.lka_dw(t, w0, b0, w1, b1)
+        c0, c1 = self.conv0, self.conv_spatial
+        return E.lka_dw(t, c0.packed(), c0.bias32(), c1.packed(), c1.bias32())
 
     def forward(self, x):
         self._require_eval()
@@ -145,10 +127,7 @@ class Attention(nn.Module):
         """What engine.lka_gate takes behind (a1, t): conv1's packed filter and bias, proj_2's packed filter, scale2 = ls,
         shift2 = ls * (proj_2.bias + bn_shift), res_scale = 1 + ls * bn_scale — fp32, built once and cached on `owner`."""
         lka = self.spatial_gating_unit
-        dt = E.precision()
-        pk1 = lka.conv1._cached("pk", lambda: E.PackedFilter(lka.conv1.filters, dt))
-        b1 = lka.conv1._cached("bias", lambda: E._f32(lka.conv1.biases)) if lka.conv1.biases is not None else None
-        pk2 = self.proj_2._cached("pk", lambda: E.PackedFilter(self.proj_2.filters, dt))
+        pk1, b1, pk2 = lka.conv1.packed(), lka.conv1.bias32(), self.proj_2.packed()
 
         def build():
             s, sh = bn.folded()
@@ -176,7 +155,7 @@ class Attention(nn.Module):
         return from_nhwc(self.proj_2.run_nhwc(g, res=v), 'channels_first')
 
 
-class Block(nn.Module):
+class Block(NHWCBlock):
     """van.py:124-148."""
 
     def __init__(self, dim, mlp_ratio=4.0, drop=0.0, drop_path=0.0, act_layer=nn.GELU):
@@ -208,10 +187,6 @@ class Block(nn.Module):
         """x (B, H, W, C) NHWC in the engine's precision -> the block's output, same shape."""
         self._require_eval()
         return self.run_mlp(self.run_attn(x))
-
-    def forward(self, x):
-        self._require_eval()
-        return from_nhwc(self.run_nhwc(as_nhwc(x, 'channels_first')), 'channels_first')
 
 
 class OverlapPatchEmbed(nn.Module):

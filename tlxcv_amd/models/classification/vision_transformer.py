@@ -26,6 +26,7 @@ import torch
 from ... import engine as E
 from ...tlx import nn
 from ...tlx.nn import as_nhwc
+from ..common import DropPath, Identity  # noqa: F401  (re-exported: the other transformer files import them from here)
 
 __all__ = ["VisionTransformer", "vit_small_patch16_224", "vit_base_patch16_224", "vit_base_patch16_384",
            "vit_base_patch32_384", "vit_large_patch16_224", "vit_large_patch16_384", "vit_large_patch32_384"]
@@ -37,24 +38,6 @@ ones_ = nn.initializers.Constant(value=1.0)
 
 def to_2tuple(x):
     return (x, x)
-
-
-class Identity(nn.Module):
-    def forward(self, x):
-        return x
-
-
-class DropPath(nn.Module):
-    """Stochastic depth: identity in eval (vision_transformer.py:36-61)."""
-
-    def __init__(self, drop_prob=None):
-        super().__init__()
-        self.drop_prob = drop_prob
-
-    def forward(self, x):
-        if self.drop_prob and self.is_train:
-            self._require_eval()
-        return x
 
 
 class Mlp(nn.Module):

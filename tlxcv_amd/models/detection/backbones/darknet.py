@@ -5,11 +5,12 @@ second conv's epilogue as a residual added AFTER the activation."""
 from .... import engine as E
 from ....tlx import nn
 from ....tlx.nn import as_nhwc, from_nhwc
+from ...common import NHWCBlock
 
 __all__ = ["DarkNet", "ConvBNLayer"]
 
 
-class ConvBNLayer(nn.Module):
+class ConvBNLayer(NHWCBlock):
     def __init__(self, ch_in, ch_out, filter_size=3, stride=1, groups=1, padding=0, act="leaky",
                  data_format="channels_first", name="", **kwargs):
         super().__init__(name=name)
@@ -25,9 +26,6 @@ class ConvBNLayer(nn.Module):
 
     def run_nhwc(self, v, res=None, **kw):
         return self.conv.run_nhwc(v, self.batch_norm, E.ACT_LEAKY, 0.1, res=res, res_after_act=res is not None, **kw)
-
-    def forward(self, inputs):
-        return from_nhwc(self.run_nhwc(as_nhwc(inputs, self.data_format)), self.data_format)
 
 
 class DownSample(nn.Module):
@@ -45,7 +43,7 @@ class DownSample(nn.Module):
         return self.conv_bn_layer(inputs)
 
 
-class BasicBlock(nn.Module):
+class BasicBlock(NHWCBlock):
     def __init__(self, ch_in, ch_out, norm_type="bn", norm_decay=0.0, freeze_norm=False, data_format="channels_first"):
         super().__init__()
         assert ch_in == ch_out and ch_in % 2 == 0, \
@@ -58,9 +56,6 @@ class BasicBlock(nn.Module):
 
     def run_nhwc(self, v):
         return self.conv2.run_nhwc(self.conv1.run_nhwc(v), res=v)       # inputs + leaky(bn(conv2(...)))
-
-    def forward(self, inputs):
-        return from_nhwc(self.run_nhwc(as_nhwc(inputs, self.data_format)), self.data_format)
 
 
 class Blocks(nn.Module):

@@ -77,12 +77,10 @@ class SeparableConvBNReLU(nn.Module):
             return self.piontwise_conv.run_nhwc(self.depthwise_conv.run_nhwc(v), **kw)
         dw._require_eval()
         pw._require_eval()
-        dt = E.precision()
-        bn1, bn2 = self.depthwise_conv.batch_norm, self.piontwise_conv.batch_norm
-        w_dw = dw._cached("dw", lambda: dw.filters.detach()[:, 0].permute(1, 2, 0).contiguous().to(dt))
-        s1, t1 = dw._cached(("bn", id(bn1)), lambda: bn1.folded(dw.biases), deps=(bn1,))
-        pk = pw._cached("pk", lambda: E.PackedFilter(pw.filters, dt))
-        s2, t2 = pw._cached(("bn", id(bn2)), lambda: bn2.folded(pw.biases), deps=(bn2,))
+        w_dw = dw.packed()
+        s1, t1 = dw.folded(self.depthwise_conv.batch_norm)
+        pk = pw.packed()
+        s2, t2 = pw.folded(self.piontwise_conv.batch_norm)
         return E.sepconv2d(v, w_dw, s1, t1, pk, s2, t2, dw.dilation[0], E.ACT_RELU, out=out, out_ld=out_ld)
 
 

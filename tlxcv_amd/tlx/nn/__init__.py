@@ -503,10 +503,48 @@ class GroupConv2d(Module):
             odd = odd or (total % 2 == 1)
         return tuple(lead), (tuple(out) if odd else None)
 
+    # -- derived tensors: the one place their cache keys, builders and deps are spelled ----------------------------------
+    def packed(self):
+        """What the conv kernels read of `filters` at the current precision: engine.PackedFilter (dense), the [R][S][C] image
+        (depthwise) or engine.PackedGroupFilter (1 < n_group < C: ResNeXt cardinality, resnext.py:83-91)."""
+        if self.n_group == 1:
+            return self._cached("pk", lambda: E.PackedFilter(self.filters, E.precision()))
+        if self.n_group == self.in_channels == self.out_channels:
+            return self._cached("dw", lambda: self.filters.detach()[:, 0].permute(1, 2, 0).contiguous().to(E.precision()))
+        return self._cached("gpk", lambda: E.PackedGroupFilter(self.filters, self.n_group, E.precision()))
+
+    def bias32(self):
+        """The fp32 bias, or None."""
+        return self._cached("bias", lambda: E._f32(self.biases)) if self.biases is not None else None
+
+    def affine(self, bn=None):
+        """The conv epilogue's (scale, shift): the BatchNorm `bn` behind this conv folded, the conv's bias in the shift; without a
+        BatchNorm (None, bias32())."""
+        if bn is None:
+            return None, self.bias32()
+        return self._cached(("bn", id(bn)), lambda: bn.folded(self.biases), deps=(bn,))
+
+    def folded(self, bn):
+        """(scale, shift) of the BatchNorm `bn` behind this conv: affine() of a BatchNorm that is there."""
+        return self.affine(bn)
+
+    def dw_padded(self, width, bn):
+        """A depthwise conv's [R][S][width] filter and folded BatchNorm [width], zero filled behind the conv's channels: the conv
+        then runs over a map's whole pitch and leaves zeros in the pad columns."""
+        def build():
+            dt = E.precision()
+            c = self.in_channels
+            s, t = self.folded(bn)
+            w = torch.zeros(self.kernel_size + (width,), dtype=dt, device=s.device)
+            w[..., :c] = self.filters.detach()[:, 0].permute(1, 2, 0).to(dt)
+            sp, tp = torch.zeros(width, dtype=torch.float32, device=s.device), torch.zeros(width, dtype=torch.float32, device=s.device)
+            sp[:c], tp[:c] = s, t
+            return w, sp, tp
+        return self._cached(("dw_padded", width), build, deps=(bn,))
+
     # fused entry point used by the model graphs: conv (+bn) (+act) (+residual) in one launch
     def run_nhwc(self, x, bn=None, act=E.ACT_NONE, act_param=0.0, res=None, res_after_act=False, **kw):
         self._require_eval()
-        dt = E.precision()
         padding = self.padding
         if self.same:
             padding, out_hw = self._same(x.shape[1], x.shape[2])
@@ -514,16 +552,8 @@ class GroupConv2d(Module):
                 kw = dict(kw, out_hw=out_hw)
                 if self.n_group == 1 or self.n_group != self.in_channels:
                     kw["overhang"] = True
-        if self.n_group == 1:
-            pk = self._cached("pk", lambda: E.PackedFilter(self.filters, dt))
-        elif self.n_group == self.in_channels == self.out_channels:
-            pk = self._cached("dw", lambda: self.filters.detach()[:, 0].permute(1, 2, 0).contiguous().to(dt))
-        else:   # 1 < n_group < C: ResNeXt cardinality, resnext.py:83-91
-            pk = self._cached("gpk", lambda: E.PackedGroupFilter(self.filters, self.n_group, dt))
-        if bn is not None:
-            scale, shift = self._cached(("bn", id(bn)), lambda: bn.folded(self.biases), deps=(bn,))
-        else:
-            scale, shift = None, (self._cached("bias", lambda: E._f32(self.biases)) if self.biases is not None else None)
+        pk = self.packed()
+        scale, shift = self.affine(bn)
         if self.n_group == 1:
             return E.conv2d(x, pk, self.stride, padding, self.dilation, scale, shift, res, act, act_param,
                             res_after_act, **kw)
@@ -564,10 +594,7 @@ class GroupConv2d(Module):
             w2, pad2 = E.s2d_filter(self.filters, b, pad[0])
             return E.PackedFilter(w2, dt), pad2
         pk, pad2 = self._cached(("s2d", b, pad[0]), build)
-        if bn is not None:
-            scale, shift = self._cached(("bn", id(bn)), lambda: bn.folded(self.biases), deps=(bn,))
-        else:
-            scale, shift = None, (self._cached("bias", lambda: E._f32(self.biases)) if self.biases is not None else None)
+        scale, shift = self.affine(bn)
         v = E.nchw_to_nhwc_s2d(x_nchw, b, dt)
         if maxpool is not None and (maxpool.kernel_size, maxpool.stride, maxpool.padding) == ((3, 3), (2, 2), (1, 1)) and not kw:
             y = E.conv2d(v, pk, (sh // b, sw // b), pad2, 1, scale, shift, act=act, act_param=act_param, out_hw=(Ho, Wo),
@@ -691,21 +718,24 @@ class Linear(Module):
             bi = str_to_init(b_init) if isinstance(b_init, str) else (b_init if callable(b_init) else Constant(0.0))
             self.biases = Parameter(data=bi(shape=(self.out_features,)))
 
+    def packed(self):
+        """engine.PackedFilter of `weights` as (out, in) at the current precision."""
+        return self._cached("pk", lambda: E.PackedFilter(self.weights.detach().t().contiguous(), E.precision()))
+
+    def bias32(self):
+        """The fp32 bias, or None."""
+        return self._cached("bias", lambda: E._f32(self.biases)) if self.biases is not None else None
+
     def run(self, x, act=E.ACT_NONE, res=None, out=None):
-        dt = E.precision()
-        pk = self._cached("pk", lambda: E.PackedFilter(self.weights.detach().t().contiguous(), dt))
-        b = self._cached("bias", lambda: E._f32(self.biases)) if self.biases is not None else None
-        if x.dtype != dt:
-            x = x.to(dt)
+        pk, b = self.packed(), self.bias32()
+        if x.dtype != pk.dtype:
+            x = x.to(pk.dtype)
         return E.linear(x, pk, b, res, act, out)
 
     # LayerNorm folded around the Linear layers of a transformer block (engine.linear_stats / linear_ln, fp16, round 5)
     def run_stats(self, x, res=None, out=None):
         """run() of a Linear that writes the residual stream, + the row statistics of its output -> (y, partials)."""
-        dt = E.precision()
-        pk = self._cached("pk", lambda: E.PackedFilter(self.weights.detach().t().contiguous(), dt))
-        b = self._cached("bias", lambda: E._f32(self.biases)) if self.biases is not None else None
-        return E.linear_stats(x, pk, b, res, out)
+        return E.linear_stats(x, self.packed(), self.bias32(), res, out)
 
     def run_ln(self, x, norm, part, act=E.ACT_NONE):
         """act(self(norm(x))) on the raw rows x, `norm` (an nn.LayerNorm) folded in: part = the row statistics of x (run_stats of whoever wrote x)."""

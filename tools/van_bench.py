@@ -17,9 +17,6 @@ import torch  # noqa: E402
 import tlxcv_amd  # noqa: E402,F401
 from tlxcv_amd import engine as E, seeded, models  # noqa: E402
 from tools.ab import ab, model_on_off  # noqa: E402
-import importlib  # noqa: E402
-
-V = importlib.import_module("tlxcv_amd.models.classification.van")      # (the package attribute `van` is the factory)
 
 dev = torch.device("cuda:0")
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
@@ -43,8 +40,8 @@ def stages():
             with torch.no_grad():
                 blk.run_nhwc(x)                                   # derived tensors
                 t = torch.randn(b, hw, hw, Cc, generator=g).half().to(dev)
-                w0, b0 = V._dw_filter(lka.conv0)
-                w1, b1 = V._dw_filter(lka.conv_spatial)
+                w0, b0 = lka.conv0.packed(), lka.conv0.bias32()
+                w1, b1 = lka.conv_spatial.packed(), lka.conv_spatial.bias32()
                 a1 = E.lka_dw(t, w0, b0, w1, b1)
                 pk1, c1, pk2, s2, h2, rs = att.gate_operands(blk.norm1, blk.layer_scale_1, blk)
 
