@@ -675,6 +675,38 @@ size_t tlxmi_inception_head_param_bytes(int Cin, int f1, int f3R, int f5R, int p
 int tlxmi_inception_head(const tlxmi_inception_head_desc* d, const void* x, const void* params, void* y, void* t, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SqueezeNet's Fire module (classification/squeezenet.py:37-52) in one launch: squeeze 1x1, expand 1x1 and expand 3x3, each with
+ * its bias and a ReLU.
+ *     s[p]                = relu( x[p] . Ws + bs )                                    sq channels, rounded to fp16, never stored
+ *     y[p][0 .. e1)       = relu( s[p] . W1 + b1 )                                    fp32 accumulation on MFMA
+ *     y[p][e1 .. e1 + e3) = relu( sum over the 3x3 taps d of s[p + d] . W3[d] + b3 )  padding 1
+ * The 3x3's padding pads s: a position outside the image contributes zero, not relu(bs).  fp16 only.  x: NHWC, N x H x W pixels at
+ * pitch x_ld, Cin channels read (columns behind Cin are never loaded).  y: the module's output map at pitch y_ld; columns outside
+ * [0, e1 + e3) and everything behind the map are left untouched.  The squeeze map is built over a haloed pixel tile in LDS; a tile
+ * takes no halo from the neighbouring image of the batch.  y aliases no input.  One writer per element, fixed summation order, no atomics.
+ * params: tlxmi_fire_module_param_bytes(Cin, sq, e1, e3) bytes, six sections one behind the other (row = output channel, K
+ * contiguous, every pad zero):
+ *     Ws  fp16 [sq][CinP]     CinP = Cin rounded up to 32
+ *     W1  fp16 [E1P][K1P]     E1P = e1 rounded up to 16, K1P = sq rounded up to 32
+ *     W3  fp16 [E3P][K3P]     E3P = e3 rounded up to 16, K3P = 9 sq rounded up to 32, k = (3 r + s) sq + c for tap (r, s), channel c
+ *     bs  fp32 [sq],   b1  fp32 [E1P],   b3  fp32 [E3P]
+ * tlxmi_fire_module_supported() is pure host code and answers 1 exactly for: fp16; N, H, W >= 1; Cin, e1 and e3 multiples of 8,
+ * 8 <= Cin <= 2048, 8 <= e1, e3 <= 1024; sq 16, 32, 48 or 64; x_ld and y_ld multiples of 8; x_ld >= Cin; y_ld >= e1 + e3;
+ * (pixels * ld + 2048) * 2 below 2^31 for both pitches (32-bit byte offsets).  1 means the call is taken, given x, params and y
+ * 16-byte aligned (TLXMI_ERR_ALIGNMENT otherwise); anything else returns TLXMI_ERR_UNSUPPORTED (run tlxmi_conv2d three times
+ * instead).  param_bytes is 0 outside the ranges.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_fire_module_desc {
+    int32_t dtype;
+    int32_t N, H, W, Cin;
+    int32_t sq, e1, e3;
+    int32_t x_ld, y_ld;
+} tlxmi_fire_module_desc;
+int tlxmi_fire_module_supported(const tlxmi_fire_module_desc* d);
+size_t tlxmi_fire_module_param_bytes(int Cin, int sq, int e1, int e3);
+int tlxmi_fire_module(const tlxmi_fire_module_desc* d, const void* x, const void* params, void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

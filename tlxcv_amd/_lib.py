@@ -70,6 +70,10 @@ class InceptionHeadDesc(C.Structure):
                                          "t_f5_off")]
 
 
+class FireModuleDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "Cin", "sq", "e1", "e3", "x_ld", "y_ld")]
+
+
 class LkaGateDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in ("C", "a1_ld", "t_ld", "res_ld", "y_ld")]
 
@@ -200,6 +204,7 @@ PROTOTYPES = {
     "tlxmi_mixconv_dw": [C.POINTER(MixConvDwDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_res2_chain": [C.POINTER(Res2ChainDesc), _vp, _vp, _vp, _vp],
     "tlxmi_inception_head": [C.POINTER(InceptionHeadDesc), _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_fire_module": [C.POINTER(FireModuleDesc), _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -241,6 +246,8 @@ _SPECIAL = {
     "tlxmi_res2_chain_param_bytes": ([C.POINTER(Res2ChainDesc)], C.c_size_t),
     "tlxmi_inception_head_supported": ([C.POINTER(InceptionHeadDesc)], C.c_int),
     "tlxmi_inception_head_param_bytes": ([_i, _i, _i, _i, _i], C.c_size_t),
+    "tlxmi_fire_module_supported": ([C.POINTER(FireModuleDesc)], C.c_int),
+    "tlxmi_fire_module_param_bytes": ([_i, _i, _i, _i], C.c_size_t),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

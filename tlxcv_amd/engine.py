@@ -102,6 +102,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # launch, x staged once in LDS with a halo, the pooled tile an MFMA operand that never leaves the CU, the four
                                   # results written into their slices of the output map and of the mid map; elsewhere and off = tlxmi_conv2d x 3 ->
                                   # tlxmi_maxpool2d -> tlxmi_conv2d (the A/B and the tests' other arm)
+            "fire_module": True,  # SqueezeNet's Fire modules (fp16, sq 16 / 32 / 48 / 64, widths multiples of 8; the shapes the measured table keeps:
+                                  # engine.FIRE_MODULE_WINS): squeeze 1x1 -> expand 1x1 | expand 3x3 on tlxmi_fire_module: ONE launch, x read
+                                  # once, the squeeze map of a haloed pixel tile in LDS only, both expands written into their slices of the output
+                                  # map; elsewhere and off = tlxmi_conv2d x 3 with bias + ReLU epilogues (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -2068,6 +2072,122 @@ def inception_head(x, params, fused=None, out=None, mid=None):
     _timed(launch, lambda: ((M * (p.cin + nout) + p.cin * nout) * es, 2 * M * p.cin * nout,
                             (N, H, W, p.cin, nout, "inception_head" if fused else "conv-conv-conv-pool-conv")))      # the chain is one entry
     return out, mid
+
+
+# ---------------------------------------------------------------------------------------------
+# SqueezeNet's Fire module: squeeze 1x1 -> expand 1x1 | expand 3x3
+# ---------------------------------------------------------------------------------------------
+def fire_module_pack(ws, bs, w1, b1, w3, b3):
+    """The parameter image tlxmi_fire_module reads (include/tlxmi.h), as one uint8 tensor on the operands' device: fp16 Ws [sq][CinP],
+    W1 [E1P][K1P], W3 [E3P][K3P] with k = (3 r + s) sq + c, then fp32 bs [sq], b1 [E1P], b3 [E3P]; CinP, K1P, K3P = Cin, sq, 9 sq
+    rounded up to 32, E1P, E3P = e1, e3 rounded up to 16, every pad zero.  ws (sq, Cin, 1, 1), w1 (e1, sq, 1, 1), w3 (e3, sq, 3, 3)."""
+    sq, cin = int(ws.shape[0]), int(ws.shape[1])
+    e1, e3 = int(w1.shape[0]), int(w3.shape[0])
+    dev, h, f = ws.device, torch.float16, torch.float32
+    e1p, e3p = _round_up(e1, 16), _round_up(e3, 16)
+    return _param_image(_zero_padded(ws.reshape(sq, cin), (sq, _round_up(cin, 32)), h, dev),
+                        _zero_padded(w1.reshape(e1, sq), (e1p, _round_up(sq, 32)), h, dev),
+                        _zero_padded(w3.detach().permute(0, 2, 3, 1).reshape(e3, 9 * sq), (e3p, _round_up(9 * sq, 32)), h, dev),
+                        _zero_padded(bs, (sq,), f, dev), _zero_padded(b1, (e1p,), f, dev), _zero_padded(b3, (e3p,), f, dev))
+
+
+class FireParams:
+    """The three convs of one Fire module in the forms both arms of fire_module() read: a PackedFilter and an fp32 bias each for the
+    layer-by-layer arm, and — fp16, inside the library's ranges — the one-buffer image of tlxmi_fire_module (fire_module_pack).
+    ws (sq, Cin, 1, 1), w1 (e1, sq, 1, 1), w3 (e3, sq, 3, 3) and their biases.  The output map's slices are [0, e1) | [e1, e1 + e3)
+    = the concatenation of the reference (squeezenet.py:52).  Cin, sq and e1 must be multiples of 8 (the squeeze map feeds 16-byte
+    vectors and the 3x3's slice must start on a 16-byte boundary): other widths are REFUSED here, in both arms.
+    packed / biases: the layers' own (PackedFilter x 3) and (fp32 bias x 3) at this precision, where a model holds them already."""
+
+    def __init__(self, ws, bs, w1, b1, w3, b3, dtype, packed=None, biases=None):
+        self.sq, self.cin = int(ws.shape[0]), int(ws.shape[1])
+        self.e1, self.e3 = int(w1.shape[0]), int(w3.shape[0])
+        if (int(w1.shape[1]) != self.sq or int(w3.shape[1]) != self.sq or tuple(w3.shape[2:]) != (3, 3) or tuple(ws.shape[2:]) != (1, 1)
+                or tuple(w1.shape[2:]) != (1, 1) or any(n <= 0 or n % 8 for n in (self.cin, self.sq, self.e1))):
+            raise RuntimeError(f"FireParams: a 1x1 squeeze (sq, Cin), a 1x1 expand (e1, sq) and a 3x3 expand (e3, sq) are expected, Cin, sq and "
+                               f"e1 multiples of 8; got {tuple(ws.shape)}, {tuple(w1.shape)}, {tuple(w3.shape)}")
+        self.dtype, self.cout = dtype, self.e1 + self.e3
+        self.pks, self.pk1, self.pk3 = packed if packed is not None else (PackedFilter(w, dtype) for w in (ws, w1, w3))
+        self.bs, self.b1, self.b3 = biases if biases is not None else (_f32(b) for b in (bs, b1, b3))
+        self.blob = None
+        nbytes = _lib.load().tlxmi_fire_module_param_bytes(self.cin, self.sq, self.e1, self.e3) if dtype == torch.float16 else 0
+        if nbytes:
+            self.blob = fire_module_pack(*(t.detach() for t in (ws, bs, w1, b1, w3, b3)))
+            assert self.blob.numel() == nbytes
+
+
+def _fire_module_desc(x, p, y_ld):
+    N, H, W, ld = x.shape
+    return _lib.FireModuleDesc(dtype=dt_code(x.dtype), N=N, H=H, W=W, Cin=p.cin, sq=p.sq, e1=p.e1, e3=p.e3, x_ld=ld, y_ld=y_ld)
+
+
+def fire_module_takes(x, params, y_ld=None):
+    """Whether the library's tlxmi_fire_module takes this NHWC map with these parameters (fp16, the widths and pitches of
+    include/tlxmi.h): what fused=True needs."""
+    if x.dim() != 4 or x.dtype != torch.float16 or not x.is_contiguous() or params.blob is None:
+        return False
+    y_ld = params.cout if y_ld is None else int(y_ld)
+    return bool(_lib.load().tlxmi_fire_module_supported(C.byref(_fire_module_desc(x, params, y_ld))))
+
+
+# (H, W, Cin, sq, e1, e3) of the modules where the one launch was measured FASTER than the layer-by-layer arm beyond the spread of both — its
+# slowest round against the layers' fastest — at batch 256 on one MI355X (tools/squeezenet_bench.py,
+# profiles/squeezenet/squeezenet_bench_b256.txt, DESIGN 4.32): fire_module() keeps the launch there and runs the layers everywhere else by
+# default.  MEASURED over the twelve distinct shapes of both versions: it wins the three sq = 32 modules at 26 x 26 / 27 x 27 (0.83 - 0.93 of
+# the layers' time); it takes 1.07 - 1.20 x the layers' time at the 54 x 54 / 55 x 55 modules and at sq = 48, 1.24 - 1.40 x at sq = 64.
+# Shapes other than those twelve are unmeasured and run layer by layer.
+FIRE_MODULE_WINS = frozenset({(26, 26, 256, 32, 128, 128), (27, 27, 128, 32, 128, 128), (27, 27, 256, 32, 128, 128)})
+
+
+def _fire_module_routed(H, W, p):
+    return (H, W, p.cin, p.sq, p.e1, p.e3) in FIRE_MODULE_WINS
+
+
+def fire_module_supported(x, params, y_ld=None):
+    """Whether fire_module() runs tlxmi_fire_module on this map by default: the "fire_module" option on, the measured table keeps the
+    shape (FIRE_MODULE_WINS) and the library takes the call (fire_module_takes)."""
+    return bool(_options["fire_module"] and x.dim() == 4 and _fire_module_routed(x.shape[1], x.shape[2], params)
+                and fire_module_takes(x, params, y_ld))
+
+
+def fire_module(x, params, fused=None, out=None):
+    """A Fire module (squeezenet.py:37-52) on an NHWC map x (N, H, W, x_ld) whose first Cin = params.cin channels are the input (the
+    columns behind them are not read):
+        s = relu(x . Ws + bs),   y[..., :e1] = relu(s . W1 + b1),   y[..., e1:e1 + e3] = relu(conv3x3 pad 1 (s) . W3 + b3)
+    -> y (N, H, W, e1 + e3), or written into `out` (its last axis is the pitch, a multiple of 8; nothing behind e1 + e3 is written).
+    params: FireParams.  One launch (tlxmi_fire_module: x read once, the squeeze map kept in LDS) when the "fire_module" option is
+    on, the precision is fp16, the measured table keeps the shape and the library takes it (fire_module_supported); otherwise — and
+    always for fp32 — tlxmi_conv2d three times with bias + ReLU epilogues, the two expands into their slices.  fused=True / False
+    forces one form (tests, tools/); True raises where the launch is not supported."""
+    need_gpu(x, "input")
+    N, H, W, ld = x.shape
+    p = params
+    if x.dtype != p.dtype or ld < p.cin or ld % 8 or not x.is_contiguous():
+        raise RuntimeError(f"fire_module: x must be a dense NHWC map of the parameters' dtype with at least {p.cin} channels at a pitch "
+                           f"that is a multiple of 8, got {tuple(x.shape)} {x.dtype}")
+    out, y_ld = _out_map("fire_module", out, N, H, W, p.cout, x.dtype, x.device, p.cout, multiple=8,
+                         what=f"a dense ({N}, {H}, {W}, >= {p.cout}) map of x's dtype at a pitch that is a multiple of 8")
+    takes = lambda: fire_module_takes(x, p, y_ld)      # noqa: E731
+    # the option and the table first: the library's predicate is asked only where they keep the launch
+    fused = _use_fused("fire_module", fused, takes, lambda: _options["fire_module"] and _fire_module_routed(H, W, p) and takes(),
+                       lambda: f"{tuple(x.shape)} {x.dtype} with Cin {p.cin}, sq {p.sq}, e1 {p.e1}, e3 {p.e3}, y_ld {y_ld}")
+    es = x.element_size()
+    M = N * H * W
+    if _sizing():
+        _note_act(x.numel() * es, M * y_ld * es)
+
+    def launch():
+        if fused:
+            desc = _fire_module_desc(x, p, y_ld)
+            _lib.call("tlxmi_fire_module", C.byref(desc), _p(x), _p(p.blob), _p(out), _stream())
+            return
+        s = conv2d(x[..., :p.cin], p.pks, shift=p.bs, act=ACT_RELU, x_ld=ld)
+        conv2d(s, p.pk1, shift=p.b1, act=ACT_RELU, out=out[..., :p.e1], out_ld=y_ld)
+        conv2d(s, p.pk3, 1, 1, 1, shift=p.b3, act=ACT_RELU, out=out[..., p.e1:p.cout], out_ld=y_ld)
+    nw = p.cin * p.sq + p.sq * p.e1 + 9 * p.sq * p.e3
+    _timed(launch, lambda: ((M * (p.cin + p.cout) + nw) * es, 2 * M * nw,
+                            (N, H, W, p.cin, p.cout, "fire_module" if fused else "conv-conv-conv")))      # the chain is one entry
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

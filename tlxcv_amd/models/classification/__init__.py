@@ -44,3 +44,4 @@ from .mixnet import (MixNet, MixUnit, MixInitBlock, MixConv, MixConvBlock, mixco
 # (the Res2Net file's ConvBNLayer / BottleneckBlock stay in their module: DenseNet's ConvBNLayer owns that name here)
 from .res2net import Res2Net, res2net  # noqa: F401
 from .googlenet import GoogLeNet, ConvLayer, Inception, googlenet  # noqa: F401
+from .squeezenet import SqueezeNet, MakeFire, MakeFireConv, squeezenet1_0, squeezenet1_1  # noqa: F401

@@ -23,6 +23,8 @@ _MIXNET_PROJ = re.compile(r"^features\.(init_block\.conv2|stage\d+\.unit\d+)\.co
 # tree has (ResNeXt's bb_<b>_<i> blocks keep conv0 / conv1 / conv2) — and the block's expand BatchNorm, which feeds the residual add
 _RES2NET_CHAIN = re.compile(r"^bb_\d+_\d+\.res\d+\w*_branch2b_\d+\.")
 _RES2NET_LAST_BN = re.compile(r"^bb_\d+_\d+\.conv2\.batch_norm$")
+# SqueezeNet (squeezenet.py:37-46): a Fire module's expand 1x1, registered as _conv<k>._conv_path1 — a name no other tree has
+_SQUEEZENET_FIRE = re.compile(r"^_conv\d+\._conv_path1\._conv\.")
 
 
 def image_batch(n, seed=0, hw=224, c=3):
@@ -97,9 +99,17 @@ def fill(shapes, seed):
                                  the logits (range 90 - 130) of every seed tried share one argmax over the batch.  With the branch at
                                  U(0.02, 0.06) the stream stays below 30 and three seeds of eight give distinct, well separated classes.
                                  Same number of draws: the values drawn for every other model (ResNeXt's bb_<b>_<i>.conv2 included) are unchanged
+      *.filters                  in a tree that has SqueezeNet's Fire modules (_conv<k>._conv_path1: squeezenet.py:37-46) only: drawn exactly as
+                                 above, then every output channel's filter has its own mean subtracted.  SqueezeNet has no normalisation and
+                                 every activation is non-negative, so under the general rule the features become a common mode: 23 of 24
+                                 fixtures tried had one argmax on both rows, and such a fixture cannot tell a forward that ignores its input
+                                 from a correct one.  With zero-mean filters 6 of 8 seeds (1.0) and 5 of 8 (1.1) give distinct, separated
+                                 argmaxes, module outputs peak between 0.6 and 15 and the logit range is 0.1 - 0.3.  Same number of draws: the
+                                 values drawn for every other model are unchanged
     """
     rng = np.random.default_rng(seed)
     res2net = any(_RES2NET_CHAIN.match(n) for n in shapes)
+    squeezenet = any(_SQUEEZENET_FIRE.match(n) for n in shapes)
     out = {}
     for name, shape in shapes.items():
         shape = tuple(shape)
@@ -119,6 +129,8 @@ def fill(shapes, seed):
         elif leaf == "filters":
             fan_in = int(np.prod(shape[1:]))
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(np.sqrt(2.0 / fan_in))
+            if squeezenet and a.size:
+                a = a - a.reshape(shape[0], -1).mean(axis=1, dtype=np.float32).reshape((shape[0],) + (1,) * (len(shape) - 1))
         elif leaf == "weights" and ("attn_in." in owner + "." or "mlp_in." in owner + "."):      # TNT's inner transformer (tnt.py:125-129)
             gain = 1.5 if (owner + ".").endswith("attn_in.qk.") else 1.0
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(gain / np.sqrt(shape[0]))
