@@ -8,7 +8,11 @@ Contents:
   tlx_cpu/       a minimal torch-CPU stand-in for the `tensorlayerx` API, used ONLY in the
                  development container by gen_golden.py to import the reference's model files
                  unmodified from /root/reference and check the restatements against them.
-  gen_golden.py  writes tests/golden/*.npz (inputs recipe ids + expected logits).
+  shims/         import shims for the other packages those files hard-import (README there).
+  gen_golden.py  writes every fixture of tests/golden/*.npz (inputs recipe ids + expected
+                 outputs) from one table of jobs, `--check` compares a regeneration with the
+                 committed files, and `reference(name)` hands a loaded reference file to the
+                 host tests.
 
 PARITY PINNING: the reference ships no tests, golden vectors or fixtures, and TensorLayerX (where
 the arithmetic lives, `tensorlayerx>=0.5.8`, not vendored) is not installable here.  The *graphs*

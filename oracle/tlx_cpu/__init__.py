@@ -10,7 +10,8 @@ import torch
 
 from . import nn, ops  # noqa: F401
 from .nn import initializers  # noqa: F401
-from .ops import GeLU, softmax, sigmoid, relu, arange, stack  # noqa: F401
+from .ops import GeLU, softmax, sigmoid, relu, arange, stack, split, squeeze, matmul, multiply  # noqa: F401
+from .pd import _DTYPES
 
 BACKEND = "torch"
 float32 = torch.float32
@@ -18,8 +19,18 @@ int64 = torch.int64
 
 
 def convert_to_tensor(value, dtype=None, device=None):
+    """dtype may be a Paddle dtype string (levit.py:184 passes 'int64')."""
+    dtype = _DTYPES[dtype] if isinstance(dtype, str) else dtype
     t = value if isinstance(value, torch.Tensor) else torch.as_tensor(np.asarray(value))
     return t.to(dtype) if dtype is not None else t
+
+
+def constant(value, dtype=None, shape=None):
+    return torch.full(tuple(shape), float(value))
+
+
+def gather(params, indices, axis=0):
+    return torch.index_select(params, axis, indices)
 
 
 def convert_to_numpy(value):
@@ -46,14 +57,11 @@ def concat(values, axis=0):
     return torch.cat(list(values), dim=axis)
 
 
-def split(value, num_or_size_splits, axis=0):
-    if isinstance(num_or_size_splits, int):
-        return torch.chunk(value, num_or_size_splits, dim=axis)
-    return torch.split(value, list(num_or_size_splits), dim=axis)
-
-
 def expand_dims(input, axis):
-    return input.unsqueeze(axis)
+    """A list axis is one unsqueeze per entry, in order (ghostnet.py:69 passes [2, 3])."""
+    for a in [axis] if isinstance(axis, int) else axis:
+        input = input.unsqueeze(a)
+    return input
 
 
 def roll(input, shifts, dims=None):
@@ -64,23 +72,11 @@ def index_select(x, index, axis=0):
     return torch.index_select(x, axis, index)
 
 
-def matmul(a, b, transpose_a=False, transpose_b=False):
-    if transpose_a:
-        a = a.transpose(-1, -2)
-    if transpose_b:
-        b = b.transpose(-1, -2)
-    return torch.matmul(a, b)
-
-
 def add_n(inputs):
     out = inputs[0]
     for t in inputs[1:]:
         out = out + t
     return out
-
-
-def multiply(x, y):
-    return x * y
 
 
 def add(value, bias):
@@ -121,16 +117,26 @@ def reduce_max(input_tensor, axis=None, keepdims=False):
     return torch.max(input_tensor) if axis is None else torch.max(input_tensor, dim=axis, keepdim=keepdims).values
 
 
-def squeeze(input, axis=None):
-    return input.squeeze() if axis is None else input.squeeze(axis)
-
-
 def argsort(values, axis=-1, descending=False):
     return torch.argsort(values, dim=axis, descending=descending, stable=True)
 
 
 def argmax(x, axis=None, dtype="int64"):
     return torch.argmax(x, dim=axis)
+
+
+class Resize:
+    """tlx.Resize [TLX-recalled]: the torch backend's F.interpolate(scale_factor=scale, mode=method, align_corners=antialias)
+    (segmentation/deeplab.py)."""
+
+    def __init__(self, scale, method="bilinear", antialias=False, data_format="channels_first"):
+        self.scale, self.method, self.antialias, self.data_format = scale, method, antialias, data_format
+
+    def __call__(self, x):
+        if self.data_format == "channels_last":
+            x = x.permute(0, 3, 1, 2)
+        y = torch.nn.functional.interpolate(x, scale_factor=self.scale, mode=self.method, align_corners=self.antialias)
+        return y.permute(0, 2, 3, 1) if self.data_format == "channels_last" else y
 
 
 class FlattenReshape(nn.Module):

@@ -37,6 +37,15 @@ class TruncatedNormal:
         return torch.randn(tuple(shape), generator=_g).clamp_(-2, 2) * self.stddev + self.mean
 
 
+class random_normal:
+    def __init__(self, mean=0.0, stddev=0.05, seed=None):
+        self.mean, self.stddev = mean, stddev
+
+    @_inplace_ok
+    def __call__(self, shape, dtype=None):
+        return torch.randn(tuple(shape), generator=_g) * self.stddev + self.mean
+
+
 class xavier_uniform:
     def __init__(self, gain=1.0, seed=None):
         pass
@@ -62,6 +71,9 @@ class he_normal:
     @_inplace_ok
     def __call__(self, shape, dtype=None):
         return torch.randn(tuple(shape), generator=_g) * 0.05
+
+
+HeNormal = he_normal          # ghostnet.py:14 imports the name
 
 
 def str_to_init(s):

@@ -1,4 +1,6 @@
 """torch-CPU layers behind the tensorlayerx.nn names (oracle-side stand-in)."""
+import types
+
 import torch
 import torch.nn.functional as F
 
@@ -6,8 +8,17 @@ from . import initializers  # noqa: F401
 from .initializers import Constant, TruncatedNormal, xavier_uniform, str_to_init  # noqa: F401
 
 
+class _Parameter(torch.nn.Parameter):
+    def set_value(self, value):          # Paddle's spelling (convnext.py:165-169, the head_init_scale lines)
+        with torch.no_grad():
+            self.copy_(torch.as_tensor(value))
+
+
 def Parameter(data=None, name=None):
-    return torch.nn.Parameter(torch.as_tensor(data, dtype=torch.float32).detach().clone(), requires_grad=False)
+    return _Parameter(torch.as_tensor(data, dtype=torch.float32).detach().clone(), requires_grad=False)
+
+
+ParameterList = torch.nn.ParameterList          # gvt.py:228
 
 
 def _falsy_bias(b_init):
@@ -86,6 +97,12 @@ class Module(torch.nn.Module):
             del self.__dict__[name]
         self.register_parameter(name, parameter)
         return parameter
+
+    def add_sublayer(self, name, sublayer):          # Paddle's Layer.add_sublayer: register under the name, return the layer
+        self.add_module(str(name), sublayer)
+        return sublayer
+
+    _sub_layers = property(lambda self: self._modules)          # Paddle's spelling of torch's _modules (mixnet.py:249, levit.py:63)
 
     # --- checkpoint interchange [TLX-recalled; the real package cannot be consulted here]: `all_weights` lists the
     # variables layer by layer in construction order, each layer's in the order its build() creates them (conv / linear:
@@ -271,6 +288,10 @@ class BatchNorm2d(Module):
 BatchNorm = BatchNorm2d
 
 
+class BatchNorm1d(BatchNorm2d):
+    """levit.py:100 — F.batch_norm over axis 1 of (rows, C): BatchNorm2d's arithmetic."""
+
+
 class LayerNorm(Module):
     def __init__(self, normalized_shape, epsilon=1e-5, gamma_init="ones", beta_init="zeros", act=None, name=None):
         super().__init__(name=name)
@@ -293,6 +314,8 @@ class Linear(Module):
         self.weights = self.biases = None
         if in_features is not None:
             self._build(in_features)
+
+    b_init = property(lambda self: True if self._has_bias else None)          # cswin_transformer.py:433 reads `m.b_init is not None`
 
     def _build(self, in_features):
         self.weights = Parameter(str_to_init(self._w_init)(shape=(in_features, self.out_features)))
@@ -399,6 +422,14 @@ class Sigmoid(_A):
 
 class GELU(_A):
     fn = staticmethod(lambda x: F.gelu(x, approximate="none"))
+
+
+class Swish(_A):
+    fn = staticmethod(lambda x: x * torch.sigmoid(x))
+
+
+# segmentation/layers/activation.py:21-34 evals `nn.layers.activation.<Name>()`
+layers = types.SimpleNamespace(activation=types.SimpleNamespace(ReLU=ReLU))
 
 
 class LeakyReLU(Module):

@@ -27,6 +27,20 @@ class PdTensor(torch.Tensor):
         a = axis if axis is not None else dim
         return super().squeeze() if a is None else super().squeeze(a)
 
+    def flatten(self, start_axis=0, stop_axis=-1):          # cswin_transformer.py:79 names them
+        return torch.flatten(self, start_axis, stop_axis)
+
+    def chunk(self, chunks, axis=0):          # cswin_transformer.py:282,290
+        return torch.chunk(self, chunks, dim=axis)
+
+    def reshape(self, *shape, **kw):
+        """A 0 extent keeps that extent of the tensor (Paddle; levit.py:42 reshapes to (0, shape0, shape1)); mixnet.py:539 names `shape=`."""
+        if "shape" in kw:
+            shape = (kw["shape"],)
+        if len(shape) == 1 and isinstance(shape[0], (list, tuple, torch.Size)):
+            shape = tuple(shape[0])
+        return super().reshape(tuple(self.shape[i] if s == 0 else s for i, s in enumerate(shape)))
+
     def astype(self, dtype):
         return self.to(_DTYPES[dtype] if isinstance(dtype, str) else dtype)
 

@@ -1,6 +1,6 @@
 """Plain-torch restatement of DeepLabV3 / ResNet50_vd (output stride 8) taking the parameter dictionary of the reference
 model (tlxcv/models/segmentation/deeplab.py:134-189, backbones/resnet_vd.py, layers/pyramid_pool.py), NCHW, any dtype and
-device.  tools/gen_seg_golden.py checks it against the reference file; the GPU tests use it for sizes without a golden.
+device.  oracle/gen_golden.py checks it against the reference file; the GPU tests use it for sizes without a golden.
 Not a test module."""
 import numpy as np
 import torch

@@ -1,6 +1,6 @@
 """Plain-torch restatement of DeepLabV3+ / ResNet50_vd (output stride 8) taking the parameter dictionary of the reference model
 (tlxcv/models/segmentation/deeplab.py:9-131, 247-309; layers/layer_libs.py:53-133; layers/pyramid_pool.py), NCHW, any dtype and
-device.  The backbone blocks, the BN and the conv helpers are deeplab_restated's; tools/gen_segp_golden.py checks this against
+device.  The backbone blocks, the BN and the conv helpers are deeplab_restated's; oracle/gen_golden.py checks this against
 the reference file; the GPU tests use it for sizes without a golden.  Not a test module."""
 import torch
 import torch.nn.functional as F

@@ -32,8 +32,9 @@ def test_deeplabv3p_parameter_tree_matches_reference_model_file():
     from oracle.gen_golden import REF
     if not os.path.isdir(os.path.join(REF, "tlxcv", "models", "segmentation")):
         pytest.skip("reference tree not present")
-    code = ("import sys; sys.path.insert(0, 'tools'); import gen_segp_golden as G; from tlxcv_amd import seeded; "
-            "print('\\n'.join(f'{k} {v}' for k, v in seeded.shapes_of(G.reference_model(19, 'channels_first')).items()))")
+    code = ("from oracle import gen_golden as G; from tlxcv_amd import seeded; "
+            "model = G.deeplab_model(G.reference('deeplab'), 'deeplabv3p', 19, 'channels_first'); "
+            "print('\\n'.join(f'{k} {v}' for k, v in seeded.shapes_of(model).items()))")
     out = subprocess.check_output([sys.executable, "-c", code], cwd=REPO, text=True)
     from tlxcv_amd import seeded
     from tlxcv_amd.models import deeplabv3p

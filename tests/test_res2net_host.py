@@ -44,8 +44,7 @@ def test_parameter_tree_matches_reference_model_file():
     from oracle.gen_golden import REF
     if not os.path.isfile(os.path.join(REF, "tlxcv", "models", "classification", "res2net.py")):
         pytest.skip("reference tree not present")
-    code = ("import sys; sys.path.insert(0, 'tools'); import gen_res2net_golden as G; from tlxcv_amd import seeded; "
-            "ref, _ = G.load_reference(); "
+    code = ("from oracle import gen_golden as G; from tlxcv_amd import seeded; ref = G.reference('res2net'); "
             "print('\\n'.join(f'{k} {v}' for k, v in seeded.shapes_of(ref.Res2Net(layers=101, scales=6, width=16, class_num=7)).items()))")
     out = subprocess.check_output([sys.executable, "-c", code], cwd=REPO, text=True)
     from tlxcv_amd import seeded

@@ -31,9 +31,10 @@ def test_deeplabv3_parameter_tree_matches_reference_model_file():
     from oracle.gen_golden import REF          # where the fixture generator reads the reference tree
     if not os.path.isdir(os.path.join(REF, "tlxcv", "models", "segmentation")):
         pytest.skip("reference tree not present")
-    # the generator's import path (oracle/tlx_cpu stand-in, run-time tlx.Resize, stage_list registration), in a fresh process
-    code = ("import sys; sys.path.insert(0, 'tools'); import gen_seg_golden as G; from tlxcv_amd import seeded; "
-            "print('\\n'.join(f'{k} {v}' for k, v in seeded.shapes_of(G.reference_model(19, 'channels_first')).items()))")
+    # the generator's import path (oracle/tlx_cpu stand-in with its tlx.Resize, stage_list registration), in a fresh process
+    code = ("from oracle import gen_golden as G; from tlxcv_amd import seeded; "
+            "model = G.deeplab_model(G.reference('deeplab'), 'deeplabv3', 19, 'channels_first'); "
+            "print('\\n'.join(f'{k} {v}' for k, v in seeded.shapes_of(model).items()))")
     out = subprocess.check_output([sys.executable, "-c", code], cwd=REPO, text=True)
     from tlxcv_amd import seeded
     from tlxcv_amd.models import deeplabv3

@@ -52,8 +52,7 @@ def test_parameter_tree_matches_reference_model_file():
     from oracle.gen_golden import REF
     if not os.path.isfile(os.path.join(REF, "tlxcv", "models", "classification", "squeezenet.py")):
         pytest.skip("reference tree not present")
-    code = ("import sys; sys.path.insert(0, 'tools'); import gen_squeezenet_golden as G; from tlxcv_amd import seeded; "
-            "ref = G.load_reference(); "
+    code = ("from oracle import gen_golden as G; from tlxcv_amd import seeded; ref = G.reference('squeezenet'); "
             "print('\\n'.join(f'{v} {k} {s}' for v in ('1.0', '1.1') for k, s in seeded.shapes_of(ref.SqueezeNet(v, num_classes=7)).items()))")
     out = subprocess.check_output([sys.executable, "-c", code], cwd=REPO, text=True)
     from tlxcv_amd import seeded

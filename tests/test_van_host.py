@@ -109,8 +109,7 @@ def test_parameter_tree_matches_reference_model_file():
     from oracle.gen_golden import REF
     if not os.path.isfile(os.path.join(REF, "tlxcv", "models", "classification", "van.py")):
         pytest.skip("reference tree not present")
-    code = ("import sys; sys.path.insert(0, 'tools'); import gen_van_golden as G; from tlxcv_amd import seeded; "
-            "ref, _ = G.reference_module(); "
+    code = ("from oracle import gen_golden as G; from tlxcv_amd import seeded; ref = G.reference('van'); "
             "print('\\n'.join(f'{k} {v}' for c in (1000, 0) for k, v in seeded.shapes_of(ref.van(class_num=c)).items()))")
     out = subprocess.check_output([sys.executable, "-c", code], cwd=REPO, text=True)
     from tlxcv_amd import seeded
