@@ -707,6 +707,30 @@ size_t tlxmi_fire_module_param_bytes(int Cin, int sq, int e1, int e3);
 int tlxmi_fire_module(const tlxmi_fire_module_desc* d, const void* x, const void* params, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DPN's dual-path 1x1 conv (classification/dpn.py:103-126): the conv that ends a DualPathFactory, with the split of its output, the
+ * add onto the residual path and the concat onto the dense path in its epilogue — one launch, fp16, fp32 accumulation on MFMA.
+ *     state[m*ld + n]             = fp16( float(state[m*ld + n]) + sum_k t[m*t_ld + k] * W[n][k] )       n < bw,  m < rows
+ *     state[m*ld + dense_off + j] = fp16( sum_k t[m*t_ld + k] * W[bw + j][k] )                           j < inc, m < rows
+ * t: rows x K, pitch t_ld >= K, already activated (the producer's epilogue applied this conv's BatchNorm + ReLU); columns k >= K are
+ * never multiplied, whatever they hold (NaN included).  w_packed: tlxmi_pack_filter of the [bw + inc][K][1][1] filter.  No scale,
+ * shift or activation: the output is raw.
+ * IN PLACE: state is both the residual and the output — a stage's NHWC buffer at pixel pitch ld.  The residual is added in fp32 and
+ * the sum is rounded once.  Each residual element is read and written by exactly one lane of one workgroup (the lane that owns its
+ * 8-channel group), so the launch needs no ordering between workgroups and its result does not depend on their schedule.  Nothing
+ * outside the columns [0, bw) and [dense_off, dense_off + inc) of the `rows` rows is written; the columns [bw, dense_off) — the dense
+ * channels of earlier blocks — are neither read nor written.  t must not overlap state.
+ * tlxmi_dual_path_conv1x1_supported() is pure host code and answers 1 exactly for: fp16; K, bw, inc, dense_off, t_ld, ld positive
+ * multiples of 8 with t_ld >= K, dense_off >= bw and dense_off + inc <= ld; rows > 0 with rows * ld * 2 and rows * t_ld * 2 below 2^31
+ * (32-bit byte offsets; the packed filter, roundup(bw + inc, 128) x roundup(2 K, 128) bytes, below 2^31 as well).  1 means the call is
+ * taken, given t, w_packed and state 16-byte aligned (TLXMI_ERR_ALIGNMENT otherwise); anything the predicate refuses returns
+ * TLXMI_ERR_UNSUPPORTED (run tlxmi_conv2d twice instead: filter rows [0, bw) with state as residual and output, rows [bw, bw + inc)
+ * into the column slice).
+ * ---------------------------------------------------------------------------------------- */
+int tlxmi_dual_path_conv1x1_supported(int dtype, int64_t rows, int K, int bw, int inc, int dense_off, int t_ld, int ld);
+int tlxmi_dual_path_conv1x1(int dtype, int64_t rows, int K, int bw, int inc, int dense_off, int t_ld, int ld, const void* t,
+                            const void* w_packed, void* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

@@ -205,6 +205,7 @@ PROTOTYPES = {
     "tlxmi_res2_chain": [C.POINTER(Res2ChainDesc), _vp, _vp, _vp, _vp],
     "tlxmi_inception_head": [C.POINTER(InceptionHeadDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_fire_module": [C.POINTER(FireModuleDesc), _vp, _vp, _vp, _vp],
+    "tlxmi_dual_path_conv1x1": [_i, _l, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -248,6 +249,7 @@ _SPECIAL = {
     "tlxmi_inception_head_param_bytes": ([_i, _i, _i, _i, _i], C.c_size_t),
     "tlxmi_fire_module_supported": ([C.POINTER(FireModuleDesc)], C.c_int),
     "tlxmi_fire_module_param_bytes": ([_i, _i, _i, _i], C.c_size_t),
+    "tlxmi_dual_path_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i], C.c_int),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

@@ -106,6 +106,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # engine.FIRE_MODULE_WINS): squeeze 1x1 -> expand 1x1 | expand 3x3 on tlxmi_fire_module: ONE launch, x read
                                   # once, the squeeze map of a haloed pixel tile in LDS only, both expands written into their slices of the output
                                   # map; elsewhere and off = tlxmi_conv2d x 3 with bias + ReLU epilogues (the A/B and the tests' other arm)
+            "dual_path": True,    # DPN's `c` convs (fp16, widths multiples of 8; the shapes the measured table keeps: engine.DUAL_PATH_WINS,
+                                  # DESIGN 4.33): the 1x1 conv whose output is split, added onto the residual path IN PLACE and appended to the
+                                  # dense path of the stage buffer on tlxmi_dual_path_conv1x1: ONE launch, the operand read once; elsewhere and
+                                  # off = tlxmi_conv2d twice on the two row ranges of the filter (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -2188,6 +2192,97 @@ def fire_module(x, params, fused=None, out=None):
     _timed(launch, lambda: ((M * (p.cin + p.cout) + nw) * es, 2 * M * nw,
                             (N, H, W, p.cin, p.cout, "fire_module" if fused else "conv-conv-conv")))      # the chain is one entry
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# DPN's dual-path 1x1 conv: split -> add onto the residual path | concat onto the dense path
+# ---------------------------------------------------------------------------------------------
+class DualPathParams:
+    """The `c` conv of a DualPathFactory (dpn.py:103-105) in the forms both arms of dual_path_conv1x1() read: the whole (bw + inc, K, 1, 1)
+    filter packed once for the launch, and its row ranges [0, bw) — the residual path — and [bw, bw + inc) — the dense path — packed once
+    each for the layer-by-layer arm.  w: the filter as the kernels see it, i.e. with the host's zero padding already in (K, bw and inc
+    multiples of 8: a DPN width that is not is padded by the model, never refused here and never seen by a kernel).
+    packed: the layer's own PackedFilter of w at this precision, where a model holds it already."""
+
+    def __init__(self, w, bw, dtype, packed=None):
+        cout, self.K = int(w.shape[0]), int(w.shape[1])
+        self.bw, self.inc = int(bw), cout - int(bw)
+        if tuple(w.shape[2:]) != (1, 1) or any(n <= 0 or n % 8 for n in (self.K, self.bw, self.inc)):
+            raise RuntimeError(f"DualPathParams: a 1x1 filter (bw + inc, K) with K, bw and inc positive multiples of 8 is expected; got "
+                               f"{tuple(w.shape)} with bw {bw}")
+        self.dtype = dtype
+        w = w.detach()
+        self.pk = packed if packed is not None else PackedFilter(w, dtype)
+        self.pk_res, self.pk_dense = PackedFilter(w[:self.bw], dtype), PackedFilter(w[self.bw:], dtype)
+
+
+def dual_path_takes(t, params, state, dense_off):
+    """Whether the library's tlxmi_dual_path_conv1x1 takes these operands (fp16, the widths and pitches of include/tlxmi.h): what
+    fused=True needs."""
+    if t.dtype != torch.float16 or state.dtype != torch.float16 or params.dtype != torch.float16:
+        return False
+    rows = state.numel() // state.shape[-1]
+    return bool(_lib.load().tlxmi_dual_path_conv1x1_supported(F16, rows, params.K, params.bw, params.inc, int(dense_off), t.shape[-1],
+                                                               state.shape[-1]))
+
+
+# (pixels per image H * W, K, bw, inc) of the `c` convs where the one launch was measured FASTER than the two layered launches in every
+# round — its slowest round against the layers' fastest — at batch 256 on one MI355X (tools/dpn_bench.py,
+# profiles/dpn/dpn_bench_b256.txt, DESIGN 4.33): dual_path_conv1x1() keeps the launch there and runs the layers everywhere else by
+# default.  dense_off is not part of the key: it moves a store, not the work (each shape was timed at its stage's last block).
+# MEASURED over the eight distinct shapes of DPN-68 and DPN-107 at 224 x 224: the launch wins all four of DPN-68 (0.66 - 0.82 of the
+# layers' time) and DPN-107's 56 x 56 and 28 x 28 stages (0.70, 0.83); at DPN-107's 14 x 14 (K 800, bw 1024) and 7 x 7 (K 1600, bw 2048)
+# stages it is 0.99 / 1.00 of the layers' time with overlapping rounds — not a win, so they stay on the layers.  Shapes other than
+# those eight (DPN-92 / 98 / 131, other input sizes) are unmeasured and run layer by layer.
+DUAL_PATH_WINS = frozenset({(3136, 128, 64, 16), (784, 256, 128, 32), (196, 512, 256, 32), (49, 1024, 512, 64),
+                            (3136, 200, 256, 24), (784, 400, 512, 64)})
+
+
+def _dual_path_routed(pixels, p):
+    return (pixels, p.K, p.bw, p.inc) in DUAL_PATH_WINS
+
+
+def dual_path_conv1x1(t, pk, state, bw, dense_off, fused=None):
+    """The conv that ends a DualPathFactory (dpn.py:121-126), IN PLACE on the stage buffer `state` (N, H, W, ld):
+        state[..., :bw] += t . W[:bw]          (the residual path: fp32 add, one rounding)
+        state[..., dense_off:dense_off + inc] = t . W[bw:]          (the dense path: this block's inc new channels)
+    t (N, H, W, t_ld) NHWC, its first K channels the operand — already activated: the 3x3's epilogue applied this conv's BatchNorm +
+    ReLU.  pk: DualPathParams (bw must be its bw).  Nothing else of state is written; the columns [bw, dense_off) are the earlier
+    blocks' dense channels.  One launch (tlxmi_dual_path_conv1x1) when the "dual_path" option is on, the precision is fp16, the measured
+    table keeps the shape and the library takes it; otherwise — and always for fp32: the parity reference — tlxmi_conv2d twice on the
+    same packed operands: filter rows [0, bw) with res = out = state, rows [bw, bw + inc) into the column slice at dense_off.
+    fused=True / False forces one form (tests, tools/); True raises where the launch is not supported.  -> state."""
+    need_gpu(t, "input")
+    p = pk
+    if t.dim() == 2:
+        t = t.view(t.shape[0], 1, 1, t.shape[1])
+    if state.dim() == 2:
+        state = state.view(state.shape[0], 1, 1, state.shape[1])
+    N, H, W, ld = state.shape
+    t_ld, dense_off = t.shape[-1], int(dense_off)
+    vw = vec(t.dtype)
+    if (int(bw) != p.bw or t.dtype != p.dtype or state.dtype != p.dtype or tuple(t.shape[:3]) != (N, H, W) or t_ld < p.K or t_ld % vw
+            or ld % vw or dense_off % vw or dense_off < p.bw or dense_off + p.inc > ld or not t.is_contiguous() or not state.is_contiguous()):
+        raise RuntimeError(f"dual_path_conv1x1: t {tuple(t.shape)} {t.dtype} and state {tuple(state.shape)} {state.dtype} must be dense NHWC maps "
+                           f"of the parameters' dtype over the same pixels, t with at least K = {p.K} channels, bw = {p.bw} <= dense_off = "
+                           f"{dense_off} and dense_off + inc = {dense_off + p.inc} <= the state's pitch, pitches and dense_off multiples of {vw}")
+    takes = lambda: dual_path_takes(t, p, state, dense_off)      # noqa: E731
+    # the option and the table first: the library's predicate is asked only where they keep the launch
+    fused = _use_fused("dual_path_conv1x1", fused, takes, lambda: _options["dual_path"] and _dual_path_routed(H * W, p) and takes(),
+                       lambda: f"t {tuple(t.shape)} {t.dtype}, state {tuple(state.shape)} with K {p.K}, bw {p.bw}, inc {p.inc}, dense_off {dense_off}")
+    es = t.element_size()
+    M = N * H * W
+    if _sizing():
+        _note_act(t.numel() * es, M * ld * es)
+    if not fused:       # two launches, each its own probe entry
+        conv2d(t, p.pk_res, res=state, out=state, out_ld=ld, res_ld=ld)
+        conv2d(t, p.pk_dense, out=state[..., dense_off:dense_off + p.inc], out_ld=ld)
+        return state
+    args = (F16, M, p.K, p.bw, p.inc, dense_off, t_ld, ld, _p(t), _p(p.pk.buf), _p(state), _stream())
+    _timed(lambda: _lib.call("tlxmi_dual_path_conv1x1", *args),
+           lambda: ((M * (p.K + 2 * p.bw + p.inc) + (p.bw + p.inc) * p.K) * es, 2 * M * (p.bw + p.inc) * p.K,
+                    (N, H, W, p.K, p.bw, p.inc, "dual_path")))
+    return state
 
 
 # ---------------------------------------------------------------------------------------------

@@ -45,3 +45,5 @@ from .mixnet import (MixNet, MixUnit, MixInitBlock, MixConv, MixConvBlock, mixco
 from .res2net import Res2Net, res2net  # noqa: F401
 from .googlenet import GoogLeNet, ConvLayer, Inception, googlenet  # noqa: F401
 from .squeezenet import SqueezeNet, MakeFire, MakeFireConv, squeezenet1_0, squeezenet1_1  # noqa: F401
+# (the DPN file's ConvBNLayer / BNACConvLayer stay in their module: DenseNet's own those names here)
+from .dpn import DPN, DualPathFactory, dpn68, dpn107  # noqa: F401

@@ -25,6 +25,10 @@ _RES2NET_CHAIN = re.compile(r"^bb_\d+_\d+\.res\d+\w*_branch2b_\d+\.")
 _RES2NET_LAST_BN = re.compile(r"^bb_\d+_\d+\.conv2\.batch_norm$")
 # SqueezeNet (squeezenet.py:37-46): a Fire module's expand 1x1, registered as _conv<k>._conv_path1 — a name no other tree has
 _SQUEEZENET_FIRE = re.compile(r"^_conv\d+\._conv_path1\._conv\.")
+# DPN (dpn.py:103-105, :121-126): a DualPathFactory's last conv, registered as dpn<k>.c1x1_c_func — a name no other tree has; its first
+# bw output channels are added to the residual path, which nothing normalises
+_DPN_C = re.compile(r"^dpn\d+\.c1x1_c_func\._conv\.")
+DPN_C_GAIN = 0.6
 
 
 def image_batch(n, seed=0, hw=224, c=3):
@@ -106,10 +110,20 @@ def fill(shapes, seed):
                                  from a correct one.  With zero-mean filters 6 of 8 seeds (1.0) and 5 of 8 (1.1) give distinct, separated
                                  argmaxes, module outputs peak between 0.6 and 15 and the logit range is 0.1 - 0.3.  Same number of draws: the
                                  values drawn for every other model are unchanged
+      dpn<k>.c1x1_c_func._conv.filters   in a tree that has DPN's DualPathFactories (dpn.py:103-105) only: drawn exactly as above, then scaled by
+                                 DPN_C_GAIN = 0.6.  The first bw outputs of that conv are ADDED to the residual path, which no BatchNorm
+                                 ever normalises (eval-mode BatchNorm is an affine map), and every block reads that path again: under the
+                                 general rule the block states grow geometrically — DPN-68 at 96 x 160 peaks between 970 and 2280 over its 22
+                                 blocks (7 of 8 seeds above the generator's limit of 1000), DPN-107 at 64 x 96 between 25 800 and 51 600 with
+                                 logit ranges of 7 400 - 25 000: outside fp16.  With the gain DPN-68's states peak at 47 (224 x 224) and 78, DPN-107's
+                                 at 314.  A smaller gain starves the image-dependent part of the features: at 0.25 and 0.5 the two rows of
+                                 the batch-2 fixture share one argmax for all eight seeds.
+                                 Same number of draws: the values drawn for every other model are unchanged
     """
     rng = np.random.default_rng(seed)
     res2net = any(_RES2NET_CHAIN.match(n) for n in shapes)
     squeezenet = any(_SQUEEZENET_FIRE.match(n) for n in shapes)
+    dpn = any(_DPN_C.match(n) for n in shapes)
     out = {}
     for name, shape in shapes.items():
         shape = tuple(shape)
@@ -131,6 +145,8 @@ def fill(shapes, seed):
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(np.sqrt(2.0 / fan_in))
             if squeezenet and a.size:
                 a = a - a.reshape(shape[0], -1).mean(axis=1, dtype=np.float32).reshape((shape[0],) + (1,) * (len(shape) - 1))
+            if dpn and _DPN_C.match(name):
+                a = a * np.float32(DPN_C_GAIN)
         elif leaf == "weights" and ("attn_in." in owner + "." or "mlp_in." in owner + "."):      # TNT's inner transformer (tnt.py:125-129)
             gain = 1.5 if (owner + ".").endswith("attn_in.qk.") else 1.0
             a = rng.standard_normal(shape, dtype=np.float32) * np.float32(gain / np.sqrt(shape[0]))
