@@ -731,6 +731,41 @@ int tlxmi_dual_path_conv1x1(int dtype, int64_t rows, int K, int bw, int inc, int
                             const void* w_packed, void* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * HarDNet's linked conv (classification/hardnet.py:85-97): a layer of a HarDBlock without the concat in front of it — one launch,
+ * fp16, fp32 accumulation on MFMA.  A stride-1 "same" conv (R x R, R 1 or 3, padding R / 2) whose input channels are the
+ * concatenation, in the order given, of nseg column slices [seg_off[s], seg_off[s] + seg_c[s]) of ONE NHWC map x (N x H x W pixels at
+ * pitch x_ld); the slices need not ascend:
+ *     y[p*y_ld + n] = fp16( act( scale[n] * sum_{taps d} sum_s sum_{c < seg_c[s]} x[(p + d)*x_ld + seg_off[s] + c] * W[n][k(s) + c][d]
+ *                                + shift[n] ) )                                              n < Cout,  k(s) = seg_c[0] + .. + seg_c[s-1]
+ * A tap outside the image contributes zero (the neighbouring image of the batch is never read).  Columns of x in no segment are never
+ * loaded, whatever they hold (NaN included).  w_packed: tlxmi_pack_filter of the [Cout][sum seg_c][R][R] filter — the image
+ * tlxmi_conv2d reads, so the same buffer serves a layer-by-layer run on a gathered copy.  scale / shift: fp32 [Cout], either may be
+ * null (1 / 0).  x points at column 0 of the map, y at the first output column.
+ * y_off: -1 when y lies outside x; else y IS the column slice [y_off, y_off + Cout) of x (y == x + 2 y_off bytes, y_ld == x_ld), which
+ * must overlap no segment: a workgroup then writes only columns that no workgroup reads, so the result does not depend on the
+ * schedule.  Nothing outside the Cout columns of the N*H*W pixels is written.  One writer per element, fixed summation order.
+ * tlxmi_link_conv2d_supported() is pure host code and answers 1 exactly for: fp16; N, H, W >= 1 (H, W < 32768); R 1 or 3; nseg 1 .. 8;
+ * every seg_off >= 0, seg_c >= 8, Cout >= 8, x_ld and y_ld multiples of 8 with seg_off + seg_c <= x_ld and Cout <= y_ld; act
+ * TLXMI_ACT_NONE, _RELU or _RELU6; y_off -1, or a multiple of 8 with y_ld == x_ld, y_off + Cout <= x_ld and no overlap with a segment;
+ * N*H*W * pitch * 2 below 2^31 for both pitches and the packed filter below 2^31 bytes (32-bit byte offsets).  1 means the call is
+ * taken, given x, w_packed and y 16-byte aligned (TLXMI_ERR_ALIGNMENT otherwise) and related as y_off says (TLXMI_ERR_BAD_ARG
+ * otherwise); anything the predicate refuses returns TLXMI_ERR_UNSUPPORTED (gather the slices with tlxmi_copy_channels and run
+ * tlxmi_conv2d instead).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct tlxmi_link_conv_desc {
+    int32_t dtype;
+    int32_t N, H, W, R;
+    int32_t nseg;
+    int32_t seg_off[8], seg_c[8];
+    int32_t Cout;
+    int32_t x_ld, y_ld, y_off;
+    int32_t act;
+} tlxmi_link_conv_desc;
+int tlxmi_link_conv2d_supported(const tlxmi_link_conv_desc* d);
+int tlxmi_link_conv2d(const tlxmi_link_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift, void* y,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

@@ -74,6 +74,11 @@ class FireModuleDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "N", "H", "W", "Cin", "sq", "e1", "e3", "x_ld", "y_ld")]
 
 
+class LinkConvDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("dtype", "N", "H", "W", "R", "nseg")] + [("seg_off", C.c_int32 * 8), ("seg_c", C.c_int32 * 8)]
+                + [(n, C.c_int32) for n in ("Cout", "x_ld", "y_ld", "y_off", "act")])
+
+
 class LkaGateDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("rows", C.c_int64)] + [(n, C.c_int32) for n in ("C", "a1_ld", "t_ld", "res_ld", "y_ld")]
 
@@ -206,6 +211,7 @@ PROTOTYPES = {
     "tlxmi_inception_head": [C.POINTER(InceptionHeadDesc), _vp, _vp, _vp, _vp, _vp],
     "tlxmi_fire_module": [C.POINTER(FireModuleDesc), _vp, _vp, _vp, _vp],
     "tlxmi_dual_path_conv1x1": [_i, _l, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "tlxmi_link_conv2d": [C.POINTER(LinkConvDesc), _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -250,6 +256,7 @@ _SPECIAL = {
     "tlxmi_fire_module_supported": ([C.POINTER(FireModuleDesc)], C.c_int),
     "tlxmi_fire_module_param_bytes": ([_i, _i, _i, _i], C.c_size_t),
     "tlxmi_dual_path_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i], C.c_int),
+    "tlxmi_link_conv2d_supported": ([C.POINTER(LinkConvDesc)], C.c_int),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

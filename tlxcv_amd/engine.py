@@ -110,6 +110,10 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # DESIGN 4.33): the 1x1 conv whose output is split, added onto the residual path IN PLACE and appended to the
                                   # dense path of the stage buffer on tlxmi_dual_path_conv1x1: ONE launch, the operand read once; elsewhere and
                                   # off = tlxmi_conv2d twice on the two row ranges of the filter (the A/B and the tests' other arm)
+            "link_conv": True,    # HarDNet's multi-link layers (fp16, R 1 or 3, up to 8 links, widths multiples of 8; the shapes the measured table
+                                  # keeps: engine.LINK_CONV_WINS): the conv of a HarDBlock layer reads its linked layers as column
+                                  # slices of the block buffer IN PLACE on tlxmi_link_conv2d: ONE launch, no concat pass; elsewhere and off = one
+                                  # tlxmi_copy_channels a link into a scratch map, then tlxmi_conv2d (the A/B and the tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -2286,6 +2290,111 @@ def dual_path_conv1x1(t, pk, state, bw, dense_off, fused=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# HarDNet's linked conv: a layer that convolves the concat of up to 8 column slices of the block buffer
+# ---------------------------------------------------------------------------------------------
+class LinkConvParams:
+    """A multi-link layer of a HarDBlock (hardnet.py:85-97) in the form both arms of link_conv2d() read: the (Cout, K, R, R) filter
+    packed once — K the sum of the links' widths in link order — with the epilogue's fp32 scale and shift.  w, scale, shift: as the
+    kernels see them, i.e. with the host's zero padding already in (Cout and every link width multiples of 8: a HarDNet width that is
+    not is padded by the model, never refused here and never seen by a kernel).  packed: the layer's own PackedFilter of w at this
+    precision, where a model holds it already."""
+
+    def __init__(self, w, scale, shift, dtype, packed=None):
+        self.Cout, self.K, self.R, s_ = (int(v) for v in w.shape)
+        if self.R != s_ or self.R not in (1, 3) or self.Cout % 8 or self.K % 8:
+            raise RuntimeError(f"LinkConvParams: a (Cout, K, R, R) filter with R 1 or 3 and Cout, K multiples of 8 is expected; got {tuple(w.shape)}")
+        self.dtype = dtype
+        self.pk = packed if packed is not None else PackedFilter(w.detach(), dtype)
+        self.scale, self.shift = _f32(scale), _f32(shift)
+
+
+def _link_conv_desc(buf, segments, p, act, out, out_ld):
+    N, H, W, ld = buf.shape
+    es = buf.element_size()
+    d = out.data_ptr() - buf.data_ptr()
+    inside = 0 <= d < buf.numel() * es          # out is a view into the map: its column (anything but a slice of pixel 0 is refused)
+    return _lib.LinkConvDesc(dtype=dt_code(buf.dtype), N=N, H=H, W=W, R=p.R, nseg=len(segments),
+                             seg_off=(C.c_int32 * 8)(*[int(o) for o, _ in segments]), seg_c=(C.c_int32 * 8)(*[int(c) for _, c in segments]),
+                             Cout=p.Cout, x_ld=ld, y_ld=int(out_ld), y_off=d // es if inside else -1, act=int(act))
+
+
+def link_conv_takes(buf, segments, params, act, out, out_ld):
+    """Whether the library's tlxmi_link_conv2d takes these operands (fp16, the widths, pitches and disjointness of include/tlxmi.h): what
+    fused=True needs."""
+    if buf.dtype != torch.float16 or out.dtype != torch.float16 or params.dtype != torch.float16 or not 1 <= len(segments) <= 8:
+        return False
+    return bool(_lib.load().tlxmi_link_conv2d_supported(C.byref(_link_conv_desc(buf, segments, params, act, out, out_ld))))
+
+
+# (pixels per image H * W, R, the links' widths in link order, Cout) of the multi-link layers where the one launch was measured FASTER
+# than the layered arm in every round — its slowest round against the layers' fastest — at batch 256 on one MI355X
+# (tools/hardnet_bench.py, profiles/hardnet/hardnet_bench_b256.txt, DESIGN 4.34): link_conv2d() keeps the launch there and runs the
+# layers everywhere else, unmeasured shapes included, by default.  Where the slices sit is not part of the key: it moves addresses, not
+# the work.
+# MEASURED over the 49 distinct multi-link shapes of HarDNet-85 (34, all 3x3) and HarDNet-39ds (15, all 1x1) at 224 x 224: the launch wins
+# every 1x1 shape (0.39 - 0.73 of the layers' time: there the copy moves more bytes than the conv) and two small 3x3 shapes at 14 x 14
+# (0.86, 0.97); at the other 32 3x3 shapes the tuned tlxmi_conv2d behind its copies is FASTER (the launch takes 1.02 - 1.58 of its time),
+# so they stay on the layers.  Shapes other than those 49 (HarDNet-68 / 68ds, other input sizes) are unmeasured and run layer by layer.
+LINK_CONV_WINS = frozenset({
+    (3136, 1, (16, 48), 32), (3136, 1, (16, 32, 48), 40),
+    (784, 1, (24, 96), 32), (784, 1, (24, 32, 96), 56), (784, 1, (24, 56), 32), (784, 1, (24, 32, 56, 96), 88), (784, 1, (24, 88), 32),
+    (784, 1, (24, 32, 88), 56), (784, 1, (24, 32, 56, 88, 96), 136),
+    (196, 1, (64, 320), 104), (196, 1, (64, 104, 320), 168), (196, 1, (64, 168), 104), (196, 1, (64, 104, 168, 320), 264),
+    (49, 1, (160, 640), 256), (49, 1, (160, 256, 640), 416),
+    (196, 3, (40, 104), 64), (196, 3, (40, 176), 64)})
+
+
+def _link_conv_routed(pixels, segments, p):
+    return (pixels, p.R, tuple(int(c) for _, c in segments), p.Cout) in LINK_CONV_WINS
+
+
+def link_conv2d(buf, segments, params, act, out, out_ld=None, fused=None):
+    """A multi-link layer of a HarDBlock on the block buffer `buf` (N, H, W, ld) NHWC:
+        out[..., :Cout] = act(scale * conv RxR pad R/2 (concat_s buf[..., off_s:off_s + c_s]) + shift)
+    segments: [(off, c)] in link order (need not ascend), every value a multiple of 8.  params: LinkConvParams.  out: a column slice of
+    buf that overlaps no segment (a view), or a map of its own; out_ld its pixel pitch (default: out's pixel stride).
+    One launch (tlxmi_link_conv2d) when the "link_conv" option is on, the precision is fp16, the measured table keeps the shape and the
+    library takes it; otherwise — and always for fp32: the parity reference — one tlxmi_copy_channels a segment into a scratch map,
+    then tlxmi_conv2d on the same packed filter.  fused=True / False forces one form (tests, tools/); True raises where the launch is
+    not supported.  -> out."""
+    need_gpu(buf, "input")
+    p = params
+    N, H, W, ld = buf.shape
+    segments = [(int(o), int(c)) for o, c in segments]
+    vw = vec(buf.dtype)
+    out_ld = int(out_ld if out_ld is not None else out.stride(2))
+    if (buf.dtype != p.dtype or out.dtype != p.dtype or not buf.is_contiguous() or tuple(out.shape[:3]) != (N, H, W) or out.shape[-1] < p.Cout
+            or not segments or sum(c for _, c in segments) != p.K or ld % vw or out_ld % vw
+            or any(o < 0 or c <= 0 or o % vw or c % vw or o + c > ld for o, c in segments)):
+        raise RuntimeError(f"link_conv2d: buf {tuple(buf.shape)} {buf.dtype} must be a dense NHWC map of the parameters' dtype, out "
+                           f"{tuple(out.shape)} a map over the same pixels with at least Cout = {p.Cout} channels, the segments {segments} "
+                           f"column slices of buf whose widths add up to K = {p.K}, every offset, width and pitch a multiple of {vw}")
+    takes = lambda: link_conv_takes(buf, segments, p, act, out, out_ld)      # noqa: E731
+    # the option and the table first: the library's predicate is asked only where they keep the launch
+    fused = _use_fused("link_conv2d", fused, takes, lambda: _options["link_conv"] and _link_conv_routed(H * W, segments, p) and takes(),
+                       lambda: f"buf {tuple(buf.shape)} {buf.dtype} with segments {segments}, R {p.R}, Cout {p.Cout}, act {act}, out at pitch {out_ld}")
+    es = buf.element_size()
+    M = N * H * W
+    if _sizing():
+        _note_act(buf.numel() * es, M * out_ld * es)
+
+    def launch():
+        if fused:
+            _lib.call("tlxmi_link_conv2d", C.byref(_link_conv_desc(buf, segments, p, act, out, out_ld)), _p(buf), _p(p.pk.buf), _p(p.scale),
+                      _p(p.shift), _p(out), _stream())
+            return
+        gathered = torch.empty((N, H, W, p.K), dtype=buf.dtype, device=buf.device)
+        k = 0
+        for o, c in segments:
+            copy_channels_into(buf[..., o:o + c], gathered, k, x_ld=ld)
+            k += c
+        conv2d(gathered, p.pk, 1, p.R // 2, 1, p.scale, p.shift, act=act, out=out, out_ld=out_ld)
+    _timed(launch, lambda: ((M * (p.K + p.Cout) + p.Cout * p.K * p.R * p.R) * es, 2 * M * p.Cout * p.K * p.R * p.R,
+                            (N, H, W, p.K, p.Cout, p.R, "link_conv" if fused else "copy-conv")))      # the chain is one entry
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # pooling / elementwise / norm
 # ---------------------------------------------------------------------------------------------
 def maxpool2d(x, kernel, stride, padding, out=None, out_ld=None):
@@ -3088,14 +3197,15 @@ def upsample2x_into(x, out, c_off):
     return out
 
 
-def copy_channels_into(x, out, c_off):
-    """out[..., c_off:c_off+C] = x   (tlx.concat along channels, one pass per source)."""
+def copy_channels_into(x, out, c_off, x_ld=None):
+    """out[..., c_off:c_off+C] = x   (tlx.concat along channels, one pass per source).
+    x_ld: the pixel pitch when x is a column slice of a wider map (a view: its last axis is the slice's width)."""
     need_gpu(x, "input")
     Cc = x.shape[-1]
     rows = x.numel() // Cc
     es = x.element_size()
     dst = C.c_void_p(out.data_ptr() + c_off * es)
-    _lib.call("tlxmi_copy_channels", _p(x), dst, dt_code(x.dtype), rows, Cc, Cc, out.shape[-1], _stream())
+    _lib.call("tlxmi_copy_channels", _p(x), dst, dt_code(x.dtype), rows, Cc, Cc if x_ld is None else int(x_ld), out.shape[-1], _stream())
     return out
 
 

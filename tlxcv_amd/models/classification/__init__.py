@@ -47,3 +47,5 @@ from .googlenet import GoogLeNet, ConvLayer, Inception, googlenet  # noqa: F401
 from .squeezenet import SqueezeNet, MakeFire, MakeFireConv, squeezenet1_0, squeezenet1_1  # noqa: F401
 # (the DPN file's ConvBNLayer / BNACConvLayer stay in their module: DenseNet's own those names here)
 from .dpn import DPN, DualPathFactory, dpn68, dpn107  # noqa: F401
+# (the HarDNet file's ConvLayer stays in its module: GoogLeNet's owns that name here)
+from .hardnet import HarDNet, HarDBlock, DWConvLayer, CombConvLayer, hardnet39, hardnet85  # noqa: F401
