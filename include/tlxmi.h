@@ -287,7 +287,9 @@ int tlxmi_bottleneck_seam_dec(const tlxmi_seam_desc* d, int H, int W, const void
  * map is neither written nor read.  The caller folds both BatchNorm scales into the filter, W' = [diag(s3) W3 | diag(sd) Wd] as one
  * [Cout][K1 + K2][1][1] filter through tlxmi_pack_filter, and passes shift = h3 + hd (fp32 [Cout], or NULL for 0).
  * x: rows of pitch x_ld (K1 columns read), x2: pixels of pitch x2_ld (K2 columns read), y: rows of pitch y_ld (Cout columns
- * written, nothing else).  d->flags: TLXMI_PLAN_SHARED_* planning hints only.
+ * written, nothing else).  d->flags: TLXMI_PLAN_SHARED_* planning hints only.  The library picks the tile form of the launch
+ * (one 8-wave workgroup per CU on 256 x 256 or 128 x 256 tiles, or two 4-wave workgroups per CU on 256 x 128 tiles) by its own
+ * price on the CUs the launch is planned for; every form takes every operand set the predicate below admits.
  * tlxmi_conv1x1_proj_supported() is pure host code (no HIP call) and answers 1 exactly when the call is taken:
  *   - d->dtype == TLXMI_F16; N, Ho, Wo, H2, W2 positive with Ho / Wo as above; stride 1 or 2; act a valid tlxmi_act;
  *   - K1 and K2 positive multiples of 64 (a 128-byte K tile never straddles the two sources), Cout a positive multiple of 8;

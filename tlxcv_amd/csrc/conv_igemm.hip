@@ -532,6 +532,17 @@ constexpr CandInfo kCands[NC] = {
     {"pp10", 256, 128, 1.25f, 144 * 1024, 1, F_PP},              // gemm_pp.hip (3x3 convs with 128 output channels)
     {"w4_11", 256, 256, 0.f, 128 * 1024, 1, F_W4},               // gemm_w4.hip: persistent, four waves with 128 x 128 wave tiles (pure GEMM rows)
 };
+// Shape efficiency of gemm256_6's tile on tlxmi_conv1x1_proj's operands (two A sources, no residual; launch_gemm256_dual), on the
+// scale of pp7's 1.40 and pp9's 1.25 above.  Two four-wave workgroups per CU hide the per-tile costs (first DMA, epilogue, store
+// drain, turnover) that one eight-wave workgroup leaves exposed, and pay more LDS fill per MFMA on the narrower tile: the form gains
+// on a short K loop and loses on a long one.  Measured at the three ResNet-50 transitions, half batch, against pp7 on the same operands
+// (profiles/proj_two_wg/standin_gemm.txt): 1.51 at 6 K tiles, 1.24 at 12, 1.14 at 24 — 0.97 + 3.24 / ktiles to +-0.04,
+// level with pp7 between 7 and 8 K tiles; outside the measured 6 ... 24 K tiles the nearest measured end stands.  TLXMI_PROJ_EFF_B
+// (tuning flavour): the second constant in thousandths, for A/B runs that move the crossover (0: never this form).
+static float proj_two_wg_eff(int ktiles) {
+    const int kt = ktiles < 6 ? 6 : ktiles > 24 ? 24 : ktiles;
+    return 0.97f + 1e-3f * (float)tune_int("TLXMI_PROJ_EFF_B", 3240) / (float)kt;
+}
 // resident blocks per CU for a candidate: LDS bound (160 KiB) and the register cap; 0 = does not fit
 static int blocks_per_cu(const CandInfo& k, int ktiles) {
     size_t lds = (size_t)k.lds;
@@ -1406,19 +1417,30 @@ extern "C" int tlxmi_conv1x1_proj(const tlxmi_proj_desc* d, const void* x, const
     g.x2 = (const char*)x2; g.x2_ld = d->x2_ld;
     g.x2_bytes = (unsigned)((long long)d->N * d->H2 * d->W2 * d->x2_ld * 2);
     g.dH2 = d->H2; g.dW2 = d->W2; g.dWo = d->Wo; g.dHoWo = d->Ho * d->Wo; g.ds = d->stride;
-    // Tile height by the dispatcher's price (tile_price with the efficiencies of pp7 and pp9): rounds of one workgroup per CU on the CUs
-    // this launch is planned for, times the fill of the last row tile (the column fill is the same for both heights)
+    // Form by the dispatcher's price (tile_price): pp7's and pp9's tiles on gemm_pp.hip's DUAL instances, one workgroup per CU, or
+    // gemm256_6's tile on gemm256.hip's, two per CU — rounds on the CUs this launch is planned for, times the fill of the partial tiles.
+    // The gemm_pp forms carry their candidates' efficiencies; the two-workgroup form carries proj_two_wg_eff, measured on this operand
+    // shape as a function of the K tiles.
     const int cus = plan_cus(d->flags);
-    const long nt = (d->Cout + 255) / 256;
-    auto price = [&](const CandInfo& k) {
-        const long mt = (long)((rows + k.bm - 1) / k.bm);
-        return tile_price(mt * nt, cus, 0.f, tile_fill((float)rows, mt, k.bm, 1), k.eff);
+    auto price = [&](const CandInfo& k, float eff) {
+        const long tiles = (long)((rows + k.bm - 1) / k.bm) * ((d->Cout + k.bn - 1) / k.bn);
+        return tile_price(tiles, (long)cus * blocks_per_cu(k, g.ksteps), 0.f, tile_fill((float)rows * d->Cout, tiles, k.bm, k.bn), eff);
     };
-    // TLXMI_PROJ_TILE (tuning flavour): 1 = 256 x 256 tiles, 2 = 128 x 256 (the tests run either form at sizes the price would not pick it)
+    // TLXMI_PROJ_TILE (tuning flavour): 1 = 256 x 256 tiles, 2 = 128 x 256, 3 = 256 x 128 on two workgroups per CU (the tests run every
+    // form at sizes the price would not pick it)
     const long knob = tune_int("TLXMI_PROJ_TILE", 0);
-    const bool half_height = knob == 1 ? false : knob == 2 ? true : price(kCands[PP9]) > price(kCands[PP7]);
-    trace_launched(half_height ? "pp_dual128" : "pp_dual256", g.M, g.Cout);
-    if (int rc = launch_gemm_pp_dual(g, half_height, as_stream(stream))) return rc;
+    int form = (int)knob;
+    if (form < 1 || form > 3) {
+        const float p7 = price(kCands[PP7], kCands[PP7].eff), p9 = price(kCands[PP9], kCands[PP9].eff), p6 = price(kCands[GEMM256_6], proj_two_wg_eff(g.ksteps));
+        form = p6 > p7 && p6 > p9 ? 3 : p9 > p7 ? 2 : 1;
+    }
+    if (form == 3) {
+        trace_launched("g256_dual", g.M, g.Cout);
+        if (int rc = launch_gemm256_dual(g, as_stream(stream))) return rc;
+    } else {
+        trace_launched(form == 2 ? "pp_dual128" : "pp_dual256", g.M, g.Cout);
+        if (int rc = launch_gemm_pp_dual(g, form == 2, as_stream(stream))) return rc;
+    }
     return check_launch("conv1x1_proj");
 }
 

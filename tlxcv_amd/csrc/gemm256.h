@@ -47,7 +47,7 @@ struct Gemm256Args {
     // gemm_pp.hip CONV mode — dilation: tap (r, s) reads input pixel (hi0 + r * cdh, wi0 + s * cdw).  Read only by the dilated
     // instances (launch_gemm_pp* pick them when cdh | cdw != 1); kept last so the other fields keep their kernel-argument offsets.
     int cdh = 1, cdw = 1;
-    // gemm_pp.hip DUAL instances (launch_gemm_pp_dual) — a second A operand: K tiles [k1_tiles, k1_tiles + k2_tiles) are rows of x2, an
+    // gemm_pp.hip DUAL instances (launch_gemm_pp_dual) and gemm256.hip's (launch_gemm256_dual) — a second A operand: K tiles [k1_tiles, k1_tiles + k2_tiles) are rows of x2, an
     // NHWC map of dH2 x dW2 pixels (pitch x2_ld, x2_bytes in all) read at pixel (ho * ds, wo * ds) for output row (n, ho, wo) of a
     // dHoWo = Ho * dWo pixel output image.  Read by those instances only; last, so the fields above keep their kernel-argument offsets.
     const char* x2 = nullptr;
@@ -57,6 +57,7 @@ struct Gemm256Args {
 };
 
 int launch_gemm256(int dtype, int variant, const Gemm256Args& a, hipStream_t st);
+int launch_gemm256_dual(const Gemm256Args& a, hipStream_t st);   // fp16, 256 x 128 tiles, two A operands (a.x2); a.ksteps as launch_gemm_pp_dual
 // gemm_pp.hip: 256 x 256 tile, two wave groups in antiphase; a.ksteps = packed pitch / 128
 int launch_gemm_pp(int dtype, const Gemm256Args& a, hipStream_t st);
 int launch_gemm_pp128(int dtype, const Gemm256Args& a, hipStream_t st);   // 128 x 256 tiles (tails)

@@ -23,8 +23,14 @@ namespace tlxmi {
 // BN = 256 with WGN = 4 (8 waves, ring of 4, one workgroup per CU) or BN = 128 with WGN = 2 (4 waves, ring
 // of 3 x 24 KiB, two independent workgroups per CU: their barriers drift apart and one's epilogue overlaps
 // the other's MFMAs).
-template <typename T, int BN, int WGN, int NSLOT>
+// DUAL (fp16, BN = 128 only; launch_gemm256_dual): a second A operand, as gemm_pp.hip's DUAL instances address it.  K steps
+// [0, 2 * a.k1_tiles) are rows of x as above; steps [2 * a.k1_tiles, 2 * (a.k1_tiles + a.k2_tiles)) are rows of a.x2, an NHWC map of
+// a.dH2 x a.dW2 pixels of pitch a.x2_ld read at pixel (ho * a.ds, wo * a.ds) for output row (n, ho, wo).  Both K extents are whole
+// 128-byte tiles, so a 64-byte step never straddles the sources; the filter rows run on over K1 + K2.  Every stage() issues the
+// same DPS pieces from either source, so the counted vmcnt waits below hold unchanged.
+template <typename T, int BN, int WGN, int NSLOT, bool DUAL = false>
 __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args a) {
+    static_assert(!DUAL || (sizeof(T) == 2 && BN == 128 && WGN == 2 && NSLOT == 3), "DUAL: the fp16 two-workgroup instance only");
     constexpr int ES = (int)sizeof(T);
     constexpr int BM = 256, NW = 2 * WGN;
     constexpr int WM = 128, WN = 64, PI = WM / 16, CI = WN / 16;
@@ -70,12 +76,39 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
         const int n = (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3);
         wo[i] = (bn0 + n) * a.Kp_bytes;
     }
+    // DUAL: this lane's rows in x2 (rows past M take BUF_OOB; a live row's pixel lies inside x2, its byte offset below a.x2_bytes < 2^31)
+    const __amdgpu_buffer_rsrc_t x2srd = DUAL ? buf_srd(a.x2, a.x2_bytes) : xsrd;
+    int xo2[XPW];
+    if constexpr (DUAL) {
+#pragma unroll
+        for (int i = 0; i < XPW; ++i) {
+            const int m = bm0 + 16 * (wid + NW * i) + lr;
+            const int mm = m < a.M ? m : 0;
+            const int n = mm / a.dHoWo, rem = mm - n * a.dHoWo;
+            const int ho = rem / a.dWo, wo_ = rem - ho * a.dWo;
+            xo2[i] = m < a.M ? ((n * a.dH2 + ho * a.ds) * a.dW2 + wo_ * a.ds) * a.x2_ld * ES : BUF_OOB;
+        }
+    }
     int q = lchunk;   // chunk index along K of the next step to stage
+    int sk = 0;       // DUAL: that step's number (wave-uniform)
     auto stage = [&](int slot) {
         char* b = smem + slot * STEP;
-        const int d = q < a.kchunks ? q * 16 : BUF_OOB;
+        if constexpr (DUAL) {
+            const int k1s = 2 * a.k1_tiles;
+            if (sk < k1s) {
 #pragma unroll
-        for (int i = 0; i < XPW; ++i) buf_dma16(xsrd, b + (wid + NW * i) * 1024, xo[i] + d);
+                for (int i = 0; i < XPW; ++i) buf_dma16(xsrd, b + (wid + NW * i) * 1024, xo[i] + q * 16);
+            } else {
+                const int d = sk < k1s + 2 * a.k2_tiles ? (q - 4 * k1s) * 16 : BUF_OOB;
+#pragma unroll
+                for (int i = 0; i < XPW; ++i) buf_dma16(x2srd, b + (wid + NW * i) * 1024, xo2[i] + d);
+            }
+            ++sk;
+        } else {
+            const int d = q < a.kchunks ? q * 16 : BUF_OOB;
+#pragma unroll
+            for (int i = 0; i < XPW; ++i) buf_dma16(xsrd, b + (wid + NW * i) * 1024, xo[i] + d);
+        }
 #pragma unroll
         for (int i = 0; i < WPW; ++i) buf_dma16(wsrd, b + BM * 64 + (wid + NW * i) * 1024, wo[i] + q * 16);
         q += 4;
@@ -219,7 +252,7 @@ __global__ __launch_bounds__(WGN * 128, 2) void gemm256_kernel(const Gemm256Args
 // Called by conv_igemm.hip's dispatcher.  Preconditions (checked there): 1x1, stride 1, no padding, dense
 // batch strides, Cout % 8 == 0, 16-byte aligned y / res rows, every tensor < 2 GiB.  variant 0: 256 x 256,
 // variant 1: 256 x 128.
-template <typename T, int BN, int WGN, int NSLOT> static int launch_v(const Gemm256Args& a0, hipStream_t st) {
+template <typename T, int BN, int WGN, int NSLOT, bool DUAL = false> static int launch_v(const Gemm256Args& a0, hipStream_t st) {
     Gemm256Args a = a0;
     a.debug = (int)tune_int("TLXMI_DEBUG", 0);     // A/B bits: tuning flavour only
     a.mtiles = (a.M + 255) / 256;
@@ -230,7 +263,7 @@ template <typename T, int BN, int WGN, int NSLOT> static int launch_v(const Gemm
         a.gn = (int)(gn < 1 ? 1 : (gn > a.ntiles ? a.ntiles : gn));
     }
     const size_t lds = (size_t)NSLOT * (256 + BN) * 64 + 2 * BN * sizeof(float);
-    const void* fn = reinterpret_cast<const void*>(&gemm256_kernel<T, BN, WGN, NSLOT>);
+    const void* fn = reinterpret_cast<const void*>(&gemm256_kernel<T, BN, WGN, NSLOT, DUAL>);
     if (int rc = raise_lds_limit(fn, (int)lds, "gemm256")) return rc;
     void* args[] = {&a};
     hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(a.mtiles * a.ntiles)), dim3(WGN * 128), args, lds, st);
@@ -245,6 +278,18 @@ int launch_gemm256(int dtype, int variant, const Gemm256Args& a, hipStream_t st)
     }
     if (dtype == TLXMI_F16) return launch_v<half_t, 128, 2, 3>(a, st);
     return launch_v<float, 128, 2, 3>(a, st);
+}
+
+// The DUAL instance (fp16, 256 x 128 tiles, two workgroups per CU).  Same operands and preconditions as launch_gemm_pp_dual (checked by
+// tlxmi_conv1x1_proj, conv_igemm.hip): a.ksteps = k1_tiles + k2_tiles 128-byte K tiles = a.Kp_bytes / 128; this kernel walks them as
+// 64-byte steps.
+int launch_gemm256_dual(const Gemm256Args& a0, hipStream_t st) {
+    if (a0.conv || a0.kslices > 1 || a0.rowstats || a0.stats_out || a0.res || !a0.x2 || a0.k1_tiles < 1 || a0.k2_tiles < 1 || a0.ksteps != a0.k1_tiles + a0.k2_tiles ||
+        a0.Kp_bytes != a0.ksteps * 128)
+        return fail(TLXMI_ERR_UNSUPPORTED, "gemm256: the two-operand form takes plain rows plus one gathered operand (no residual, no split K, no LayerNorm fold)");
+    Gemm256Args a = a0;
+    a.ksteps = a.Kp_bytes / 64;
+    return launch_v<half_t, 128, 2, 3, true>(a, st);
 }
 
 }  // namespace tlxmi

@@ -19,7 +19,7 @@ X, X2, W, RES, Y, PART = (C.c_void_p(i << 32) for i in range(1, 7))      # 4 GiB
 SC, SH = C.c_void_p(7 << 32), C.c_void_p((7 << 32) + 65536)
 HALF, FULL, BCAST, POOL = _lib.PLAN_SHARED_HALF, _lib.PLAN_SHARED_FULL, 2, _lib.EPI_MAXPOOL_3S2P1
 KNOBS = ("TLXMI_TAIL", "TLXMI_PP128", "TLXMI_WREG", "TLXMI_HALO", "TLXMI_PP_DIL", "TLXMI_PLAN_CUS", "TLXMI_TILE", "TLXMI_FORCE", "TLXMI_GCONV",
-         "TLXMI_PROJ_TILE")
+         "TLXMI_PROJ_TILE", "TLXMI_PROJ_EFF_B")
 
 
 class Sweep:
@@ -125,7 +125,7 @@ def main():
                                         s.conv("grid", dt, N, hw, hw, Cin, Cout, k=k, stride=stride, pad=pad, res=res, flags=flags)
     settings = [{}] + [{"TLXMI_TAIL": v} for v in "012"] + [{"TLXMI_PP128": "0"}] + [{"TLXMI_WREG": v} for v in "023"] + [
         {"TLXMI_HALO": "0"}, {"TLXMI_PP_DIL": "0"}, {"TLXMI_PLAN_CUS": "128"}, {"TLXMI_PLAN_CUS": "304"}, {"TLXMI_GCONV": "0"},
-        {"TLXMI_PROJ_TILE": "1"}, {"TLXMI_PROJ_TILE": "2"}, {"TLXMI_FORCE": "50176:768:2304:1:1=9,200704:1152:128:3:1=2"}] + [
+        {"TLXMI_PROJ_TILE": "1"}, {"TLXMI_PROJ_TILE": "2"}, {"TLXMI_PROJ_TILE": "3"}, {"TLXMI_PROJ_EFF_B": "0"}, {"TLXMI_FORCE": "50176:768:2304:1:1=9,200704:1152:128:3:1=2"}] + [
         {"TLXMI_TILE": str(v)} for v in range(12)]
     for env in settings:
         os.environ.update(env)
