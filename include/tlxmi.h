@@ -768,6 +768,32 @@ int tlxmi_link_conv2d(const tlxmi_link_conv_desc* d, const void* x, const void* 
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SE-gated 1x1 projection: the tail of ReXNet's LinearBottleneck (classification/rexnet.py:61-64, :84-95) in one launch — the
+ * Squeeze-Excitation gate `x * y`, nn.ReLU6, the projecting 1x1 conv + BatchNorm and the PARTIAL shortcut `out[:, 0:in_channels] += x`.
+ * fp16, fp32 accumulation on MFMA.
+ *     a[m][k] = fp16( pre( x[m*x_ld + k] * gate[(m / HW)*gate_ld + k] ) )    k < K   (fp32 product, rounded once)
+ *     y[m*y_ld + n] = fp16( (sum_k a[m][k] * W[n][k]) * scale[n] + shift[n] + (n < res_c ? res[m*res_ld + n] : 0) )   n < Cout, m < rows
+ * rows = N_img * HW pixels; a row tile may span several images (the gate row is chosen per row).  x is a channel PREFIX of a wider
+ * buffer (x_ld >= K): columns k >= K are never multiplied, whatever they hold (NaN included); the same holds for gate (fp16
+ * [N_img][gate_ld]; gate NULL and gate_ld 0: no gate).  pre_act: TLXMI_ACT_RELU6 or TLXMI_ACT_NONE.  w_packed: tlxmi_pack_filter of
+ * the [Cout][K][1][1] filter; scale / shift: fp32 [Cout] or NULL (1 / 0).  res: rows of pitch res_ld of which the first res_c
+ * channels are added — res_c ANY integer 0 .. Cout, masked per element: what res holds at and behind column res_c reaches no output
+ * (NaN included); res_c 0: res and res_ld are ignored.  y is a column slice of a wider buffer (y_ld >= Cout); nothing outside
+ * rows x Cout is written.  y aliases no input.  One writer per element, fixed summation order, no atomics.
+ * tlxmi_gated_conv1x1_supported() is pure host code and answers 1 exactly for: fp16; HW >= 1 and rows a positive multiple of HW; K,
+ * Cout, x_ld, y_ld positive multiples of 8 with x_ld >= K and y_ld >= Cout; gate_ld 0 or a multiple of 8 >= K; 0 <= res_c <= Cout and,
+ * for res_c > 0, res_ld a multiple of 8 >= res_c; pre_act none or ReLU6; rows * pitch * 2 for x, y and res, the gate and the packed
+ * filter all below 2^31 bytes (32-bit byte offsets).  1 means the call is taken, given x, gate, w_packed, res and y 16-byte aligned
+ * (TLXMI_ERR_ALIGNMENT otherwise) and gate / res given as gate_ld / res_c say (TLXMI_ERR_BAD_ARG otherwise); anything the predicate
+ * refuses returns TLXMI_ERR_UNSUPPORTED (run tlxmi_scale_channels, tlxmi_affine_act and tlxmi_conv2d instead).
+ * ---------------------------------------------------------------------------------------- */
+int tlxmi_gated_conv1x1_supported(int dtype, int64_t rows, int HW, int K, int Cout, int x_ld, int gate_ld, int y_ld, int res_ld, int res_c,
+                                  int pre_act);
+int tlxmi_gated_conv1x1(int dtype, int64_t rows, int HW, int K, int Cout, int x_ld, int gate_ld, int y_ld, int res_ld, int res_c,
+                        const void* x, const void* gate, int pre_act, const void* w_packed, const float* scale, const float* shift,
+                        const void* res, void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling.  nn.MaxPool2d(3,2,padding=1) resnet.py:213-218 (padding value -inf);
  * nn.AdaptiveAvgPool2d((1,1)) resnet.py:228-231 / mobilenetv1.py:246; AdaptiveAvgPool1d(1) over
  * tokens swin_transformer.py:609.

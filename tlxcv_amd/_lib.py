@@ -212,6 +212,7 @@ PROTOTYPES = {
     "tlxmi_fire_module": [C.POINTER(FireModuleDesc), _vp, _vp, _vp, _vp],
     "tlxmi_dual_path_conv1x1": [_i, _l, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "tlxmi_link_conv2d": [C.POINTER(LinkConvDesc), _vp, _vp, _vp, _vp, _vp, _vp],
+    "tlxmi_gated_conv1x1": [_i, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _SPECIAL = {
     "tlxmi_version": ([], C.c_int),
@@ -257,6 +258,7 @@ _SPECIAL = {
     "tlxmi_fire_module_param_bytes": ([_i, _i, _i, _i], C.c_size_t),
     "tlxmi_dual_path_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i], C.c_int),
     "tlxmi_link_conv2d_supported": ([C.POINTER(LinkConvDesc)], C.c_int),
+    "tlxmi_gated_conv1x1_supported": ([_i, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i], C.c_int),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(_SPECIAL))
 

@@ -114,6 +114,11 @@ _options = {"splitk": True,       # classifier heads: K slices side by side (tlx
                                   # keeps: engine.LINK_CONV_WINS): the conv of a HarDBlock layer reads its linked layers as column
                                   # slices of the block buffer IN PLACE on tlxmi_link_conv2d: ONE launch, no concat pass; elsewhere and off = one
                                   # tlxmi_copy_channels a link into a scratch map, then tlxmi_conv2d (the A/B and the tests' other arm)
+            "gated_conv": True,   # ReXNet's projecting 1x1 convs (fp16, widths and pitches multiples of 8; the shapes the measured table keeps:
+                                  # engine.GATED_CONV_WINS): SE gate -> ReLU6 -> 1x1 conv + BN -> shortcut onto the first res_c channels
+                                  # on tlxmi_gated_conv1x1: ONE launch, the gated map only on its way into the MFMA; elsewhere and off =
+                                  # tlxmi_scale_channels -> tlxmi_affine_act -> tlxmi_conv2d with the shortcut as its residual (the A/B and the
+                                  # tests' other arm)
             "tail_splitk": False} # Linear layers: the rows of a short last round of 256 x 256 tiles on K slices (_linear_tail): built,
                                   # parity-green, measured a LOSS on the ViT-B/16 forward (10.63 -> 11.61 ms for every K >= 768,
                                   # 10.91 for fc2 only: two more launches + the fp32 partial planes cost more than the idle round)
@@ -2391,6 +2396,137 @@ def link_conv2d(buf, segments, params, act, out, out_ld=None, fused=None):
         conv2d(gathered, p.pk, 1, p.R // 2, 1, p.scale, p.shift, act=act, out=out, out_ld=out_ld)
     _timed(launch, lambda: ((M * (p.K + p.Cout) + p.Cout * p.K * p.R * p.R) * es, 2 * M * p.Cout * p.K * p.R * p.R,
                             (N, H, W, p.K, p.Cout, p.R, "link_conv" if fused else "copy-conv")))      # the chain is one entry
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# ReXNet's gated projection: SE gate -> ReLU6 -> 1x1 conv + BN -> shortcut onto a channel prefix
+# ---------------------------------------------------------------------------------------------
+def _gated_conv_desc(x, gate, pk, res, res_c, pre_act, out_ld):
+    """The positional geometry of tlxmi_gated_conv1x1 / _supported: (dtype, rows, HW, K, Cout, x_ld, gate_ld, y_ld, res_ld, res_c)."""
+    N, H, W, ld = x.shape
+    return (dt_code(x.dtype), N * H * W, H * W, pk.Cin, pk.Cout, ld, 0 if gate is None else gate.shape[-1], int(out_ld),
+            res.shape[-1] if res_c else 0, int(res_c))
+
+
+def gated_conv1x1_takes(x, gate, pk, res=None, res_c=0, pre_act=ACT_RELU6, out_ld=None):
+    """Whether the library's tlxmi_gated_conv1x1 takes these operands (fp16, the widths and pitches of include/tlxmi.h): what
+    fused=True needs."""
+    if x.dtype != torch.float16 or pk.dtype != torch.float16 or pk.R != 1 or pk.S != 1 or x.dim() != 4:
+        return False
+    d = _gated_conv_desc(x, gate, pk, res, res_c, pre_act, pk.Cout if out_ld is None else out_ld)
+    return bool(_lib.load().tlxmi_gated_conv1x1_supported(*d, int(pre_act)))
+
+
+# (pixels per image H * W, K, Cout, res_c, gated) — K and Cout as the kernel sees them, padded to 8; res_c the true shortcut width — of
+# the projections where the one launch was measured FASTER than the layered arm on every alternation at batch 256 on one MI355X
+# (tools/rexnet_bench.py, profiles/rexnet/, DESIGN 4.36): gated_conv1x1() keeps the launch there and runs the layers everywhere else,
+# unmeasured shapes included, by default.
+# MEASURED over the 32 distinct projections of ReXNet-1.0 and ReXNet-2.0 at 224 x 224: the launch wins ALL of them, at 0.26 - 0.84 of the
+# layered arm's time (0.26 - 0.59 at 112 x 112 .. 14 x 14, 0.60 - 0.84 at 7 x 7, where K reaches 2088 and the A tile is re-read by up to six
+# column tiles); both arms give identical bits at every shape.  Shapes other than those 32 (ReXNet-1.3 / 1.5 / 3.0, other input sizes) are
+# unmeasured and run layer by layer.
+GATED_CONV_WINS = frozenset({
+    (12544, 32, 16, 0, False), (3136, 96, 32, 0, False), (3136, 168, 40, 27, False), (784, 232, 56, 0, True), (784, 304, 64, 50, True),
+    (196, 368, 72, 0, True), (196, 432, 88, 72, True), (196, 504, 96, 84, True), (196, 576, 112, 95, True), (196, 640, 120, 106, True),
+    (196, 704, 128, 117, True), (49, 768, 144, 0, True), (49, 840, 152, 140, True), (49, 912, 168, 151, True), (49, 976, 176, 162, True),
+    (49, 1048, 192, 174, True),
+    (12544, 64, 32, 0, False), (3136, 192, 56, 0, False), (3136, 328, 80, 54, False), (784, 464, 104, 0, True), (784, 600, 128, 100, True),
+    (196, 736, 144, 0, True), (196, 864, 168, 144, True), (196, 1008, 192, 167, True), (196, 1144, 216, 190, True), (196, 1272, 240, 212, True),
+    (196, 1408, 264, 234, True), (49, 1544, 280, 0, True), (49, 1680, 304, 280, True), (49, 1816, 328, 302, True), (49, 1944, 352, 324, True),
+    (49, 2088, 376, 347, True)})
+
+
+def _gated_conv_routed(pixels, pk, res_c, gated):
+    return (pixels, pk.Cin, pk.Cout, int(res_c), bool(gated)) in GATED_CONV_WINS
+
+
+def gated_conv1x1_supported(x, gate, pk, res=None, res_c=0, pre_act=ACT_RELU6, out_ld=None):
+    """Whether gated_conv1x1() runs tlxmi_gated_conv1x1 on these operands by default: the "gated_conv" option on, the shape in the
+    measured table and the library's predicate."""
+    return bool(_options["gated_conv"] and _gated_conv_routed(x.shape[1] * x.shape[2], pk, res_c, gate is not None)
+                and gated_conv1x1_takes(x, gate, pk, res, res_c, pre_act, out_ld))
+
+
+def gated_conv1x1(x, gate, pk, scale, shift, res=None, res_c=0, pre_act=ACT_RELU6, out=None, out_ld=None, fused=None):
+    """The tail of ReXNet's LinearBottleneck (rexnet.py:61-64, :84-95) on an NHWC map x (N, H, W, x_ld) whose first K = pk.Cin channels
+    are the operand:
+        y[..., n] = conv1x1(pre_act(x[..., :K] * gate[image, :K]))[n] * scale[n] + shift[n] + (res[..., n] if n < res_c else 0)
+    gate: (N, gate_ld >= K) in x's dtype, or None (no gate); pre_act: ACT_RELU6 or ACT_NONE; pk: the PackedFilter of the (Cout, K, 1, 1)
+    filter; scale / shift: fp32 [Cout]; res: a dense NHWC map over the same pixels whose first res_c channels are added — res_c any
+    integer 0 .. Cout; what res holds behind them is never used.  -> y (N, H, W, Cout), or written into `out` (a dense map whose last
+    axis is the pitch; with out_ld, a column slice of a wider buffer at that pitch); nothing behind Cout is written.
+    One launch (tlxmi_gated_conv1x1) when the "gated_conv" option is on, the precision is fp16, the measured table keeps the shape and
+    the library takes it; otherwise — and always for fp32: the parity reference — tlxmi_scale_channels -> tlxmi_affine_act (the ReLU6)
+    -> tlxmi_conv2d with the shortcut as its residual: res itself where res_c == Cout, else a zero-filled Cout-wide copy of its first
+    res_c columns (tlxmi_copy_channels; a dense copy where res_c is no whole 16-byte chunk).  fused=True / False forces one form
+    (tests, tools/); True raises where the launch is not supported."""
+    need_gpu(x, "input")
+    if x.dim() != 4:
+        raise RuntimeError(f"gated_conv1x1: x must be an NHWC map, got {tuple(x.shape)}")
+    N, H, W, ld = x.shape
+    K, Cout, v = pk.Cin, pk.Cout, vec(x.dtype)
+    res_c = int(res_c)
+    if pk.R != 1 or pk.S != 1 or x.dtype != pk.dtype or ld < K or not x.is_contiguous() or K % v or ld % v or Cout % v:
+        raise RuntimeError(f"gated_conv1x1: x must be a dense NHWC map of the filter's dtype with at least K = {K} channels, K, Cout = {Cout} "
+                           f"and the pitch multiples of {v}, and the filter 1x1; got {tuple(x.shape)} {x.dtype} for a {pk.R}x{pk.S} filter")
+    if gate is not None and (gate.dtype != x.dtype or gate.dim() != 2 or gate.shape[0] != N or gate.shape[1] < K or gate.shape[1] % v
+                             or not gate.is_contiguous()):
+        raise RuntimeError(f"gated_conv1x1: gate must be a dense ({N}, >= {K}) matrix of x's dtype at a pitch that is a multiple of {v}, "
+                           f"got {tuple(gate.shape)} {gate.dtype}")
+    if pre_act not in (ACT_NONE, ACT_RELU6):
+        raise RuntimeError(f"gated_conv1x1: pre_act must be ACT_NONE or ACT_RELU6, got {pre_act}")
+    if not 0 <= res_c <= Cout or (res_c and (res is None or res.dtype != x.dtype or tuple(res.shape[:3]) != (N, H, W) or res.shape[-1] < res_c
+                                             or res.shape[-1] % v or not res.is_contiguous())):
+        raise RuntimeError(f"gated_conv1x1: res_c = {res_c} must lie in 0 .. Cout = {Cout} and res be a dense ({N}, {H}, {W}, >= res_c) map of "
+                           f"x's dtype at a pitch that is a multiple of {v}; got {None if res is None else tuple(res.shape)}")
+    if out is None or out_ld is None:
+        out, out_ld = _out_map("gated_conv1x1", out, N, H, W, Cout, x.dtype, x.device, Cout, multiple=v,
+                               what=f"a dense ({N}, {H}, {W}, >= {Cout}) map of x's dtype whose pitch is a multiple of {v}")
+    else:
+        out_ld = int(out_ld)
+        if out.dtype != x.dtype or tuple(out.shape[:3]) != (N, H, W) or out.shape[-1] < Cout or out_ld < Cout or out_ld % v:
+            raise RuntimeError(f"gated_conv1x1: out must be a column slice of at least {Cout} channels over the same pixels at a pitch that is "
+                               f"a multiple of {v}, got {tuple(out.shape)} at pitch {out_ld}")
+    takes = lambda: gated_conv1x1_takes(x, gate, pk, res, res_c, pre_act, out_ld)      # noqa: E731
+    # the option and the table first: the library's predicate is asked only where they keep the launch
+    fused = _use_fused("gated_conv1x1", fused, takes,
+                       lambda: _options["gated_conv"] and _gated_conv_routed(H * W, pk, res_c, gate is not None) and takes(),
+                       lambda: f"x {tuple(x.shape)} {x.dtype}, gate {None if gate is None else tuple(gate.shape)}, K {K}, Cout {Cout}, "
+                               f"res_c {res_c}, pre_act {pre_act}, out at pitch {out_ld}")
+    es = x.element_size()
+    M = N * H * W
+    if _sizing():
+        _note_act(x.numel() * es, M * out_ld * es, res.numel() * es if res_c else 0)
+
+    def launch():
+        if fused:
+            d = _gated_conv_desc(x, gate, pk, res, res_c, pre_act, out_ld)
+            _lib.call("tlxmi_gated_conv1x1", *d, _p(x), _p(gate), int(pre_act), _p(pk.buf), _p(scale), _p(shift), _p(res if res_c else None),
+                      _p(out), _stream())
+            return
+        dt = dt_code(x.dtype)
+        t, t_ld = x, ld
+        if gate is not None:
+            g = torch.empty((N, H, W, K), dtype=x.dtype, device=x.device)
+            _lib.call("tlxmi_scale_channels", _p(t), _p(gate), _p(g), dt, N, H * W, K, t_ld, gate.shape[-1], K, _stream())
+            t, t_ld = g, K
+        if pre_act == ACT_RELU6:
+            a = torch.empty((N, H, W, K), dtype=x.dtype, device=x.device)
+            _lib.call("tlxmi_affine_act", _p(t), None, None, None, _p(a), dt, M, K, t_ld, 0, K, ACT_RELU6, 0.0, 0, _stream())
+            t, t_ld = a, K
+        r = None
+        if res_c == Cout:
+            r = res
+        elif res_c:
+            r = torch.zeros((N, H, W, Cout), dtype=x.dtype, device=x.device)
+            if res_c % v == 0:
+                copy_channels_into(res[..., :res_c], r, 0, x_ld=res.shape[-1])
+            else:       # the shortcut ends inside a 16-byte chunk: a dense copy
+                r[..., :res_c] = res[..., :res_c]
+        conv2d(t if t_ld == K else t[..., :K], pk, 1, 0, 1, scale, shift, res=r, out=out, out_ld=out_ld, x_ld=None if t_ld == K else t_ld)
+    _timed(launch, lambda: ((M * (K + Cout + res_c) + Cout * K) * es, 2 * M * Cout * K,
+                            (N, H, W, K, Cout, "gated_conv" if fused else "gate-act-conv")))      # the chain is one entry
     return out
 
 

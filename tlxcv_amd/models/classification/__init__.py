@@ -49,3 +49,4 @@ from .squeezenet import SqueezeNet, MakeFire, MakeFireConv, squeezenet1_0, squee
 from .dpn import DPN, DualPathFactory, dpn68, dpn107  # noqa: F401
 # (the HarDNet file's ConvLayer stays in its module: GoogLeNet's owns that name here)
 from .hardnet import HarDNet, HarDBlock, DWConvLayer, CombConvLayer, hardnet39, hardnet85  # noqa: F401
+from .rexnet import ReXNetV1, LinearBottleneck, SE, rexnet_1_0, rexnet_1_3, rexnet_1_5, rexnet_2_0, rexnet_3_0  # noqa: F401
