@@ -85,7 +85,8 @@ def _check(y, ref, bound, what):
 
 
 SHAPES = ([(64, 64, 2048, d) for d in (6, 12, 18)] + [(16, 20, 2048, d) for d in (6, 12, 18)]
-          + [(33, 47, 2048, d) for d in (6, 12, 18)] + [(hw[0], hw[1], c, 1) for c in (304, 256) for hw in ((128, 128), (32, 40))])
+          + [(33, 47, 2048, d) for d in (6, 12, 18)] + [(hw[0], hw[1], c, 1) for c in (304, 256) for hw in ((128, 128), (32, 40))]
+          + [(5, 13, 72, 2)])       # the smallest with a row tail (65 / 195 rows) AND a K tail (72 = 64 + 8 channels)
 
 
 @pytest.mark.parametrize("batch", [1, 3])

@@ -1,5 +1,7 @@
 // Device-side one-liners shared by the kernels: buffer descriptors and buffer loads / stores, the LDS-DMA piece, the MFMA pair
-// of the fp16 / fp32 paths, v_fma_mix_f32, counted waits, DPP (gfx950 only).  One copy: a kernel file adds none of its own.
+// of the fp16 / fp32 paths, v_fma_mix_f32, counted waits, DPP (gfx950 only).  One copy: a kernel file adds none of its own — and
+// none of the LDS-staged GEMM tile's pieces either (tile map, piece roles, swizzle, filter perm, MFMA step): those are tile_gemm.h
+// (gated_conv.hip and link_conv.hip keep the copies they were measured with: DESIGN 4.37).
 #pragma once
 #include "common.h"
 

@@ -7,17 +7,16 @@
 // hold anything, NaN included, so a K tile that runs past K is forced to zero AFTER the affine (0 * NaN is NaN: the packed filter's zero
 // padding does not help), as are the rows past M (a zero-filled out-of-range load would become pre(pt[k])).
 //
-// 256 threads = 4 waves; a tile is 128 rows x 128 output channels (tlxmi_pack_filter pads Cout to 128), K tiles of 64 channels.
-//   B: the packed filter's 128 rows x 128 B by LDS-DMA into one of TWO buffers (row rho holds filter row perm(rho), as sepconv.hip:
-//      the epilogue lanes then own 8 consecutive channels); the piece for K tile kt + 1 is issued before the MFMAs of K tile kt;
+// On the tile of tile_gemm.h: 128 rows x 128 output channels, mma_cols<2>.
+//   B: the packed filter's 128 rows x 128 B by LDS-DMA into one of TWO buffers; the pieces for K tile kt + 1 are issued before the
+//      MFMAs of K tile kt;
 //   A: thread t owns channel chunk t & 7 (8 channels) of rows (t >> 3) + 32 i, i < 4: four 16-byte loads through a buffer descriptor
 //      (rows past M / chunks past K masked to an out-of-range offset), also fetched one K tile ahead — into registers, together with the
-//      chunk's ps / pt —, transformed once per element and written to the swizzled A tile (chunk c of row r in slot c ^ ((r >> 1) & 7));
-//   per K tile: ds_write A | wait for B, barrier | issue B and A of kt + 1 | 32 MFMA 16x16x32 per wave (wave w: filter rows 32 w .. + 31
-//   x all 128 rows) | barrier.  The closing barrier is a raw s_barrier behind lgkmcnt(0): __syncthreads() there would drain the LDS-DMA
-//   in flight (it is a pending LDS write on the vector-memory counter).
+//      chunk's ps / pt —, transformed once per element and written to the swizzled A tile;
+//   per K tile: ds_write A | wait for B, barrier | issue B and A of kt + 1 | 32 MFMAs per wave (wave w: filter rows 32 w .. + 31 x all
+//   128 rows) | tile_close_keep_dma.
 // 48 KiB of LDS and 64 accumulator registers a lane: three workgroups share a CU, whose loads overlap one another's MFMAs.
-#include "kernel_util.h"
+#include "tile_gemm.h"
 
 namespace tlxmi {
 
@@ -41,14 +40,7 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
     const int t = threadIdx.x, lane = t & 63;
     const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
 
-    // block -> tile: blocks sharing an XCD (id % 8) take consecutive tiles, the column tiles of one row tile next to each other, so
-    // the re-reads of an A tile (Cout > 128) meet in one L2
-    int tile;
-    {
-        const int nb = a.tiles, id = (int)blockIdx.x;
-        const int xcd = id & 7, qd = nb >> 3, rm = nb & 7;
-        tile = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (id >> 3);
-    }
+    const int tile = xcd_tile(a.tiles, (int)blockIdx.x);
     const int mt = tile / a.ntiles, nt = tile - mt * a.ntiles;
     const int bm0 = mt * 128;
     const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.wp, a.w_bytes), ysrd = buf_srd(a.y, a.y_bytes);
@@ -61,30 +53,15 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
         const int m = bm0 + pr + 32 * i;
         xo[i] = m < a.M ? m * a.x_ld * 2 + c * 16 : BUF_OOB;      // < 2^31: tlxmi_preact_conv1x1_supported
     }
-    char* const arow = sa + pr * 128 + ((c ^ ((pr >> 1) & 7)) << 4);      // + 32 * 128 * i: (r >> 1) & 7 is the same for all i
+    char* const arow = sa + a_slot(pr, c);      // + 32 * 128 * i: the slot is the same for all i
 
-    // ---- B loader: piece q = wid + 4 j (8 rows x 128 B, one wave instruction); lane -> row 8 q + (lane >> 3), slot lane & 7
-    int wo;
-    {
-        const int lc = (lane & 7) ^ ((4 * (wid & 1) + (lane >> 4)) & 7);
-        const int rho = 8 * wid + (lane >> 3);
-        const int n = (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3);      // perm within the 32-row group
-        wo = (nt * 128 + n) * a.Kp_bytes + lc * 16;
-    }
-    const int wstep = 32 * a.Kp_bytes;
-
-    // ---- fragments: lane (frow, fg) reads row frow of a 16-row sub-tile, 16-byte chunk 4 ks + fg
-    const int frow = lane & 15, fg = lane >> 4;
-    const int foff = frow * 128 + ((fg ^ ((frow >> 1) & 7)) << 4);     // ks = 1: foff ^ 64
-
-    f32x4 acc[2][8];   // [filter sub-tile ci: rows 32 wid + 16 ci][row sub-tile pi: rows 16 pi]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int wo = filter_dma_offset(lane, wid, nt * 128, a.Kp_bytes), wstep = filter_dma_step(a.Kp_bytes);
+    const int fg = lane >> 4, foff = frag_off(lane);
 
     u32x4 xr[4];
     f32x4 sc[2], sf[2];
+    f32x4 acc[2][8];   // [filter sub-tile ci: rows 32 wid + 16 ci][row sub-tile pi: rows 16 pi]
+    zero_acc(acc);
     auto fetch = [&](int kt) {
         const int ch0 = kt * 64 + c * 8;
         const bool cl = ch0 < a.K;
@@ -97,14 +74,8 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
         sf[0] = *reinterpret_cast<const f32x4*>(a.pt + cs);
         sf[1] = *reinterpret_cast<const f32x4*>(a.pt + cs + 4);
     };
-    auto issue_b = [&](int kt) {
-        char* const dst = sb[kt & 1];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            buf_dma16(wsrd, dst + (wid + 4 * j) * 1024, wo + j * wstep + kt * 128);
-    };
 
-    issue_b(0);
+    dma_filter<4>(wsrd, sb[0], wid, wo, wstep, 0);
     fetch(0);
     for (int kt = 0; kt < a.ktiles; ++kt) {
         // A(kt): the affine (+ ReLU), once per element, then the zeros of the chunks past K and the rows past M
@@ -127,40 +98,15 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of B(kt) landed
         __syncthreads();
         if (kt + 1 < a.ktiles) {
-            issue_b(kt + 1);      // the other buffer: its last readers (K tile kt - 1) passed the barrier that closed that tile
+            // the other buffer: its last readers (K tile kt - 1) passed the barrier that closed that tile
+            dma_filter<4>(wsrd, sb[(kt + 1) & 1], wid, wo, wstep, kt + 1);
             fetch(kt + 1);
         }
-
-        // 32 MFMAs: W rows 32 wid + 16 ci, rows 16 pi
-        {
-            const char* const bb = sb[kt & 1];
-            u32x4 wf[2][2];
-#pragma unroll
-            for (int ci = 0; ci < 2; ++ci) {
-                const char* p = bb + (2 * wid + ci) * 2048;
-                wf[ci][0] = *reinterpret_cast<const u32x4*>(p + foff);
-                wf[ci][1] = *reinterpret_cast<const u32x4*>(p + (foff ^ 64));
-            }
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int pi = 0; pi < 8; ++pi) {
-                const char* p = sa + pi * 2048;
-                const u32x4 x0 = *reinterpret_cast<const u32x4*>(p + foff), x1 = *reinterpret_cast<const u32x4*>(p + (foff ^ 64));
-#pragma unroll
-                for (int ci = 0; ci < 2; ++ci) {
-                    acc[ci][pi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, wf[ci][0]), __builtin_bit_cast(half8v, x0), acc[ci][pi], 0, 0, 0);
-                    acc[ci][pi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, wf[ci][1]), __builtin_bit_cast(half8v, x1), acc[ci][pi], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
-        // every fragment read of this tile has returned before the A tile is rewritten; B(kt + 1) stays in flight
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        mma_cols<2>(acc, sb[kt & 1] + 2 * wid * 2048, sa, foff);
+        tile_close_keep_dma();      // before the A tile is rewritten; B(kt + 1) stays in flight
     }
 
-    // ---- epilogue: lane (fg, px) owns channels 128 nt + 32 wid + 8 fg .. +7 (sub-tiles ci = 0, 1: 4 each) of row 16 pi + px
+    // ---- epilogue: lane (fg, px) owns channels 128 nt + 32 wid + 8 fg .. +7 of row 16 pi + px
     const int px = lane & 15;
     const int ch0 = nt * 128 + 32 * wid + 8 * fg;
     const bool chl = ch0 < a.Cout;
@@ -175,9 +121,9 @@ __global__ __launch_bounds__(256, 3) void preact_gemm_kernel(const PreArgs a) {
         const int m = bm0 + 16 * pi + px;
         half8v hv;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v0 = acc[0][pi][e] * s2[e] + t2[e];
-            float v1 = acc[1][pi][e] * s2[4 + e] + t2[4 + e];
+        for (int e = 0; e < 4; ++e) {      // (the two sub-tiles side by side: the order the accumulators are read in)
+            float v0 = owned8(acc[0][pi], acc[1][pi], e) * s2[e] + t2[e];
+            float v1 = owned8(acc[0][pi], acc[1][pi], 4 + e) * s2[4 + e] + t2[4 + e];
             if (RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
             hv[e] = (half_t)v0;
             hv[4 + e] = (half_t)v1;
@@ -193,9 +139,8 @@ static bool pre_ok(int dtype, int64_t rows, int K, int Cout, int x_ld, int y_ld,
     if (K < 8 || K % 8 || Cout < 8 || Cout % 8 || x_ld < K || x_ld % 8 || y_ld < Cout || y_ld % 8) return false;
     if (pre_act != TLXMI_ACT_NONE && pre_act != TLXMI_ACT_RELU) return false;
     if (act != TLXMI_ACT_NONE && act != TLXMI_ACT_RELU) return false;
-    if (rows >= (1ll << 31) / 16) return false;     // (x_ld, y_ld >= 8)
-    if (rows * x_ld * 2 >= (1ll << 31) || rows * y_ld * 2 >= (1ll << 31)) return false;
-    return true;
+    // (no packed_filter_under_2gib test here, unlike the other predicates: kept as it was)
+    return rows_addressable(rows) && map_under_2gib(rows, x_ld) && map_under_2gib(rows, y_ld);
 }
 
 }  // namespace tlxmi
@@ -216,15 +161,12 @@ extern "C" int tlxmi_preact_conv1x1(int dtype, int64_t rows, int K, int Cout, in
                   dtype, (long long)rows, K, Cout, x_ld, y_ld, pre_act, act);
     TLXMI_REQUIRE(aligned16(x) && aligned16(pre_scale) && aligned16(pre_shift) && aligned16(w_packed) && aligned16(y), TLXMI_ERR_ALIGNMENT,
                   "preact_conv1x1: x, pre_scale, pre_shift, w_packed and y must be 16-byte aligned");
+    const PackedFilter pf(K, Cout, 128);
     PreArgs a;
     a.x = (const char*)x; a.ps = pre_scale; a.pt = pre_shift; a.wp = (const char*)w_packed; a.s2 = scale; a.t2 = shift; a.y = (char*)y;
     a.K = K; a.Cout = Cout; a.x_ld = x_ld; a.y_ld = y_ld; a.M = (int)rows;
-    a.Kp_bytes = (K * 2 + 127) / 128 * 128;        // tlxmi_pack_filter's row pitch for a 1 x 1 filter
-    a.ktiles = a.Kp_bytes / 128;
-    a.ntiles = (Cout + 127) / 128;
-    a.tiles = (int)((rows + 127) / 128) * a.ntiles;
+    a.Kp_bytes = pf.Kp_bytes; a.ktiles = pf.ktiles; a.ntiles = pf.ntiles; a.tiles = pf.tiles(rows); a.w_bytes = pf.w_bytes;
     a.x_bytes = (unsigned)(rows * x_ld * 2);
-    a.w_bytes = (unsigned)(a.ntiles * 128) * (unsigned)a.Kp_bytes;
     a.y_bytes = (unsigned)(((rows - 1) * y_ld + Cout) * 2);
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)a.tiles), block(256);

@@ -5,21 +5,20 @@
 // The depthwise map never reaches memory: a workgroup computes it for its pixel tile, one K tile (64 channels) at a time, straight
 // into the LDS A tile of the 1 x 1 GEMM, and multiplies it by all 256 output channels there, so each depthwise value is made once.
 //
-// 256 threads = 4 waves; a tile is 128 output pixels (rows of the flattened N*H*W index: tiles cross rows and images) x 256 output
-// channels.  Per K tile:
-//   B: the packed pointwise filter's 256 rows x 128 B by LDS-DMA (row rho holds filter row perm(rho), as gemm_pp.hip: the epilogue
-//      lanes then own 8 consecutive channels), issued first so it lands under the depthwise stage;
+// On the tile of tile_gemm.h: 128 output pixels (rows of the flattened N*H*W index: tiles cross rows and images) x 256 output
+// channels, mma_cols<4>.  Per K tile:
+//   B: the packed pointwise filter's 256 rows x 128 B by LDS-DMA, issued first so it lands under the depthwise stage;
 //   A: thread t computes channel chunk t & 7 (8 channels) of pixels (t >> 3) + 32 i, i < 4: the 9 taps are 16-byte loads through
 //      L1 / L2 (taps outside the image — padding, another row, another image — are masked per pixel to an out-of-range descriptor
 //      offset and read as zeros), fp32 fmaf in dwconv_kernel's tap order (r-major, then s), then * s1, + t1, rounded to fp16 and
-//      written to the swizzled A tile (chunk c of row r in slot c ^ ((r >> 1) & 7)).  Channel chunks past C (the 48-channel tail
-//      K tile of C = 304) and pixel rows past M are written as zeros; the packed filter's K padding is zero too;
-//   then one barrier, 64 MFMA 16x16x32 per wave (wave w: filter rows 64 w .. +63 x all 128 pixels), one barrier.
+//      written to the swizzled A tile.  Channel chunks past C (the 48-channel tail K tile of C = 304) and pixel rows past M are
+//      written as zeros; the packed filter's K padding is zero too;
+//   then one barrier, 64 MFMAs per wave (wave w: filter rows 64 w .. +63 x all 128 pixels), one barrier.
 // A and B are single-buffered (48 KiB): two workgroups share a CU (the accumulators hold 128 registers a lane; 248 VGPRs, no
 // scratch), and only the other workgroup's stages overlap one's depthwise stage — its tap loads are not prefetched across K tiles.
 // Measured at DeepLabV3+'s ASPP shape: 0.42 ms against 0.80 ms for the dwconv + conv pair, ~165 TFLOP/s, far from the
 // MFMA bound; at dilation 1 the pair (dwconv_strip_kernel + gemm_pp) is faster and the engine keeps it there.
-#include "kernel_util.h"
+#include "tile_gemm.h"
 
 namespace tlxmi {
 
@@ -45,14 +44,7 @@ __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
     const int t = threadIdx.x, lane = t & 63;
     const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
 
-    // block -> tile: blocks sharing an XCD (id % 8) take consecutive tiles, so the halo rows of neighbouring tiles meet in one L2
-    int tile;
-    {
-        const int nb = a.mtiles, id = (int)blockIdx.x;
-        const int xcd = id & 7, qd = nb >> 3, rm = nb & 7;
-        tile = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (id >> 3);
-    }
-    const int bm0 = tile * 128;
+    const int bm0 = xcd_tile(a.mtiles, (int)blockIdx.x) * 128;
     const __amdgpu_buffer_rsrc_t xsrd = buf_srd(a.x, a.x_bytes), wsrd = buf_srd(a.wp, a.w_bytes), ysrd = buf_srd(a.y, a.y_bytes);
 
     // ---- depthwise role: chunk c of pixel rows p_i = (t >> 3) + 32 i; tap (r, s) of row i at byte xo[i] + r * rowb + s * colb
@@ -79,35 +71,16 @@ __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
         }
         mk[i] = k;
     }
-    char* const arow = sa + pr * 128;      // + 32 * 128 * i;  slot of chunk c in rows pr + 32 i: (pr >> 1) & 7 is the same for all i
-    const int aslot = (c ^ ((pr >> 1) & 7)) << 4;
+    char* const arow = sa + a_slot(pr, c);      // + 32 * 128 * i: the slot is the same for all i
 
-    // ---- B loader: piece q = wid + 4 j (8 rows x 128 B, one wave instruction); lane -> row 8 q + (lane >> 3), slot lane & 7
-    const int lc = (lane & 7) ^ ((4 * (wid & 1) + (lane >> 4)) & 7);
-    // filter row of LDS row rho = 8 (wid + 4 j) + (lane >> 3): perm(rho) = 32 j + wo_p (bits 0-1 and 3-4 of rho come from the lane)
-    int wo0;
-    {
-        const int rho = 8 * wid + (lane >> 3);
-        const int n = (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3);
-        wo0 = n * a.Kp_bytes + lc * 16;
-    }
-    const int wstep = 32 * a.Kp_bytes;
-
-    // ---- fragments: lane (frow, fg) reads row frow of a 16-row sub-tile, 16-byte chunk 4 ks + fg
-    const int frow = lane & 15, fg = lane >> 4;
-    const int foff = frow * 128 + ((fg ^ ((frow >> 1) & 7)) << 4);     // ks = 1: foff ^ 64
-
+    const int wo = filter_dma_offset(lane, wid, 0, a.Kp_bytes), wstep = filter_dma_step(a.Kp_bytes);
+    const int fg = lane >> 4, foff = frag_off(lane);
     f32x4 acc[4][8];   // [filter sub-tile ci: rows 64 wid + 16 ci][pixel sub-tile pi: rows 16 pi]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     for (int kt = 0; kt < a.ktiles; ++kt) {
         // B(kt): the barrier that closed K tile kt - 1 retired every fragment read of the old tile
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            buf_dma16(wsrd, sb + (wid + 4 * j) * 1024, wo0 + j * wstep + kt * 128);
+        dma_filter<8>(wsrd, sb, wid, wo, wstep, kt);
 
         // A(kt): depthwise
         {
@@ -160,38 +133,16 @@ __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
                     hv[e] = (half_t)v;
                 }
                 if (!(mk[i] & 0x10u)) hv = half8v{0, 0, 0, 0, 0, 0, 0, 0};   // centre tap outside = pixel row past M
-                *reinterpret_cast<half8v*>(arow + 32 * 128 * i + aslot) = hv;
+                *reinterpret_cast<half8v*>(arow + 32 * 128 * i) = hv;
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's B pieces landed
         __syncthreads();
-
-        // 64 MFMAs: W rows 64 wid + 16 ci, pixel rows 16 pi
-        {
-            u32x4 wf[4][2];
-#pragma unroll
-            for (int ci = 0; ci < 4; ++ci) {
-                const char* p = sb + (4 * wid + ci) * 2048;
-                wf[ci][0] = *reinterpret_cast<const u32x4*>(p + foff);
-                wf[ci][1] = *reinterpret_cast<const u32x4*>(p + (foff ^ 64));
-            }
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int pi = 0; pi < 8; ++pi) {
-                const char* p = sa + pi * 2048;
-                const u32x4 x0 = *reinterpret_cast<const u32x4*>(p + foff), x1 = *reinterpret_cast<const u32x4*>(p + (foff ^ 64));
-#pragma unroll
-                for (int ci = 0; ci < 4; ++ci) {
-                    acc[ci][pi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, wf[ci][0]), __builtin_bit_cast(half8v, x0), acc[ci][pi], 0, 0, 0);
-                    acc[ci][pi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8v, wf[ci][1]), __builtin_bit_cast(half8v, x1), acc[ci][pi], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
+        mma_cols<4>(acc, sb + 4 * wid * 2048, sa, foff);
         __syncthreads();
     }
 
-    // ---- epilogue: lane (fg, px) owns channels 64 wid + 32 g + 8 fg .. +7 (sub-tiles ci = 2 g, 2 g + 1) of pixel 16 pi + px
+    // ---- epilogue: lane (fg, px) owns channels 64 wid + 32 g + 8 fg .. +7 of pixel 16 pi + px
     const int px = lane & 15;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
@@ -207,9 +158,9 @@ __global__ __launch_bounds__(256, 2) void sepconv_kernel(const SepArgs a) {
             const int m = bm0 + 16 * pi + px;
             half8v hv;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v0 = acc[2 * g][pi][e] * sc[e] + sf[e];
-                float v1 = acc[2 * g + 1][pi][e] * sc[4 + e] + sf[4 + e];
+            for (int e = 0; e < 4; ++e) {      // (the two sub-tiles side by side: the order the accumulators are read in)
+                float v0 = owned8(acc[2 * g][pi], acc[2 * g + 1][pi], e) * sc[e] + sf[e];
+                float v1 = owned8(acc[2 * g][pi], acc[2 * g + 1][pi], 4 + e) * sc[4 + e] + sf[4 + e];
                 if (RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
                 hv[e] = (half_t)v0;
                 hv[4 + e] = (half_t)v1;
@@ -260,12 +211,10 @@ extern "C" int tlxmi_sepconv2d(const tlxmi_sepconv2d_desc* d, const void* x, con
     a.H = d->H; a.W = d->W; a.C = d->C; a.dil = d->dil_h; a.x_ld = d->x_ld; a.y_ld = d->y_ld;
     const long long M = (long long)d->N * d->H * d->W;
     a.M = (int)M; a.HW = d->H * d->W;
-    a.Kp_bytes = (d->C * 2 + 127) / 128 * 128;        // tlxmi_pack_filter's row pitch for a 1 x 1 filter
-    a.ktiles = a.Kp_bytes / 128;
-    a.mtiles = (int)((M + 127) / 128);
+    const PackedFilter pf(d->C, 256, 256);
+    a.Kp_bytes = pf.Kp_bytes; a.ktiles = pf.ktiles; a.mtiles = pf.tiles(M); a.w_bytes = pf.w_bytes;
     a.act_param = d->act_param;
     a.x_bytes = (unsigned)(M * d->x_ld * 2);
-    a.w_bytes = (unsigned)(256u * (unsigned)a.Kp_bytes);
     a.y_bytes = (unsigned)(((M - 1) * d->y_ld + 256) * 2);
     hipStream_t st = as_stream(stream);
     if (d->act == TLXMI_ACT_RELU)
