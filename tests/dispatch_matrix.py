@@ -9,6 +9,8 @@ epilogue.  Features (the `feat` letter of a case):
   c y is a column slice (y_ld > Cout)        h geometry: strides, dilation, (3,5) taps, one-sided overhang, crop
   d res is a column slice, both orders       i TLXMI_PLAN_SHARED_HALF / _FULL
   e y_nstride + TLXMI_EPI_RES_BCAST_N        j grouped layers on the block-diagonal chunk path
+  k a K tail inside a column slice of x: the 16-byte chunks by which the last 128-byte K tile overruns K lie in the
+    columns to the right of the slice, which the test fills with NaN / +inf / -inf (k_tail() below)
 """
 import zlib
 from dataclasses import dataclass, replace
@@ -138,6 +140,12 @@ def _cases():
     # j. grouped layers as block-diagonal launch chunks
     c += [Case("j_g8", "j", 2, 12, 12, 256, 1024, R=3, S=3, pad=(1, 1), groups=8, res="dense", **relu),
           Case("j_g8_diag", "j", 2, 12, 12, 128, 128, R=3, S=3, pad=(1, 1), groups=8, **relu)]   # 64 -> 64 chunks, 16 per group
+    # k. a K tail inside a column slice: K is no whole number of 128-byte tiles in either dtype and x_ld > x_off + Cin
+    c += [Case("k_gemm", "k", 3, 7, 37, 200, 328, x_ld=296, **xs, **relu),                       # 25 / 50 chunks
+          Case("k_gemm_res", "k", 3, 7, 37, 712, 328, x_ld=760, **xs, scale=False, res="dense", res_ld=328 + 24, res_off=8,
+               **relu),                                                                      # 89 chunks = 12 K tiles: gemm_stream with a residual
+          Case("k_conv", "k", 2, 9, 10, 24, 72, R=3, S=3, pad=(1, 1), x_ld=40, x_off=8),         # 27 / 54 chunks
+          Case("k_conv72", "k", 2, 13, 11, 72, 264, R=3, S=3, pad=(1, 1), x_ld=136, **xs)]      # 81 / 162 chunks
     assert len({k.name for k in c}) == len(c)
     return c
 
@@ -166,6 +174,13 @@ def group_chunks(Cin, Cout, groups, es):
         if m * cgi * es >= 128 and m * cgo >= 64:
             break
     return groups // m_ok if m_ok else 0
+
+
+def k_tail(case, dtype):
+    """(kchunks, the 16-byte chunks by which the last 128-byte K tile overruns K, the columns of x's buffer to the right of the
+    slice) of an ungrouped case: a loader that lost its K-tail mask reads the overrun from those columns."""
+    kchunks = case.R * case.S * (case.Cin * es_of(dtype) // 16)
+    return kchunks, -kchunks % 8, (case.x_ld or case.Cin) - case.x_off - case.Cin
 
 
 @dataclass(frozen=True)

@@ -3,8 +3,8 @@
 dispatch<T>() of conv_igemm.hip serves Conv2d and Linear with a dozen kernels (five implicit-GEMM tiles, gemm256, the antiphase
 gemm_pp family, the persistent gemm_stream, conv_halo, gemm_wreg) chosen by the CU count, the output bytes per FLOP, M and the
 plan flags.  dispatch_matrix.py lists small cases per feature (column slices of x / y / res, batch strides, the broadcast
-residual, scalar stores, geometry, plan flags, grouped chunks) and, from the documented eligibility conditions, the kernels
-that admit each case.  Here every (case, dtype, kernel) cell is forced through the tuning flavour (TLXMI_TILE, TLXMI_HALO=0 /
+residual, scalar stores, geometry, plan flags, grouped chunks, a K tail inside a column slice) and, from the documented
+eligibility conditions, the kernels that admit each case.  Here every (case, dtype, kernel) cell is forced through the tuning flavour (TLXMI_TILE, TLXMI_HALO=0 /
 TLXMI_WREG=0 when a tile is forced, TLXMI_TAIL=0, split K off) — only where the product dispatcher itself could launch that
 kernel — and checked:
 
@@ -12,6 +12,13 @@ kernel — and checked:
 * against float64 F.conv2d on the fp16-rounded inputs + a float64 epilogue, within util.tol;
 * the output is a window of a wider, longer buffer pre-filled with NaN and followed by a sentinel tail: every addressed element is
   written, every other element (pad columns, lead rows, the gaps between images, the guard rows) is still NaN, the tail intact;
+* the memory beside the operands does not reach the result: x and res are column slices / row ranges of buffers whose every other
+  element (the columns left and right of the slice, the spare row behind the last pixel, the rows between the images of res)
+  holds NaN, +inf or -inf in turn — all three, since fmaxf(NaN, 0) of a ReLU epilogue is 0 wherever the reference is 0 — and a
+  twin launch on the same buffers, same pitches, same forced kernel, with those elements set to zero must give the same bits.
+  A tile's zero factor (a K tile past K, a filter row past Cout, a pixel row past M, a padding tap) times finite junk is 0 and
+  would go unnoticed; times NaN or inf it is NaN, so this holds only while the load on the other side is masked too.  The twin is
+  compared first: a difference is reported as a read of foreign memory, apart from any other error;
 * a second launch gives the same bits.
 
 The GEMM-family candidates forced onto the batch-strided / unaligned cases (e, f, g) must end on an igemm tile and still be
@@ -36,26 +43,31 @@ RESULTS = {}              # (feat, kernel, 'fp16' | 'fp32') -> 'confirmed' | 'fa
 _cache = {}               # the device buffers of the (case, dtype) in use
 
 
+def _junk(rows, ld):
+    """[rows][ld] of NaN, +inf, -inf, NaN, ... : what no kernel may read."""
+    return torch.tensor([float("nan"), float("inf"), float("-inf")]).repeat(-(-rows * ld // 3))[:rows * ld].view(rows, ld).clone()
+
+
 class _Bufs:
     def __init__(self, case, dtype, dev):
         self.case, self.dtype, self.L = case, dtype, DM.layout(case, dtype)
         L, c = self.L, case
         t = DM.make_inputs(case, dtype)
         self.ref = DM.reference(case, t)
-        g = torch.Generator().manual_seed(7)
-        junk = lambda *shape: torch.randn(*shape, generator=g).half().float()       # noqa: E731  finite, unlike any input row
-        # x: [N*H*W (+ 1 spare row)][x_ld], the image in columns x_off .. x_off + Cin, everything else junk
-        xb = junk(c.N * c.H * c.W + 1, L.x_ld)
+        # x: [N*H*W (+ 1 spare row)][x_ld], the image in columns x_off .. x_off + Cin, everything else non-finite
+        xb = _junk(c.N * c.H * c.W + 1, L.x_ld)
         xb[:-1].view(c.N, c.H, c.W, L.x_ld)[..., c.x_off:c.x_off + c.Cin] = t["x"].permute(0, 2, 3, 1)
         self.xbuf = xb.to(dtype).to(dev).view(-1)
+        self.foreign = [(self.xbuf, ~self.xbuf.isfinite(), self.xbuf.clone())]      # (buffer, its foreign elements, as poisoned)
         self.x4 = torch.as_strided(self.xbuf, (c.N, c.H, c.W, L.x_ld), (c.H * c.W * L.x_ld, c.W * L.x_ld, L.x_ld, 1), c.x_off)
         self.res = self.resbuf = None
         if c.res:
-            rb = junk(L.res_images * L.res_rows_per_image + 1, L.res_ld)
+            rb = _junk(L.res_images * L.res_rows_per_image + 1, L.res_ld)
             rv = rb[:-1].view(L.res_images, L.res_rows_per_image, L.res_ld)
             rv[:, :L.HoWo, c.res_off:c.res_off + c.Cout] = t["res"].permute(0, 2, 3, 1).reshape(L.res_images, L.HoWo, c.Cout)
             self.resbuf = rb.to(dtype).to(dev).view(-1)
             self.res = self.resbuf[c.res_off:]
+            self.foreign.append((self.resbuf, ~self.resbuf.isfinite(), self.resbuf.clone()))
         w = t["w"].to(dev)
         self.pk = E.PackedGroupFilter(w, c.groups, dtype) if c.groups > 1 else E.PackedFilter(w, dtype)
         self.scale = t["scale"].to(dev) if t["scale"] is not None else None
@@ -77,6 +89,18 @@ class _Bufs:
     def reset(self):
         self.ybuf[:self.n].fill_(float("nan"))
         self.ybuf[self.n:].fill_(SENTINEL)
+
+    def poison(self, on):
+        """The elements around x and res: NaN / +inf / -inf (on), or zeros in the same buffers (the twin)."""
+        for buf, mask, poisoned in self.foreign:
+            if on:
+                buf.copy_(poisoned)
+            else:
+                buf.masked_fill_(mask, 0.0)
+
+    def addressed(self):
+        torch.cuda.synchronize()
+        return self.ybuf[:self.n][self.idx]
 
     def launch(self):
         """The C entry point itself, on whichever flavour of the library is current."""
@@ -118,7 +142,8 @@ def _cell_id(cell):
 
 
 def _forced(b, kernel, capfd):
-    """Two launches with `kernel` forced -> the kernels the trace says were launched."""
+    """Three launches with `kernel` forced (poisoned neighbours, zero neighbours, poisoned again) -> the kernels the trace says were
+    launched."""
     env = dict(TLXMI_TAIL="0", TLXMI_TRACE_TILES="1", TLXMI_GCONV="0")
     if kernel in DM.TILE_OF:
         env.update(TLXMI_TILE=str(DM.TILE_OF[kernel]), TLXMI_HALO="0", TLXMI_WREG="0")
@@ -129,18 +154,29 @@ def _forced(b, kernel, capfd):
         with tuning(**env):
             b.reset()
             b.launch()
-            first = b.check(what)
+            first = b.addressed()
+            b.poison(False)
             b.reset()
             b.launch()
-            torch.cuda.synchronize()
-            second = b.ybuf[:b.n][b.idx]
+            twin = b.addressed()
+            b.poison(True)
+            b.reset()
+            b.launch()
+            second = b.addressed()
     finally:
+        b.poison(True)
         E.set_option("conv_splitk", True)
     bits = torch.int16 if b.dtype == torch.float16 else torch.int32
+    differ = first.view(bits) != twin.view(bits)
+    assert not bool(differ.any()), (f"{what}: the kernel read the memory beside its operands: {int(differ.sum())} of {differ.numel()} "
+                                    f"addressed elements change when the NaN / inf around x and res become zeros "
+                                    f"({int((~first.isfinite()).sum())} of them non-finite), first at [n, pixel, channel] = "
+                                    f"{differ.nonzero()[0].tolist()}")
     assert torch.equal(first.view(bits), second.view(bits)), f"{what}: a second launch gave other bits"
+    b.check(what)
     trace = capfd.readouterr().err
     names = [ln.split()[1] for ln in trace.splitlines() if ln.startswith("launched ")]
-    assert len(names) == 2, f"{what}: expected one `launched` line per call:\n{trace}"
+    assert len(names) == 3, f"{what}: expected one `launched` line per call:\n{trace}"
     return names, trace
 
 
@@ -153,7 +189,7 @@ def test_required_cell(dev, capfd, cell):
     except BaseException:
         RESULTS[key] = f"{case.name} failed"
         raise
-    if names != [kernel, kernel]:
+    if names != [kernel] * 3:
         RESULTS[key] = f"{case.name} ran on {names}"
         raise AssertionError(f"{_cell_id(cell)}: the dispatcher launched {names}, not the forced kernel:\n{trace}")
     RESULTS.setdefault(key, "confirmed")

@@ -289,7 +289,7 @@ def test_dispatch_matrix_reference_agrees_with_the_oracle(case):
 
 def test_dispatch_matrix_has_every_required_pair():
     """a - d, h, i on every product-reachable kernel, e / f / g / j on the four small igemm tiles, in fp16 and fp32 (fp16 only:
-    conv_halo, gemm_wreg); the special shapes the matrix must contain; no case outside a kernel's documented conditions."""
+    conv_halo, gemm_wreg); k (a K tail inside a column slice) on the ten tile kernels, gemm_stream in fp16 at least; the special shapes the matrix must contain; no case outside a kernel's documented conditions."""
     import dispatch_matrix as DM
     from tlxcv_amd import _lib
     have = {(c.feat, kn, dt) for c, dt, kn in DM.CELLS}
@@ -303,6 +303,9 @@ def test_dispatch_matrix_has_every_required_pair():
                 feats += "efgj"
             if kn == "stream8" and dt != torch.float16:
                 feats = feats.replace("d", "")         # gemm_stream takes a residual in fp16 only
+            if kn in DM.TILE_OF and not (kn == "stream8" and dt != torch.float16):
+                feats += "k"                           # a K tail inside a column slice: the ten tile kernels (conv_halo and gemm_wreg
+                                                       # take whole K tiles only)
             missing = [f for f in feats if (f, kn, dt) not in have]
             assert not missing, (kn, dt, missing)
     # GEMM-family kernels never appear where the batch strides or the row alignment rule them out
@@ -317,6 +320,17 @@ def test_dispatch_matrix_has_every_required_pair():
             if c.groups > 1:
                 n = DM.group_chunks(c.Cin, c.Cout, c.groups, es)
                 assert n > 1 and n == _lib.load().tlxmi_group_conv_chunks(c.Cin, c.Cout, c.groups, 0 if es == 2 else 1)
+    # feature k is not vacuous: in both dtypes K ends inside a 128-byte tile, and the chunks by which that tile overruns K are
+    # covered by the columns to the right of the slice, which hold no input (the GPU test fills them with NaN / inf); the first
+    # chunk past K of a 1x1 row lies wholly inside them
+    kcases = [c for c in DM.CASES if c.feat == "k"]
+    assert {c.name for c in kcases} == {"k_gemm", "k_gemm_res", "k_conv", "k_conv72"}
+    assert not any(kn in DM.FP16_ONLY for c, _, kn in DM.CELLS if c.feat == "k") and not any(c.feat == "k" for c, _, _ in DM.FALLBACK_CELLS)
+    for c in kcases:
+        for dt in DM.DTYPES:
+            kchunks, overrun, spare = DM.k_tail(c, dt)
+            assert c.groups == 1 and c.x_off > 0 and kchunks % 8 != 0 and spare >= overrun >= 1 and spare >= 16 // DM.es_of(dt), (c.name, dt)
+    assert DM.k_tail(kcases[0], torch.float16) == (25, 7, 72) and DM.k_tail(kcases[0], torch.float32) == (50, 6, 72)
     f16 = torch.float16
     kch = lambda c: c.R * c.S * c.Cin * 2 // 16      # noqa: E731
     assert any(kch(c) % 8 for c in DM.CASES) and any(DM.layout(c, f16).M % 256 for c in DM.CASES)

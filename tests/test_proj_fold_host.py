@@ -148,6 +148,9 @@ def test_folded_filter_is_built_once_and_follows_its_four_sources(monkeypatch):
     monkeypatch.setattr(E, "PackedFilter", _FakePacked)
     monkeypatch.setattr(E, "_f32", lambda t: t.detach().float())
     monkeypatch.setattr(E, "note_cache_build", lambda: None)
+    # set_eval() moves a model that is still on the host to the GPU whenever one is visible (tlx/nn: lazy device placement); this test
+    # compares the fold with host tensors, so it keeps the block where it was built, on a machine with a GPU as on one without
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     down = nn.Sequential([nn.GroupConv2d(in_channels=64, out_channels=256, kernel_size=1, stride=2, b_init=(), padding=0, data_format="channels_first"),
                           nn.BatchNorm2d(num_features=256, data_format="channels_first")])
     blk = BottleneckBlock(64, 64, stride=2, downsample=down)
