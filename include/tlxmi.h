@@ -183,7 +183,11 @@ int tlxmi_conv2d_maxpool_supported(const tlxmi_conv2d_desc* d);
  * tlxmi_multiclass_nms: tlx_multiclass_nms — best class per box, score >= score_threshold, class-aware greedy NMS
  *   (IoU > nms_threshold, descending score), the first keep_top_k survivors as rows (class, score, x1, y1, x2, y2) of
  *   detections [N][keep_top_k][6] (zero filled), counts [N].  M <= 65536 boxes per image; workspace:
- *   tlxmi_multiclass_nms_workspace_bytes(N, M).
+ *   tlxmi_multiclass_nms_workspace_bytes(N, M).  More than 65536 boxes: TLXMI_ERR_UNSUPPORTED, nothing written.
+ *   Scores: any float, negative ones under a negative threshold included (reported and ordered as they are); a box with a NaN
+ *   among its C scores is dropped, as torch.max propagates the NaN and NaN >= threshold is false.  The IoU arithmetic is
+ *   torchvision's, every operation rounded once to fp32 (no fused multiply-add).  Box coordinates must be finite: NaN / inf
+ *   coordinates are out of scope (the class shift max + 1 and every IoU of the image would depend on them).
  * ---------------------------------------------------------------------------------------- */
 /* IoU-aware objectness of the YOLOv3 head (yolov3.py:355-376): x [pixels][A*(6+C)] NHWC (A IoU channels first) ->
  * y [pixels][A*(5+C)] with obj' = de_sigmoid(sigmoid(obj)^(1 - factor) * sigmoid(iou)^factor); box / class entries copied. */
@@ -204,13 +208,16 @@ int tlxmi_multiclass_nms_index(const float* boxes, const float* scores, int N, i
 /* ------------------------------------------------------------------------------------------
  * Image pre-processing on the device (the host pipeline of demo/image_classification/predict.py:22-29,
  * Compose([Resize((h, w)), Normalize(mean, std), ToTensor(data_format)])): uint8 HWC images in, network input out.
- *   images:  [N][H][W][C] uint8, C <= 4
+ *   images:  [N][H][W][C] uint8, C <= 4.  The channels are resampled independently (Pillow's mode "L", channel by channel):
+ *            that is this entry's contract for every C.  The host Resize of an RGBA image premultiplies alpha first; that
+ *            path stays on the host.
  *   xbounds / xk, ybounds / yk: the resampler tables of the two passes — bounds[o] = (first input sample, count),
  *            k[o][t] integer weights with 22 fractional bits, row pitch kw / kh — built by the caller exactly as Pillow's
  *            ImagingResample does (tlxcv_amd/tlx/vision/transforms/resample.py), which makes the result bit-identical to
  *            PIL.Image.resize on the host; an axis that keeps its size passes the identity table (count 1, weight 1 << 22)
  *   mean / std: [C] fp32 when `normalize`, else the value is scaled by 1/255 (ToTensor on uint8)
- *   workspace: tlxmi_preprocess_u8_workspace_bytes(d) bytes (the uint8 image after the horizontal pass)
+ *   workspace: tlxmi_preprocess_u8_workspace_bytes(d) bytes (the uint8 image after the first pass: the horizontal one, or, as in
+ *            Pillow's Image.resize, the vertical one when H > 100 * W and out_h < H)
  *   out:     layout 0 [N][C][out_h][out_w] ("CHW"), 1 [N][out_h][out_w][C] ("HWC"), 2 the fold_b x fold_b space-to-depth
  *            NHWC image of tlxmi_nchw_to_nhwc_s2d ([N][out_h/b][out_w/b][cpad], channel (ph*b + pw)*C + c, zero padded)
  * ---------------------------------------------------------------------------------------- */

@@ -88,7 +88,21 @@ __global__ void yolo_box_kernel(const T* __restrict__ x, const int* __restrict__
     }
 }
 
-// keys[n][MP]: (score bits << 32) | ~index for candidates (score >= threshold), 0 otherwise / for padding; cls[n][M]
+// keys[n][MP]: (score_key(best) << 32) | ~index for candidates (best >= threshold), 0 otherwise / for padding; cls[n][M].
+// score_key maps the float's bits to an unsigned word that orders as the float does, any sign (negative: all bits flipped,
+// else the sign bit set; -0 counts as +0, the two compare equal and tie by index as in a stable sort), and is never 0 for a
+// candidate.  The word only orders: the row's score is read back from `scores` where the row is written.  A NaN among a box's
+// scores makes its best score NaN (torch.max propagates it) and NaN >= threshold is false: the box is no candidate.
+__device__ __forceinline__ unsigned score_key(float v) {
+    const unsigned u = v == 0.f ? 0u : __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ unsigned long long nms_key(float best, float thr, int m) {
+    if (!(best >= thr)) return 0ull;
+    return ((unsigned long long)score_key(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)m);
+}
+
 __global__ void nms_keys_kernel(const float* __restrict__ scores, unsigned long long* __restrict__ keys, int* __restrict__ cls, int N, int M,
                                 int C, int MP, float thr) {
     const long total = (long)N * MP;
@@ -101,10 +115,9 @@ __global__ void nms_keys_kernel(const float* __restrict__ scores, unsigned long 
             float best = sp[0];
             int bc = 0;
             for (int c = 1; c < C; ++c)
-                if (sp[c] > best) { best = sp[c]; bc = c; }        // first maximal value, as argmax
+                if (!(sp[c] <= best) && best == best) { best = sp[c]; bc = c; }        // first maximal value, as argmax; a NaN sticks
             cls[n * M + m] = bc;
-            if (best >= thr && best > 0.f) key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)m);
-            else if (best >= thr) key = 1ull + (unsigned long long)(0xFFFFFFFEu - (unsigned)m);   // score 0 with a threshold <= 0: still a candidate
+            key = nms_key(best, thr, m);
         }
         keys[i] = key;
     }
@@ -127,31 +140,56 @@ __global__ void nms_keys16_kernel(const float* __restrict__ scores, unsigned lon
             const float* sp = scores + (n * M + m) * C;
             for (int c = sub; c < C; c += 16) {
                 const float v = sp[c];
-                if (v > best || c == sub) { best = v; bc = c; }          // first maximal value among this lane's classes
+                if (c == sub || (!(v <= best) && best == best)) { best = v; bc = c; }          // first maximal value among this lane's classes; a NaN sticks
             }
         }
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) {
             const float ob = __shfl_xor(best, o, 64);
             const int oc = __shfl_xor(bc, o, 64);
-            if (oc != 0x7fffffff && (bc == 0x7fffffff || ob > best || (ob == best && oc < bc))) { best = ob; bc = oc; }   // first maximal value, as argmax
+            // first maximal value, as argmax; a NaN on either side wins on both (the two lanes of a pair must agree)
+            if (oc != 0x7fffffff && (bc == 0x7fffffff || (best == best && (!(ob <= best) || (ob == best && oc < bc))))) { best = ob; bc = oc; }
         }
         if (sub == 0) {
             unsigned long long key = 0ull;
             if (m < M) {
                 cls[n * M + m] = bc;
-                if (best >= thr && best > 0.f) key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)m);
-                else if (best >= thr) key = 1ull + (unsigned long long)(0xFFFFFFFEu - (unsigned)m);
+                key = nms_key(best, thr, m);
             }
             keys[bi] = key;
         }
     }
 }
 
+// torchvision's arithmetic, restated with every operation rounded once: boxes + idxs * (max + 1), area = (x2 - x1) * (y2 - y1),
+// iou = inter / (area_a + area_b - inter).  Contraction is switched OFF in these three functions: left on, the compiler fuses
+// a * b + c into one fma rounding wherever it sees one, and it sees different ones in different copies of the same expression
+// (the kept box of the global-key kernel was shifted with one rounding; the candidate it is compared with, and every box of the
+// LDS-key kernel, with two).  The __f*_rn intrinsics do not help: HIP defines them as the plain operators, which contract.
+__device__ __forceinline__ f32x4 nms_shifted(const float* b, int c, float shift) {
+#pragma clang fp contract(off)
+    const float off = (float)c * shift;
+    return f32x4{b[0] + off, b[1] + off, b[2] + off, b[3] + off};
+}
+
+__device__ __forceinline__ float nms_area(const f32x4 b) {
+#pragma clang fp contract(off)
+    return (b[2] - b[0]) * (b[3] - b[1]);
+}
+
+__device__ __forceinline__ float nms_iou(const f32x4 a, float aarea, const f32x4 b) {
+#pragma clang fp contract(off)
+    const float w = fminf(a[2], b[2]) - fmaxf(a[0], b[0]), h = fminf(a[3], b[3]) - fmaxf(a[1], b[1]);
+    const float inter = (w > 0.f ? w : 0.f) * (h > 0.f ? h : 0.f);
+    const float barea = nms_area(b);
+    return inter / (aarea + barea - inter);
+}
+
 template <bool LDSKEYS>
-__global__ __launch_bounds__(1024) void nms_image_kernel(const float* __restrict__ boxes, unsigned long long* __restrict__ keys,
-                                                         const int* __restrict__ cls, float* __restrict__ det, int* __restrict__ count,
-                                                         int* __restrict__ kidx, int M, int MP, float nms_thr, int keep_top_k) {
+__global__ __launch_bounds__(1024) void nms_image_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                         unsigned long long* __restrict__ keys, const int* __restrict__ cls,
+                                                         float* __restrict__ det, int* __restrict__ count, int* __restrict__ kidx,
+                                                         int M, int C, int MP, float nms_thr, int keep_top_k) {
     extern __shared__ __attribute__((aligned(16))) char nms_smem[];
     // LDSKEYS (MP <= 16384): the image's keys are sorted in LDS, [MP] keys then [MP] suppression flags — the 105 compare-exchange
     // passes of 16 384 keys cost a global round trip each when sorted in place (YOLOv3, 32 images: 662 us, most of it the sort)
@@ -212,9 +250,7 @@ __global__ __launch_bounds__(1024) void nms_image_kernel(const float* __restrict
         __syncthreads();
         for (int i = t; i < LB; i += 1024) {
             const int mi = (int)(0xFFFFFFFFu - (unsigned)(kg[i] & 0xFFFFFFFFull));
-            const float* b = boxes + ((long)n * M + mi) * 4;
-            const float off = (float)cls[(long)n * M + mi] * shift;
-            lbox[i] = f32x4{b[0] + off, b[1] + off, b[2] + off, b[3] + off};
+            lbox[i] = nms_shifted(boxes + ((long)n * M + mi) * 4, cls[(long)n * M + mi], shift);
         }
         __syncthreads();
     }
@@ -226,17 +262,14 @@ __global__ __launch_bounds__(1024) void nms_image_kernel(const float* __restrict
         // the kept box: from LDS when it is among the first LB (no global load inside the loop — the key -> box / class gathers of
         // every kept box were a chain of two dependent global loads that all 1024 threads waited for); its output row is
         // written after the loop, all rows in parallel
-        float ax1, ay1, ax2, ay2;
+        f32x4 ab;
         if (i < LB) {
-            const f32x4 ab = lbox[i];
-            ax1 = ab[0]; ay1 = ab[1]; ax2 = ab[2]; ay2 = ab[3];
+            ab = lbox[i];
         } else {
             const int mi = (int)(0xFFFFFFFFu - (unsigned)(kg[i] & 0xFFFFFFFFull));
-            const float* bi = boxes + ((long)n * M + mi) * 4;
-            const float off = (float)cls[(long)n * M + mi] * shift;
-            ax1 = bi[0] + off; ay1 = bi[1] + off; ax2 = bi[2] + off; ay2 = bi[3] + off;
+            ab = nms_shifted(boxes + ((long)n * M + mi) * 4, cls[(long)n * M + mi], shift);
         }
-        const float aarea = (ax2 - ax1) * (ay2 - ay1);
+        const float aarea = nms_area(ab);
         if (defer) {
             if (t == 0) s_kept[kept] = i;
         } else if (t == 0) {
@@ -244,26 +277,21 @@ __global__ __launch_bounds__(1024) void nms_image_kernel(const float* __restrict
             const int mi = (int)(0xFFFFFFFFu - (unsigned)(ki & 0xFFFFFFFFull));
             const float* bi = boxes + ((long)n * M + mi) * 4;
             float* o = dp + kept * 6;
-            o[0] = (float)cls[(long)n * M + mi]; o[1] = __uint_as_float((unsigned)(ki >> 32)); o[2] = bi[0]; o[3] = bi[1]; o[4] = bi[2]; o[5] = bi[3];
+            const int ci = cls[(long)n * M + mi];
+            o[0] = (float)ci; o[1] = scores[((long)n * M + mi) * C + ci]; o[2] = bi[0]; o[3] = bi[1]; o[4] = bi[2]; o[5] = bi[3];
             if (kidx) kidx[(long)n * keep_top_k + kept] = mi;
         }
         ++kept;
         for (int j = i + 1 + t; j < K; j += 1024) {
             if (sup[j]) continue;
-            float bx1, by1, bx2, by2;
+            f32x4 bb;
             if (j < LB) {
-                const f32x4 bb = lbox[j];
-                bx1 = bb[0]; by1 = bb[1]; bx2 = bb[2]; by2 = bb[3];
+                bb = lbox[j];
             } else {
                 const int mj = (int)(0xFFFFFFFFu - (unsigned)(kg[j] & 0xFFFFFFFFull));
-                const float* bj = boxes + ((long)n * M + mj) * 4;
-                const float offj = (float)cls[(long)n * M + mj] * shift;
-                bx1 = bj[0] + offj; by1 = bj[1] + offj; bx2 = bj[2] + offj; by2 = bj[3] + offj;
+                bb = nms_shifted(boxes + ((long)n * M + mj) * 4, cls[(long)n * M + mj], shift);
             }
-            const float w = fminf(ax2, bx2) - fmaxf(ax1, bx1), h = fminf(ay2, by2) - fmaxf(ay1, by1);
-            const float inter = (w > 0.f ? w : 0.f) * (h > 0.f ? h : 0.f);
-            const float iou = inter / (aarea + (bx2 - bx1) * (by2 - by1) - inter);
-            if (iou > nms_thr) sup[j] = 1;
+            if (nms_iou(ab, aarea, bb) > nms_thr) sup[j] = 1;
         }
         __syncthreads();
     }
@@ -274,7 +302,8 @@ __global__ __launch_bounds__(1024) void nms_image_kernel(const float* __restrict
             const int mi = (int)(0xFFFFFFFFu - (unsigned)(ki & 0xFFFFFFFFull));
             const float* bi = boxes + ((long)n * M + mi) * 4;
             float* o = dp + t * 6;
-            o[0] = (float)cls[(long)n * M + mi]; o[1] = __uint_as_float((unsigned)(ki >> 32)); o[2] = bi[0]; o[3] = bi[1]; o[4] = bi[2]; o[5] = bi[3];
+            const int ci = cls[(long)n * M + mi];
+            o[0] = (float)ci; o[1] = scores[((long)n * M + mi) * C + ci]; o[2] = bi[0]; o[3] = bi[1]; o[4] = bi[2]; o[5] = bi[3];
             if (kidx) kidx[(long)n * keep_top_k + t] = mi;
         }
     }
@@ -349,12 +378,12 @@ static int multiclass_nms_impl(const float* boxes, const float* scores, int N, i
         const size_t lds = (size_t)MP * 9;
         if (lds > 48 * 1024)       // (the kernel also has 8 KB of static LDS: the dynamic limit cannot be the whole 160 KB)
             if (int rc = raise_lds_limit(reinterpret_cast<const void*>(&nms_image_kernel<true>), 148 * 1024, "multiclass_nms")) return rc;
-        hipLaunchKernelGGL(nms_image_kernel<true>, dim3(N), dim3(1024), lds, st, boxes, keys, cls, detections, counts, keep_index, M, MP, nms_threshold, keep_top_k);
+        hipLaunchKernelGGL(nms_image_kernel<true>, dim3(N), dim3(1024), lds, st, boxes, scores, keys, cls, detections, counts, keep_index, M, C, MP, nms_threshold, keep_top_k);
     } else {
         const size_t lds = (size_t)MP;
         if (lds > 48 * 1024)
             if (int rc = raise_lds_limit(reinterpret_cast<const void*>(&nms_image_kernel<false>), 96 * 1024, "multiclass_nms")) return rc;
-        hipLaunchKernelGGL(nms_image_kernel<false>, dim3(N), dim3(1024), lds, st, boxes, keys, cls, detections, counts, keep_index, M, MP, nms_threshold, keep_top_k);
+        hipLaunchKernelGGL(nms_image_kernel<false>, dim3(N), dim3(1024), lds, st, boxes, scores, keys, cls, detections, counts, keep_index, M, C, MP, nms_threshold, keep_top_k);
     }
     return check_launch("multiclass_nms");
 }

@@ -5,7 +5,8 @@
 //
 // Resize is Pillow's two-pass resampler restated (tlxcv_amd/tlx/vision/transforms/resample.py builds the tables from the
 // published algorithm, checked bit for bit against PIL): per axis, output sample o = clip((2^21 + sum_t in[lo(o) + t] *
-// k[o][t]) >> 22) in integer arithmetic, horizontal pass first, its uint8 result feeds the vertical pass — so the device
+// k[o][t]) >> 22) in integer arithmetic, horizontal pass first, its uint8 result feeds the vertical pass (the vertical pass first
+// where Pillow's Image.resize runs it first: height > 100 * width and a smaller output height) — so the device
 // result is BIT-IDENTICAL to the host pipeline, not merely close.  Normalize is (v - mean[c]) / std[c] in fp32 with IEEE
 // subtraction and division (numpy's float32 arithmetic); without it the uint8 value is scaled by 1/255 (ToTensor's rule).
 // Output layouts: NCHW ("CHW"), NHWC ("HWC"), or the b x b space-to-depth NHWC image of tlxmi_nchw_to_nhwc_s2d (channel
@@ -33,22 +34,48 @@ __global__ void resize_h_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __r
     }
 }
 
+// vertical pass on its own: src [N][H][W][C] -> dst [N][OH][W][C]; one thread per output pixel.  Pillow runs it FIRST on a very tall
+// image that shrinks vertically (Image.resize: height > 100 * width and out_h < height), and the uint8 rounding between the passes
+// makes the order visible in the result.
+__global__ void resize_v_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const int* __restrict__ bounds,
+                                   const int* __restrict__ kk, long N, int H, int OH, int W, int C, int ksize) {
+    const long total = N * OH * W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W);
+        const long r = i / W;
+        const int yy = (int)(r % OH);
+        const long n = r / OH;
+        const int y0 = bounds[2 * yy], cnt = bounds[2 * yy + 1];
+        const int* k = kk + (long)yy * ksize;
+        const uint8_t* sp = src + ((n * H + y0) * W + x) * C;
+        const long rs = (long)W * C;
+        for (int c = 0; c < C; ++c) {
+            int acc = 1 << 21;
+            for (int t = 0; t < cnt; ++t) acc += (int)sp[t * rs + c] * k[t];
+            acc >>= 22;
+            dst[i * C + c] = (uint8_t)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
+        }
+    }
+}
+
 struct PreArgs {
-    const uint8_t* src;       // [N][H][OW][C] (after the horizontal pass)
-    const int* bounds;        // [OH][2]
-    const int* kk;            // [OH][ksize]
+    const uint8_t* src;       // [N][H][OW][C] (after the horizontal pass); xfirst == 0: [N][OH][W][C] (after the vertical pass)
+    const int* bounds;        // [OH][2]; xfirst == 0: [OW][2]
+    const int* kk;            // [OH][ksize]; xfirst == 0: [OW][ksize]
     const float* mean;        // [C] or null
     const float* std_;        // [C] or null
     void* out;
     int N, H, OH, OW, C, ksize, layout, b, cpad, normalize;
+    int xfirst, W;            // xfirst: the horizontal pass ran first and this kernel does the vertical one; else the other way round
 };
 
 __device__ __forceinline__ float pre_value(const PreArgs& a, long n, int yy, int x, int c) {
-    const int y0 = a.bounds[2 * yy], cnt = a.bounds[2 * yy + 1];
-    const int* k = a.kk + (long)yy * a.ksize;
-    const uint8_t* sp = a.src + ((n * a.H + y0) * a.OW + x) * a.C + c;
+    const int o = a.xfirst ? yy : x;                                   // the output sample along the axis of this pass
+    const int y0 = a.bounds[2 * o], cnt = a.bounds[2 * o + 1];
+    const int* k = a.kk + (long)o * a.ksize;
+    const uint8_t* sp = a.xfirst ? a.src + ((n * a.H + y0) * a.OW + x) * a.C + c : a.src + ((n * a.OH + yy) * a.W + y0) * a.C + c;
     int acc = 1 << 21;
-    const long rs = (long)a.OW * a.C;
+    const long rs = a.xfirst ? (long)a.OW * a.C : (long)a.C;
     for (int t = 0; t < cnt; ++t) acc += (int)sp[t * rs] * k[t];
     acc >>= 22;
     const float v = (float)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
@@ -164,8 +191,12 @@ extern "C" int tlxmi_preprocess_linear_u8(const tlxmi_preproc_desc* d, const voi
     return check_launch("preprocess_linear_u8");
 }
 
+// Pillow's Image.resize: a very tall image that shrinks vertically gets its vertical pass first
+static bool pre_vertical_first(const tlxmi_preproc_desc* d) { return (long long)d->H > (long long)d->W * 100 && d->out_h < d->H; }
+
 extern "C" size_t tlxmi_preprocess_u8_workspace_bytes(const tlxmi_preproc_desc* d) {
-    if (!d || d->N <= 0 || d->H <= 0 || d->out_w <= 0 || d->C <= 0) return 0;
+    if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->out_h <= 0 || d->out_w <= 0 || d->C <= 0) return 0;
+    if (pre_vertical_first(d)) return (size_t)d->N * d->out_h * d->W * d->C;
     return (size_t)d->N * d->H * d->out_w * d->C;
 }
 
@@ -184,15 +215,22 @@ extern "C" int tlxmi_preprocess_u8(const tlxmi_preproc_desc* d, const void* imag
     TLXMI_REQUIRE((long long)d->N * d->H * (d->W > d->out_w ? d->W : d->out_w) * d->C < (1ll << 40), TLXMI_ERR_UNSUPPORTED, "preprocess_u8: batch too large");
     hipStream_t st = as_stream(stream);
     const long rows = (long)d->N * d->H;
-    {
+    const bool vfirst = pre_vertical_first(d);
+    if (vfirst) {
+        const long total = (long)d->N * d->out_h * d->W;
+        const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+        hipLaunchKernelGGL(resize_v_u8_kernel, dim3(grid), dim3(256), 0, st, (const uint8_t*)images, (uint8_t*)workspace, ybounds, yk, (long)d->N,
+                           d->H, d->out_h, d->W, d->C, d->kh);
+    } else {
         const long total = rows * d->out_w;
         const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
         hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid), dim3(256), 0, st, (const uint8_t*)images, (uint8_t*)workspace, xbounds, xk, rows,
                            d->W, d->out_w, d->C, d->kw);
     }
     PreArgs a;
-    a.src = (const uint8_t*)workspace; a.bounds = ybounds; a.kk = yk; a.mean = mean; a.std_ = std_; a.out = out;
-    a.N = d->N; a.H = d->H; a.OH = d->out_h; a.OW = d->out_w; a.C = d->C; a.ksize = d->kh; a.layout = d->layout;
+    a.src = (const uint8_t*)workspace; a.bounds = vfirst ? xbounds : ybounds; a.kk = vfirst ? xk : yk; a.mean = mean; a.std_ = std_; a.out = out;
+    a.N = d->N; a.H = d->H; a.OH = d->out_h; a.OW = d->out_w; a.C = d->C; a.ksize = vfirst ? d->kw : d->kh; a.layout = d->layout;
+    a.xfirst = vfirst ? 0 : 1; a.W = d->W;
     a.b = d->fold_b; a.cpad = d->cpad; a.normalize = d->normalize;
     const long total = d->layout == 2 ? (long)d->N * (d->out_h / d->fold_b) * (d->out_w / d->fold_b) : (long)d->N * d->out_h * d->out_w;
     const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);

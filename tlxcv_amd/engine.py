@@ -564,6 +564,9 @@ def preprocess_u8(images, size, mean=None, std=None, layout="CHW", dtype=torch.f
     """uint8 HWC images (N,H,W,C) on the device -> Resize(size) -> Normalize(mean, std) (or /255 without) -> ToTensor,
     one call (tlxmi_preprocess_u8), bit-identical to the host pipeline of tlx.vision.transforms.  layout 'CHW' -> (N,C,h,w),
     'HWC' -> (N,h,w,C); fold=b -> the b x b space-to-depth NHWC image the stem kernels read ((N,h/b,w/b,pad(b*b*C)))."""
+    from .tlx.vision.transforms import resample
+    if interpolation not in resample.SUPPORTED:
+        raise RuntimeError(f"preprocess_u8: interpolation {interpolation!r} is not supported (supported: {', '.join(resample.SUPPORTED)})")
     need_gpu(images, "images")
     if images.dtype != torch.uint8 or images.dim() != 4:
         raise RuntimeError("preprocess_u8: a (N, H, W, C) uint8 tensor is expected")

@@ -38,6 +38,10 @@ class Compose:
         if plan is None:
             raise NotImplementedError("Compose.batch: only [Resize, Normalize, ToTensor] / [Resize, ToTensor] run on the device")
         rs, nm, tt = plan
+        from . import resample
+        if rs.interpolation not in resample.SUPPORTED:      # before the upload: the same error with and without a GPU
+            raise RuntimeError(f"Compose.batch: interpolation {rs.interpolation!r} is not supported on the device "
+                               f"(supported: {', '.join(resample.SUPPORTED)})")
         if isinstance(images, torch.Tensor):
             t = images
         else:

@@ -22,10 +22,13 @@ def _bicubic(x, a=-0.5):
 
 
 _FILTERS["bicubic"] = (2.0, _bicubic)
+SUPPORTED = tuple(sorted(k for k, v in _FILTERS.items() if v is not None))      # the filters with a coefficient table
 
 
 def coefficients(in_size, out_size, interpolation="bilinear"):
     """-> (bounds int32 [out_size][2] = (xmin, count), kk int32 [out_size][ksize]) for one axis, full-image box."""
+    if _FILTERS.get(interpolation) is None:       # "nearest" has no coefficient table: PIL's own path, on the host
+        raise RuntimeError(f"resample.coefficients: interpolation {interpolation!r} is not supported (supported: {', '.join(SUPPORTED)})")
     support0, filt = _FILTERS[interpolation]
     scale = float(in_size) / float(out_size)
     filterscale = scale if scale >= 1.0 else 1.0
@@ -73,4 +76,12 @@ def resize_u8_numpy(img, size, interpolation="bilinear"):
             acc = np.tensordot(kk[xx, :n].astype(np.int64), src[x0:x0 + n], axes=(0, 0)) + (1 << (PRECISION_BITS - 1))
             out[xx] = np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
         return np.moveaxis(out, 0, axis)
+    if vertical_first(H, W, oh):
+        return one_axis(one_axis(a, H, oh, 0), W, ow, 1)
     return one_axis(one_axis(a, W, ow, 1), H, oh, 0)
+
+
+def vertical_first(in_h, in_w, out_h):
+    """Pillow's Image.resize runs the vertical pass first on a very tall image that shrinks vertically; the uint8 rounding between the
+    passes makes the order visible in the result (tlxmi_preprocess_u8 applies the same rule)."""
+    return in_h > in_w * 100 and out_h < in_h
